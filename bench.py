@@ -14,7 +14,7 @@ value    : ranks * steps * 1024 * 25 344 coded bits / wall time (max over ranks)
 scaling  : weak -- every rank decodes its own 1024 blocks; code blocks are independent, there is no
            collective on the data path (results are gathered once, outside the timed region).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -326,6 +326,8 @@ def main():
     ap.add_argument("--kernel", type=int, default=0, help="0 = best kernel for the code, 1 = generic kernel")
     ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling slot measurement (configs[4])")
     ap.add_argument("--no-chain", action="store_true", help="skip the chain_roofline measurement (de-matching kernel, configs[4])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -438,6 +440,13 @@ def main():
     # ---- headline: fixed work (all 9 passes) ----------------------------------------------------------
     dt, kern_ms = timed(llr_fixed, args.steps, args.warmup)
     per_rank_ms_per_step = list(timed.per_rank_ms)
+    if args.dump_outputs and rank == 0:
+        # the headline's last step, as a caller of LDPCdecoder_batch receives it: the packed hard decisions of every block
+        # and its pass count (inputs are seeded, so two builds can be compared output for output; 13.4 MB as float32)
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        np.save(dump / "decoded_bits.npy", out.cpu().numpy().astype(np.float32))
+        np.save(dump / "n_iter.npy", n_iter.cpu().numpy().astype(np.float32))
     passes_fixed = float(n_iter.float().mean().item())
     value = world * args.steps * BATCH * N_TX / dt / 1e9
     kern_avg_s = float(np.mean(kern_ms)) / 1e3

@@ -6,6 +6,7 @@ library can only be BUILT in the development container.  Once built it travels t
 the committed fixtures tests/golden/ref_*.npz (tools/make_ref_fixtures.py) carry its outputs everywhere.
 """
 import ctypes as C
+import os
 import subprocess
 from pathlib import Path
 
@@ -21,9 +22,21 @@ CHECK_CRC_T = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint8)
 _lib = None
 
 
+def readable(path):
+    """True when `path` exists and this user may read it (a tree under another user's home raises instead of answering)."""
+    try:
+        return path.exists() and os.access(path, os.R_OK)
+    except OSError:
+        return False
+
+
+def reference_present():
+    return readable(REFERENCE / "openair1/PHY/CODING/nrLDPC_encoder/ldpc_generate_coefficient.c")
+
+
 def build():
     """(Re)build oracle/_ref when the reference tree is present; no-op otherwise."""
-    if (REFERENCE / "openair1/PHY/CODING/nrLDPC_encoder/ldpc_generate_coefficient.c").exists():
+    if reference_present():
         subprocess.run(["make", "-C", str(PIN_DIR)], check=True, capture_output=True)
     return LIB_PATH
 

@@ -1,8 +1,9 @@
 """38.212 base-graph tables and the code descriptors built from them (CPU only).
 
-When the reference tree is present (development container) the tables are cross-checked against BOTH copies the
-reference holds as data: nrLDPC_decoder_LYC/bgs/BG*_I* (the generator's source) and, independently formatted,
-nrLDPC_decoder/nrLDPC_lut.h (circShift_*, posBnInCnProcBuf_*) + nrLDPCdecoder_defs.h (group sizes)."""
+The tables are cross-checked against BOTH copies the reference holds as data: nrLDPC_decoder_LYC/bgs/BG*_I* (the
+generator's source) and, independently formatted, nrLDPC_decoder/nrLDPC_lut.h (circShift_*, posBnInCnProcBuf_*) +
+nrLDPCdecoder_defs.h (group sizes).  The numbers read from the latter travel as tests/golden/ref_tables.npz
+(tools/make_ref_table_fixtures.py); where the reference tree is readable the fixture is re-read from it and compared."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import ref_lib as RL
 
 REF = Path("/root/reference/openair1/PHY/CODING")
 RATES = {1: (13, 23, 89), 2: (15, 13, 23)}
@@ -87,15 +89,45 @@ def _parse_arrays(text, pattern):
     return out
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree not present (development container only)")
-def test_tables_against_reference_lut(emul):
+def reference_table_data():
+    """The reference's table data as arrays: circShift_BG*_Z*_CNG* / posBnInCnProcBuf_BG*_CNG* (nrLDPC_lut.h),
+    lut_numCnInCnGroups_BG*_R* / lut_numBnInBnGroups_BG*_R* (nrLDPCdecoder_defs.h), index_k0 (nr_rate_matching.c)."""
     lut = (REF / "nrLDPC_decoder" / "nrLDPC_lut.h").read_text()
     defs = (REF / "nrLDPC_decoder" / "nrLDPCdecoder_defs.h").read_text()
-    shifts = _parse_arrays(lut, r"circShift_BG(\d)_Z(\d+)_CNG(\d+)")
-    posbn = _parse_arrays(lut, r"posBnInCnProcBuf_BG(\d)_CNG(\d+)")
-    ncn = {}
-    for m in re.finditer(r"lut_numCnInCnGroups_BG(\d)_R(\d+)\[[^\]]*\]\s*=\s*\{([^}]*)\}", defs):
-        ncn[(int(m.group(1)), int(m.group(2)))] = [int(v) for v in re.findall(r"\d+", m.group(3))]
+    rm = (REF / "nr_rate_matching.c").read_text()
+    data = {}
+    for (BG, Z, d), rows in _parse_arrays(lut, r"circShift_BG(\d)_Z(\d+)_CNG(\d+)").items():
+        data[f"circShift_BG{BG}_Z{Z}_CNG{d}"] = np.array(rows, np.int32)
+    for (BG, d), rows in _parse_arrays(lut, r"posBnInCnProcBuf_BG(\d)_CNG(\d+)").items():
+        data[f"posBnInCnProcBuf_BG{BG}_CNG{d}"] = np.array(rows, np.int32)
+    for name in ("numCnInCnGroups", "numBnInBnGroups"):
+        for m in re.finditer(r"lut_%s_BG(\d)_R(\d+)\[[^\]]*\]\s*=\s*\{([^}]*)\}" % name, defs):
+            data[f"{name}_BG{m.group(1)}_R{m.group(2)}"] = np.array([int(v) for v in re.findall(r"\d+", m.group(3))], np.int32)
+    m = re.search(r"index_k0\[2\]\[4\]\s*=\s*\{\{([^}]*)\},\s*\{([^}]*)\}\}", rm)
+    data["index_k0"] = np.array([[int(v) for v in re.findall(r"\d+", m.group(i))] for i in (1, 2)], np.int32)
+    return data
+
+
+def _reference_tables():
+    """tests/golden/ref_tables.npz; equal to what the reference tree holds wherever that tree is readable"""
+    with np.load(GOLDEN_DIR / "ref_tables.npz") as f:
+        stored = {k: f[k] for k in f.files}
+    if RL.readable(REF / "nrLDPC_decoder" / "nrLDPC_lut.h"):
+        live = reference_table_data()
+        assert sorted(live) == sorted(stored)
+        for k in live:
+            assert np.array_equal(live[k], stored[k]), k
+    return stored
+
+
+def test_tables_against_reference_lut(emul):
+    data = _reference_tables()
+    shifts = {tuple(k[len("circShift_BG"):].replace("_Z", " ").replace("_CNG", " ").split()): v.tolist()
+              for k, v in data.items() if k.startswith("circShift_")}
+    posbn = {tuple(k[len("posBnInCnProcBuf_BG"):].split("_CNG")): v.tolist()
+             for k, v in data.items() if k.startswith("posBnInCnProcBuf_")}
+    ncn = {(int(k[len("numCnInCnGroups_BG")]), int(k.split("_R")[1])): v.tolist()
+           for k, v in data.items() if k.startswith("numCnInCnGroups_")}
     groups = {1: [3, 4, 5, 6, 7, 8, 9, 10, 19], 2: [3, 4, 5, 6, 8, 10]}
     checked = 0
     for BG in (1, 2):
@@ -152,15 +184,16 @@ def test_product_and_oracle_tables_come_from_two_routes_and_agree():
 GOLDEN_DIR = ROOT / "tests" / "golden"
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree not present (development container only)")
 def test_bit_node_side_and_k0_against_reference_data(emul):
     """The bit-node side of the reference's tables, read as data: lut_numBnInBnGroups_BG*_R* (nrLDPCdecoder_defs.h: how
     many columns of each degree a rate mode has) against the column degrees of the oracle's / product's graph, and
     index_k0 (nr_rate_matching.c:34) against the k0 the oracle and the product compute."""
-    defs = (REF / "nrLDPC_decoder" / "nrLDPCdecoder_defs.h").read_text()
-    for m in re.finditer(r"lut_numBnInBnGroups_BG(\d)_R(\d+)\[[^\]]*\]\s*=\s*\{([^}]*)\}", defs):
-        BG, R = int(m.group(1)), int(m.group(2))
-        ref = [int(v) for v in re.findall(r"\d+", m.group(3))]           # ref[d-1] = columns of degree d
+    data = _reference_tables()
+    n_modes = 0
+    for key in sorted(k for k in data if k.startswith("numBnInBnGroups_")):
+        BG, R = int(key[len("numBnInBnGroups_BG")]), int(key.split("_R")[1])
+        ref = data[key].tolist()                                         # ref[d-1] = columns of degree d
+        n_modes += 1
         for Z in (384, 208, 6):
             g = O.graph(BG, Z, R)
             deg = np.bincount(np.asarray(g.col[:g.nedges]), minlength=g.ncols)
@@ -168,9 +201,8 @@ def test_bit_node_side_and_k0_against_reference_data(emul):
             assert got == ref, (BG, R, Z)
             p = product_graph(emul, BG, Z, R)
             assert np.array_equal(np.bincount(p["col"], minlength=p["ncols"]), deg)
-    rm = (REF / "nr_rate_matching.c").read_text()
-    m = re.search(r"index_k0\[2\]\[4\]\s*=\s*\{\{([^}]*)\},\s*\{([^}]*)\}\}", rm)
-    k0 = [[int(v) for v in re.findall(r"\d+", m.group(i))] for i in (1, 2)]
+    assert n_modes == 6
+    k0 = data["index_k0"].tolist()
     assert k0 == [[0, 17, 33, 56], [0, 13, 25, 43]]
     import openairinterface5g_amd as pkg
     for BG in (1, 2):
