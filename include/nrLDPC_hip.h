@@ -278,6 +278,28 @@ void nrLDPC_hip_host_free(void *p);
 int32_t nrLDPC_hip_host_register(void *p, uint64_t bytes);
 int32_t nrLDPC_hip_host_unregister(void *p);
 /* ---------------------------------------------------------------------------------------------------
+ * Codeword scrambling (38.211 5.2.1 Gold sequence, 6.3.1.1 PUSCH / 7.3.1.1 PDSCH): the reference's nr_codeword_scrambling()
+ * and nr_codeword_unscrambling() (openair1/PHY/NR_TRANSPORT/nr_scrambling.c:27-78) on the GPU, with
+ * c_init = n_RNTI * 2^15 + q * 2^14 + Nid (PUSCH: q = 0).  Word w of the sequence holds c(32w + k) in bit k.
+ *   scrambling:   `in` = `size` bytes holding one bit each (bit 0 of a byte, as the reference reads them: the output of
+ *                 nrLDPC_hip_dlsch_encode); out[w] bit k = in[32w + k] ^ c(32w + k), ceil(size/32) words.  The bits behind
+ *                 `size` in the last word are 0 (the reference leaves its input's padding XOR c there).
+ *   unscrambling: `size` int16 LLRs negated in place where c = 1, as the reference's multiplication by -1 does (-32768 stays
+ *                 -32768).  Only [0, size) is touched; the reference also negates up to 31 values behind `size`.
+ * mem = NRLDPC_HIP_MEM_HOST (synchronous) or NRLDPC_HIP_MEM_DEVICE (enqueued on `stream`, NULL = the default stream; `in`
+ * and `out` / `llr` in device memory -- hipMalloc or managed -- of one GPU, which runs the kernel).
+ * 0, or negative -- before anything is enqueued or written -- for n_RNTI > 0xFFFF, Nid > 1023, q > 1, size > 2^21, another
+ * mem value, a NULL buffer or (DEVICE) a buffer that is not device memory of the GPU `in` is on; nrLDPC_hip_last_error()
+ * names the reason.
+ * These are the separate passes over a codeword; scrambling inside the transport-block chain calls is not provided.
+ * gold_words: words first_word .. first_word + n_words - 1 of the sequence of c_init (c_init < 2^31, first_word < 2^17 - 50)
+ * on the host -- no GPU involved; the jump-ahead the kernels use, for checking them.  0 / -1. */
+int32_t nrLDPC_hip_codeword_scrambling(const uint8_t *in, uint32_t size, uint8_t q, uint32_t Nid, uint32_t n_RNTI,
+                                       uint32_t *out, int32_t mem, void *stream);
+int32_t nrLDPC_hip_codeword_unscrambling(int16_t *llr, uint32_t size, uint8_t q, uint32_t Nid, uint32_t n_RNTI,
+                                         int32_t mem, void *stream);
+int32_t nrLDPC_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out);
+/* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one
  * segment per call, rate (de)matching + (de)interleaving + HARQ combining inside, soft buffers kept on the device per

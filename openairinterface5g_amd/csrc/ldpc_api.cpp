@@ -25,6 +25,7 @@
 #include "ldpc_graph.h"
 #include "ldpc_kernels.h"
 #include "nr_coding_host.h"
+#include "nr_gold.h"
 #include "tb_chain.h"
 #include "ldpc_enc_packed_core.h"
 
@@ -1495,3 +1496,4 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "tb_api.inc.cpp"
 #include "dec_jobs.inc.cpp"
 #include "tb_offload.inc.cpp"
+#include "scrambling_api.inc.cpp"

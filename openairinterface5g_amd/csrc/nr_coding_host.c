@@ -2,6 +2,7 @@
  * nr_coding_host.c -- see nr_coding_host.h.  Plain C, results identical to the reference functions named there.
  */
 #include "nr_coding_host.h"
+#include "nr_gold.h"
 
 int nr_hip_segmentation(uint32_t B, int BG, nr_hip_seg_t *s)
 {
@@ -147,4 +148,24 @@ int nr_hip_check_crc(const uint8_t *decoded_bytes, uint32_t n, uint8_t crc_type)
   for (uint32_t i = 0; i < L; i++)
     stored = (stored << 8) | decoded_bytes[(n >> 3) - L + i];
   return (reg >> (32 - 8 * L)) == stored;
+}
+
+/* jump to the first word (nr_gold.h), then one step per word */
+int nr_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out)
+{
+  if (c_init >> 31)
+    return NR_HIP_GOLD_BAD_C_INIT;
+  if (first_word >= NR_GOLD_MAX_FIRST_WORD)
+    return NR_HIP_GOLD_BAD_FIRST_WORD;
+  if (n_words && !out)
+    return NR_HIP_GOLD_NULL_OUT;
+  const nr_gold_tables_t t = nr_gold_make_tables();
+  uint32_t x1, x2;
+  nr_gold_jump(&t, c_init, first_word, &x1, &x2);
+  for (uint32_t w = 0; w < n_words; w++) {
+    out[w] = x1 ^ x2;
+    x1 = nr_gold_step1(x1);
+    x2 = nr_gold_step2(x2);
+  }
+  return 0;
 }

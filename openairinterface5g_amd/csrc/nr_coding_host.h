@@ -65,6 +65,12 @@ uint32_t nr_hip_first_tx_columns(const nr_hip_rm_t *g, uint32_t E, uint32_t Zc);
 /* check_crc() of openair1/PHY/CODING/crc_byte.c:314-380 for any n: 1 when the CRC of the first n - 8 L bits (MSB first,
  * L = 3 / 3 / 2 / 1 bytes for crc_type 0..3) equals the L bytes in front of byte n >> 3; 0 otherwise and for an unknown type */
 int nr_hip_check_crc(const uint8_t *decoded_bytes, uint32_t n, uint8_t crc_type);
+/* words first_word .. first_word + n_words - 1 of the Gold sequence of c_init (nr_gold.h; what lte_gold_generic() returns
+ * from its second call on, word 0 first): 0, or one of the negative codes below (nothing written) */
+#define NR_HIP_GOLD_BAD_C_INIT -1     /* c_init >= 2^31 */
+#define NR_HIP_GOLD_BAD_FIRST_WORD -2 /* first_word >= NR_GOLD_MAX_FIRST_WORD */
+#define NR_HIP_GOLD_NULL_OUT -3       /* n_words > 0 and out NULL */
+int nr_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,131 @@
+/*
+ * scrambling_api.inc.cpp -- codeword (un)scrambling entry points (included at the end of ldpc_api.cpp; shares its library
+ * state).  The sequence itself: nr_gold.h, on the GPU tb_scrambling.hip, on the host nr_hip_gold_words (nr_coding_host.c).
+ */
+
+namespace {
+
+#define NR_SCR_MAX_BITS (1u << 21) /* one codeword: G <= 1.5 Mbit (the sequence's jump tables reach 2^17 - 50 words) */
+
+/* 38.211 7.3.1.1 / 6.3.1.1: n_RNTI < 2^16, n_ID < 1024, q = codeword 0 / 1 */
+int scr_validate(uint32_t n_rnti, uint32_t q, uint32_t n_id)
+{
+  if (n_rnti > 0xffffu)
+    return set_error("scrambling: n_RNTI above 0xFFFF");
+  if (n_id > 1023u)
+    return set_error("scrambling: n_ID above 1023");
+  if (q > 1u)
+    return set_error("scrambling: q must be 0 or 1");
+  return 0;
+}
+
+int scr_check_call(const void *p, uint32_t size, int32_t mem, uint32_t n_rnti, uint32_t q, uint32_t n_id)
+{
+  if (scr_validate(n_rnti, q, n_id) != 0)
+    return -1;
+  if (size > NR_SCR_MAX_BITS)
+    return set_error("scrambling: size above 2^21 bits");
+  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
+    return set_error("scrambling: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (size && !p)
+    return set_error("null argument");
+  return 0;
+}
+
+/* DEVICE mem: the HIP ordinal of the GPU whose memory holds p (hipMalloc or managed), -1 for anything else */
+int scr_device_ordinal(const void *p)
+{
+  hipPointerAttribute_t at;
+  if (p && hipPointerGetAttributes(&at, p) == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged))
+    return at.device;
+  (void)hipGetLastError();
+  return -1;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t nrLDPC_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out)
+{
+  /* the arguments are checked once, by nr_hip_gold_words (nr_coding_host.c); here its code becomes the error text */
+  switch (nr_hip_gold_words(c_init, first_word, n_words, out)) {
+    case 0: return 0;
+    case NR_HIP_GOLD_BAD_C_INIT: return set_error("gold_words: c_init must be below 2^31");
+    case NR_HIP_GOLD_BAD_FIRST_WORD: return set_error("gold_words: first_word must be below 2^17 - 50");
+    case NR_HIP_GOLD_NULL_OUT: return set_error("null argument");
+    default: return set_error("gold_words: invalid arguments");
+  }
+}
+
+int32_t nrLDPC_hip_codeword_scrambling(const uint8_t *in, uint32_t size, uint8_t q, uint32_t Nid, uint32_t n_RNTI, uint32_t *out,
+                                       int32_t mem, void *stream)
+{
+  if (scr_check_call(in, size, mem, n_RNTI, q, Nid) != 0)
+    return -1;
+  if (size && !out)
+    return set_error("null argument");
+  if (size == 0)
+    return 0;
+  const uint32_t c_init = nr_gold_c_init(n_RNTI, q, Nid), out_bytes = 4u * ((size + 31u) >> 5);
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    const int ord = scr_device_ordinal(in);
+    if (ord < 0 || scr_device_ordinal(out) != ord)
+      return set_error("scrambling: DEVICE mem needs `in` and `out` in device memory of one GPU");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    HIP_TRY(nr_launch_scramble_bits(in, size, c_init, out, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  if (c.ensure(align_up(size, 16), out_bytes) != 0)
+    return -1;
+  memcpy(c.h_in, in, size);
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, size, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(nr_launch_scramble_bits(c.d_in, size, c_init, reinterpret_cast<uint32_t *>(c.d_out), c.stream));
+  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  memcpy(out, c.h_out, out_bytes);
+  return 0;
+}
+
+int32_t nrLDPC_hip_codeword_unscrambling(int16_t *llr, uint32_t size, uint8_t q, uint32_t Nid, uint32_t n_RNTI, int32_t mem, void *stream)
+{
+  if (scr_check_call(llr, size, mem, n_RNTI, q, Nid) != 0)
+    return -1;
+  if (size == 0)
+    return 0;
+  const uint32_t c_init = nr_gold_c_init(n_RNTI, q, Nid);
+  const size_t bytes = (size_t)size * sizeof(int16_t);
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    const int ord = scr_device_ordinal(llr);
+    if (ord < 0)
+      return set_error("unscrambling: DEVICE mem needs `llr` in device memory");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    HIP_TRY(nr_launch_unscramble_llr(llr, size, c_init, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  if (c.ensure(align_up(bytes, 16), 0) != 0)
+    return -1;
+  memcpy(c.h_in, llr, bytes);
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, bytes, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(nr_launch_unscramble_llr(reinterpret_cast<int16_t *>(c.d_in), size, c_init, c.stream));
+  HIP_TRY(hipMemcpyAsync(c.h_in, c.d_in, bytes, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  memcpy(llr, c.h_in, bytes);
+  return 0;
+}
+
+} /* extern "C" */

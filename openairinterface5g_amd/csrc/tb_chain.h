@@ -70,6 +70,10 @@ struct ldpc_dec_args;
 hipError_t tb_launch_rx_fused(const struct ldpc_dec_args &a, const tb_rx_fused_args &x, int n_threads, int lds_bytes, uint32_t n_jobs,
                               hipStream_t s);
 hipError_t tb_rx_fused_init(void);
+/* codeword scrambling (tb_scrambling.hip, 38.211 5.2.1 / 6.3.1.1 / 7.3.1.1) with the sequence of c_init: out[ceil(size/32)] words
+ * from `size` bytes holding a bit each (bit 0 of a byte) / `size` int16 LLRs negated in place where the sequence has a one */
+hipError_t nr_launch_scramble_bits(const uint8_t *in, uint32_t size, uint32_t c_init, uint32_t *out, hipStream_t s);
+hipError_t nr_launch_unscramble_llr(int16_t *llr, uint32_t size, uint32_t c_init, hipStream_t s);
 /* reassembly per segment (payload copy + partial TB CRC into acc[tb], zero on entry and on exit), then per-TB verdict */
 hipError_t tb_launch_rx_assemble(const tb_rx_tb_job *jobs, uint32_t n_tb, const tb_rx_seg_job *segs, uint32_t n_seg,
                                  const int32_t *n_iter, uint8_t *scratch, uint8_t *payload, uint8_t *ack, int32_t *iter_max,

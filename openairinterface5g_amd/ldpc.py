@@ -702,3 +702,85 @@ def ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter=8, st
     _check(L.nrLDPC_hip_ulsch_decode(C.byref(b)), "nrLDPC_hip_ulsch_decode")
     for i, t in enumerate(tbs):
         t["llrLen"] = arr[i].llrLen
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Codeword scrambling (include/nrLDPC_hip.h: nrLDPC_hip_codeword_scrambling / _unscrambling / nrLDPC_hip_gold_words)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_codeword_scrambling", "nrLDPC_hip_codeword_unscrambling", "nrLDPC_hip_gold_words"]
+
+
+def _scr_lib():
+    L = load_library()
+    L.nrLDPC_hip_gold_words.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.nrLDPC_hip_gold_words.restype = C.c_int32
+    L.nrLDPC_hip_codeword_scrambling.argtypes = [C.c_void_p, C.c_uint32, C.c_uint8, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_codeword_scrambling.restype = C.c_int32
+    L.nrLDPC_hip_codeword_unscrambling.argtypes = [C.c_void_p, C.c_uint32, C.c_uint8, C.c_uint32, C.c_uint32, C.c_int32,
+                                                   C.c_void_p]
+    L.nrLDPC_hip_codeword_unscrambling.restype = C.c_int32
+    return L
+
+
+def gold_c_init(n_rnti, q, n_id):
+    """c_init of PDSCH / PUSCH data scrambling (38.211 7.3.1.1 / 6.3.1.1)"""
+    return (n_rnti << 15) + (q << 14) + n_id
+
+
+def gold_words(c_init, first_word, n_words):
+    """uint32[n_words]: words first_word .. of the Gold sequence of c_init (bit k of word w = c(32w + k)); host only."""
+    out = np.zeros(max(n_words, 1), np.uint32)
+    _check(_scr_lib().nrLDPC_hip_gold_words(c_init, first_word, n_words, out.ctypes.data), "nrLDPC_hip_gold_words")
+    return out[:n_words]
+
+
+def _scr_size(size, n):
+    """the element count a scrambling call covers: all of the array, or its first `size` elements"""
+    n_sz = n if size is None else int(size)
+    if not 0 <= n_sz <= n:
+        raise ValueError(f"size {n_sz} outside the array's {n} elements")
+    return n_sz
+
+
+def codeword_scrambling(bits, q, n_id, n_rnti, out=None, size=None, stream=None):
+    """nr_codeword_scrambling: `bits` one bit per byte, the first `size` of them (all by default).  numpy uint8 -> host call,
+    returns uint32[ceil(size/32)]; torch uint8 CUDA tensor -> device call enqueued on `stream` into `out`, a contiguous
+    torch int32 / uint32 CUDA tensor of at least that many words on the same GPU; returns `out`."""
+    L = _scr_lib()
+    if isinstance(bits, np.ndarray):
+        assert bits.dtype == np.uint8
+        src = np.ascontiguousarray(bits).reshape(-1)
+        n = _scr_size(size, src.size)
+        res = np.zeros(max((n + 31) // 32, 1), np.uint32)
+        _check(L.nrLDPC_hip_codeword_scrambling(src.ctypes.data, n, q, n_id, n_rnti, res.ctypes.data, MEM_HOST, None),
+               "nrLDPC_hip_codeword_scrambling")
+        return res[:(n + 31) // 32]
+    import torch
+    assert bits.is_cuda and bits.dtype == torch.uint8 and bits.is_contiguous()
+    n = _scr_size(size, bits.numel())
+    assert out is not None and out.is_cuda and out.device == bits.device and out.is_contiguous()
+    assert out.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and out.numel() >= (n + 31) // 32
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_codeword_scrambling(bits.data_ptr(), n, q, n_id, n_rnti, out.data_ptr(), MEM_DEVICE, s),
+           "nrLDPC_hip_codeword_scrambling")
+    return out
+
+
+def codeword_unscrambling(llr, q, n_id, n_rnti, size=None, stream=None):
+    """nr_codeword_unscrambling, in place on the first `size` int16 LLRs (all by default): numpy -> host call, torch CUDA
+    tensor -> device call enqueued on `stream`."""
+    L = _scr_lib()
+    if isinstance(llr, np.ndarray):
+        assert llr.dtype == np.int16 and llr.flags.c_contiguous
+        n = _scr_size(size, llr.size)
+        _check(L.nrLDPC_hip_codeword_unscrambling(llr.ctypes.data, n, q, n_id, n_rnti, MEM_HOST, None),
+               "nrLDPC_hip_codeword_unscrambling")
+        return llr
+    import torch
+    assert llr.is_cuda and llr.dtype == torch.int16 and llr.is_contiguous()
+    n = _scr_size(size, llr.numel())
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_codeword_unscrambling(llr.data_ptr(), n, q, n_id, n_rnti, MEM_DEVICE, s),
+           "nrLDPC_hip_codeword_unscrambling")
+    return llr
