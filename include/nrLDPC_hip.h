@@ -264,6 +264,23 @@ typedef struct nrLDPC_hip_tb_batch {
 } nrLDPC_hip_tb_batch_t;
 int32_t nrLDPC_hip_dlsch_encode(const nrLDPC_hip_tb_batch_t *b);
 int32_t nrLDPC_hip_ulsch_decode(const nrLDPC_hip_tb_batch_t *b);
+/* The same chain calls with data scrambling (38.211 7.3.1.1 / 6.3.1.1) inside; `scr` = host array of n_tb entries, one
+ * codeword per transport block, whose sequence starts at the block's codeword bit 0.
+ *   encode_scrambled: for each block ceil(G/32) uint32_t words at coded + coded_off (a byte offset, multiple of 4); bit k of
+ *     word w = f(32w + k) ^ c(32w + k) -- nrLDPC_hip_dlsch_encode followed by nrLDPC_hip_codeword_scrambling; the bits
+ *     behind G are 0 and nothing behind the last word is written.
+ *   decode_scrambled: every output (payload, ack, iter_max, llrLen, soft buffers) as nrLDPC_hip_codeword_unscrambling on the
+ *     block's G LLRs followed by nrLDPC_hip_ulsch_decode; the LLR array itself is only read.
+ * Every mem mode of the unscrambled calls.  Negative -- before anything is enqueued or written -- for a NULL scr,
+ * n_RNTI > 0xFFFF, Nid > 1023, q > 1, G > 2^21, (encode) coded_off % 4 != 0; nrLDPC_hip_last_error() names the reason. */
+typedef struct nrLDPC_hip_tb_scr {
+  uint32_t n_RNTI; /* <= 0xFFFF */
+  uint16_t Nid;    /* <= 1023 */
+  uint8_t q;       /* codeword index, 0 or 1; PUSCH: 0 */
+  uint8_t pad;
+} nrLDPC_hip_tb_scr_t; /* one per transport block; c_init = n_RNTI * 2^15 + q * 2^14 + Nid */
+int32_t nrLDPC_hip_dlsch_encode_scrambled(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr);
+int32_t nrLDPC_hip_ulsch_decode_scrambled(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr);
 /* Soft buffers kept by the library (NRLDPC_HIP_MEM_HARQ_LIBRARY).  release: forget one transport block's buffers (its HARQ
  * process ended) / all of them; read: copy int16 values [first, first + n) of a block's C x harq_stride soft values to host
  * memory (diagnostics and tests; a device-memory decode call that wrote them must have completed on its stream).  0, or -1
@@ -291,7 +308,8 @@ int32_t nrLDPC_hip_host_unregister(void *p);
  * 0, or negative -- before anything is enqueued or written -- for n_RNTI > 0xFFFF, Nid > 1023, q > 1, size > 2^21, another
  * mem value, a NULL buffer or (DEVICE) a buffer that is not device memory of the GPU `in` is on; nrLDPC_hip_last_error()
  * names the reason.
- * These are the separate passes over a codeword; scrambling inside the transport-block chain calls is not provided.
+ * These are the separate passes over a codeword; nrLDPC_hip_dlsch_encode_scrambled / nrLDPC_hip_ulsch_decode_scrambled
+ * scramble inside the transport-block chain calls.
  * gold_words: words first_word .. first_word + n_words - 1 of the sequence of c_init (c_init < 2^31, first_word < 2^17 - 50)
  * on the host -- no GPU involved; the jump-ahead the kernels use, for checking them.  0 / -1. */
 int32_t nrLDPC_hip_codeword_scrambling(const uint8_t *in, uint32_t size, uint8_t q, uint32_t Nid, uint32_t n_RNTI,

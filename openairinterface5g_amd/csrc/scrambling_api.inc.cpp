@@ -42,9 +42,63 @@ int scr_device_ordinal(const void *p)
   return -1;
 }
 
+/* the scrambled transport-block chain calls: every argument of the batch is checked before anything is enqueued */
+int scr_check_batch(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr, bool encode)
+{
+  if (!scr && b->n_tb)
+    return set_error("scrambled: scr is NULL");
+  for (uint32_t i = 0; i < b->n_tb; i++) {
+    if (scr_validate(scr[i].n_RNTI, scr[i].q, scr[i].Nid) != 0)
+      return -1;
+    if (b->tb[i].G > NR_SCR_MAX_BITS)
+      return set_error("scrambled: G above 2^21 bits");
+    if (encode && (b->tb[i].coded_off & 3u))
+      return set_error("encode_scrambled: coded_off must be a multiple of 4");
+  }
+  return 0;
+}
+
 } // namespace
 
 extern "C" {
+
+int32_t nrLDPC_hip_dlsch_encode_scrambled(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
+{
+  if (!b || !b->tb || !b->payload || !b->coded)
+    return set_error("null argument");
+  if (b->mem & ~NRLDPC_HIP_MEM_DEVICE)
+    return set_error("encode: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (scr_check_batch(b, scr, true) != 0)
+    return -1;
+  if (b->n_tb == 0)
+    return ensure_ready();
+  return tb_run_sharded(
+      b, [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) { return tb_tx_enqueue(b, tb0, n, staged, s, scr + tb0); },
+      [&](uint32_t, uint32_t n) { return tb_tx_finish(b, n); });
+}
+
+int32_t nrLDPC_hip_ulsch_decode_scrambled(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
+{
+  if (!b || !b->tb || !b->payload || !b->coded)
+    return set_error("null argument");
+  const bool harq_lib = (b->mem & NRLDPC_HIP_MEM_HARQ_LIBRARY) != 0;
+  if ((b->mem & ~(NRLDPC_HIP_MEM_DEVICE | NRLDPC_HIP_MEM_HARQ_DEVICE | NRLDPC_HIP_MEM_HARQ_LIBRARY)) ||
+      (harq_lib && (b->mem & NRLDPC_HIP_MEM_HARQ_DEVICE)))
+    return set_error("decode: invalid mem flags");
+  if ((!b->harq && !harq_lib) || !b->ack || !b->iter_max || b->harq_stride < 66 * 384)
+    return set_error("decode needs harq (stride >= 66*384), ack and iter_max buffers");
+  if (scr_check_batch(b, scr, false) != 0)
+    return -1;
+  if (b->n_tb == 0)
+    return ensure_ready();
+  return tb_run_sharded(
+      b,
+      [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) {
+        return (staged && !(b->mem & NRLDPC_HIP_MEM_DEVICE)) ? tb_rx_enqueue_host(b, tb0, n, scr + tb0)
+                                                              : tb_rx_enqueue(b, tb0, n, staged, s, nullptr, scr + tb0);
+      },
+      [&](uint32_t tb0, uint32_t n) { return tb_rx_finish(b, tb0, n); });
+}
 
 int32_t nrLDPC_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out)
 {

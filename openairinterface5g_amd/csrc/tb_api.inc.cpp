@@ -96,11 +96,12 @@ struct TbPlan {
   }
   uint64_t stamp = 0; /* LRU */
   /* the descriptors tb[0 .. n_tb) of a call (one device's share of the batch); salt = whatever else the plan depends on */
-  bool matches(const nrLDPC_hip_tb_t *tb, uint32_t n_tb, const uint64_t salt[3]) const
+  /* xb / xn: further bytes the plan depends on (the scrambled calls' nrLDPC_hip_tb_scr_t array), behind the descriptors */
+  bool matches(const nrLDPC_hip_tb_t *tb, uint32_t n_tb, const uint64_t salt[3], const void *xb = nullptr, size_t xn = 0) const
   {
     const size_t n = (size_t)n_tb * sizeof(nrLDPC_hip_tb_t);
-    return valid && key.size() == n + 32 && memcmp(key.data(), &n_tb, 4) == 0 && memcmp(key.data() + 8, salt, 24) == 0 &&
-           memcmp(key.data() + 32, tb, n) == 0;
+    return valid && key.size() == n + 32 + xn && memcmp(key.data(), &n_tb, 4) == 0 && memcmp(key.data() + 8, salt, 24) == 0 &&
+           memcmp(key.data() + 32, tb, n) == 0 && (xn == 0 || memcmp(key.data() + 32 + n, xb, xn) == 0);
   }
   /* any descriptor array as bytes (LDPCdecoder_jobs) */
   bool matches_raw(const void *d, size_t n, const uint64_t salt[3]) const
@@ -114,13 +115,15 @@ struct TbPlan {
     memcpy(key.data() + 32, d, n);
     valid = true;
   }
-  void remember(const void *tb_bytes, uint32_t n_tb, const uint64_t salt[3])
+  void remember(const void *tb_bytes, uint32_t n_tb, const uint64_t salt[3], const void *xb = nullptr, size_t xn = 0)
   {
     const size_t n = (size_t)n_tb * sizeof(nrLDPC_hip_tb_t);
-    key.assign(n + 32, 0);
+    key.assign(n + 32 + xn, 0);
     memcpy(key.data(), &n_tb, 4);
     memcpy(key.data() + 8, salt, 24);
     memcpy(key.data() + 32, tb_bytes, n);
+    if (xn)
+      memcpy(key.data() + 32 + n, xb, xn);
     valid = true;
   }
 };
@@ -133,10 +136,10 @@ struct TbPlan {
 struct TbPlanCache {
   TbPlan slot[TB_PLAN_SLOTS];
   uint64_t clock = 0;
-  TbPlan *find(const nrLDPC_hip_tb_t *tb, uint32_t n_tb, const uint64_t salt[3])
+  TbPlan *find(const nrLDPC_hip_tb_t *tb, uint32_t n_tb, const uint64_t salt[3], const void *xb = nullptr, size_t xn = 0)
   {
     for (TbPlan &p : slot)
-      if (p.matches(tb, n_tb, salt)) {
+      if (p.matches(tb, n_tb, salt, xb, xn)) {
         p.stamp = ++clock;
         return &p;
       }
@@ -439,7 +442,10 @@ struct TbExtent {
     }                                                                                        \
   } while (0)
 
-int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct)
+/* scr != nullptr (nrLDPC_hip_dlsch_encode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the chain's bit-per-byte output goes
+ * to scratch, and one more launch packs and scrambles every block into its ceil(G/32) words at coded + coded_off */
+int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
+                  const nrLDPC_hip_tb_scr_t *scr = nullptr)
 {
   hipStream_t s;
   if (tb_begin(s, s_direct, staged) != 0)
@@ -449,14 +455,21 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
   const nrLDPC_hip_tb_t *tbs = b->tb + tb0;
   TbCtx &c = tls_tb;
   const bool fused = ldpc_enc_is_packed() != 0;
-  const uint64_t salt[3] = {(fused ? 1u : 0u) | (tb_trunc_enabled() ? 2u : 0u), 0, 0};
-  TbPlan *hit = c.tx.find(tbs, ntb, salt);
+  /* bit 2: scrambled (its key also holds the scr bytes: a scrambled and an unscrambled plan never match) */
+  const uint64_t salt[3] = {(fused ? 1u : 0u) | (tb_trunc_enabled() ? 2u : 0u) | (scr ? 4u : 0u), 0, 0};
+  const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
+  TbPlan *hit = c.tx.find(tbs, ntb, salt, scr, scr_n);
   TbPlan &pl = hit ? *hit : c.tx.victim();
   if (!hit) {
     std::vector<tb_tx_tb_job> tbj(ntb);
     std::vector<tb_tx_seg_job> sj;
     std::vector<ldpc_enc_job> ej;
     std::vector<tb_crc_chunk_job> cj;
+    /* scrambled, three-kernel path: the bytes in scratch, then one packing launch (pj) */
+    std::vector<tb_scr_tb_job> pj(scr && !fused ? ntb : 0);
+    uint32_t max_g = 0;
+    uint32_t n_tickets = 0; /* scrambled, fused path: the words several segments share, and their parts */
+    size_t n_parts = 0;
     Arena ar;
     int enc_threads = 64, enc_lds = 0;
     TbExtent ex;
@@ -485,8 +498,21 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       tbj[i].B = B;
       tbj[i].crc_type = t.A > NR_HIP_MAX_PDSCH_TBS ? NR_HIP_CRC24_A : NR_HIP_CRC16;
       ex.add(ex.pay_lo, ex.pay_hi, (size_t)t.payload_off, (size_t)t.payload_off + t.A / 8);
-      ex.add(ex.cod_lo, ex.cod_hi, (size_t)t.coded_off, (size_t)t.coded_off + t.G);
-      ex.cod_sum += t.G;
+      /* scrambled: the caller's array takes the packed words.  Fused: the segment kernel stores them itself (out_off = the TB's
+       * first byte); three-kernel path: the bytes stay in scratch at byte_base for the packing launch */
+      const size_t out_len = scr ? (size_t)((t.G + 31u) / 32u) * 4u : (size_t)t.G;
+      const bool scr_bytes = scr && !fused;
+      const uint64_t byte_base = scr_bytes ? (uint64_t)ar.take(t.G + 16) : t.coded_off;
+      const size_t seg_first = sj.size();
+      if (scr_bytes) {
+        pj[i].in_off = byte_base;
+        pj[i].out_off = t.coded_off;
+        pj[i].G = t.G;
+        pj[i].c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
+        max_g = std::max(max_g, t.G);
+      }
+      ex.add(ex.cod_lo, ex.cod_hi, (size_t)t.coded_off, (size_t)t.coded_off + out_len);
+      ex.cod_sum += out_len;
       const uint32_t chunk0 = (uint32_t)cj.size();
       for (uint32_t fb = 0; fb < t.A / 8; fb += crc_chunk)
         cj.push_back(tb_crc_chunk_job{i, fb | (crc_chunk == TB_CRC_CHUNK_SMALL ? 0x80000000u : 0u)});
@@ -507,7 +533,11 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
           j.c_off = ar.take(sg.K / 8 + 4);
           j.d_off = ar.take(N);
         }
-        j.out_off = t.coded_off + r_offset;
+        j.out_off = (scr && fused) ? t.coded_off : byte_base + r_offset;
+        if (scr && fused) {
+          j.c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
+          j.bit_off = r_offset;
+        }
         j.r = r; j.C = sg.C; j.Kprime = sg.Kprime; j.L = sg.L; j.K = sg.K;
         j.E = nr_hip_get_E(t.G, sg.C, t.Qm, t.Nl, r);
         j.Qm = t.Qm;
@@ -543,6 +573,32 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         e.code = ce_seg->dev; e.in_off = j.c_off; e.out_off = j.d_off; e.Kb = (int32_t)sg.Kb; e.pad = 0;
         ej.push_back(e);
       }
+      if (scr && fused) {
+        /* words the block's segments share (tb_tx_settle_word): a segment's first word when it starts inside a word, its last
+         * word when it ends inside one and is not the block's last segment (behind G the last word is 0: complete) -- once
+         * per segment and word; each word gets a ticket and one part slot per segment that touches it */
+        std::map<uint32_t, std::vector<std::pair<size_t, int>>> shared;
+        for (size_t q = seg_first; q < sj.size(); q++) {
+          const uint32_t lo = sj[q].bit_off, hi = lo + sj[q].E;
+          const bool head = (lo & 31u) != 0, last = sj[q].r + 1 == sj[q].C;
+          if (head)
+            shared[lo >> 5].push_back({q, 0});
+          if (!last && (hi & 31u) && !(head && ((hi - 1) >> 5) == (lo >> 5)))
+            shared[(hi - 1) >> 5].push_back({q, 1});
+        }
+        for (const auto &kv : shared) {
+          const uint32_t tk = n_tickets++, p0 = (uint32_t)n_parts, n = (uint32_t)kv.second.size();
+          for (uint32_t k = 0; k < n; k++) {
+            tb_tx_seg_job &q = sj[kv.second[k].first];
+            if (kv.second[k].second == 0) {
+              q.h_ticket = tk; q.h_part = p0 + k; q.h_part0 = p0; q.h_n = n;
+            } else {
+              q.t_ticket = tk; q.t_part = p0 + k; q.t_part0 = p0; q.t_n = n;
+            }
+          }
+          n_parts += n;
+        }
+      }
     }
     const size_t n_seg = sj.size();
     const size_t o_tb = 0, o_seg = align_up(tbj.size() * sizeof(tb_tx_tb_job), 16),
@@ -550,10 +606,15 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
                  o_chk = o_enc + align_up(n_seg * sizeof(ldpc_enc_job), 16),
                  o_acc = o_chk + align_up(cj.size() * sizeof(tb_crc_chunk_job), 16),
                  /* CRC accumulators, uploaded as zeros: one per block (unfused path, atomics) / one per chunk (fused) */
-                 jobs_bytes = o_acc + align_up(std::max<size_t>(ntb, cj.size()) * sizeof(uint32_t), 16);
+                 o_scr = o_acc + align_up(std::max<size_t>(ntb, cj.size()) * sizeof(uint32_t), 16),
+                 o_tk = o_scr + align_up(pj.size() * sizeof(tb_scr_tb_job), 16),  /* tickets: uploaded as zeros, left zero */
+                 o_pt = o_tk + align_up((size_t)n_tickets * 4, 16),                /* parts */
+                 jobs_bytes = o_pt + align_up(n_parts * 4, 16);
     if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_bytes) != 0 || pl.jobs_d.ensure(jobs_bytes) != 0)
       return -1;
-    memset(c.jobs_h.p + o_acc, 0, jobs_bytes - o_acc);
+    memset(c.jobs_h.p + o_acc, 0, o_scr - o_acc);
+    memcpy(c.jobs_h.p + o_scr, pj.data(), pj.size() * sizeof(tb_scr_tb_job));
+    memset(c.jobs_h.p + o_tk, 0, jobs_bytes - o_tk);
     memcpy(c.jobs_h.p + o_chk, cj.data(), cj.size() * sizeof(tb_crc_chunk_job));
     memcpy(c.jobs_h.p + o_tb, tbj.data(), tbj.size() * sizeof(tb_tx_tb_job));
     memcpy(c.jobs_h.p + o_seg, sj.data(), n_seg * sizeof(tb_tx_seg_job));
@@ -568,13 +629,14 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       std::vector<size_t> len(ntb);
       for (uint32_t i = 0; i < ntb; i++) {
         off[i] = tbs[i].coded_off;
-        len[i] = tbs[i].G;
+        len[i] = scr ? (size_t)((tbs[i].G + 31u) / 32u) * 4u : (size_t)tbs[i].G;
       }
       pl.build_out_runs(off.data(), len.data(), ntb);
     }
-    pl.off[0] = o_tb; pl.off[1] = o_seg; pl.off[2] = o_enc; pl.off[3] = o_chk; pl.off[4] = o_acc;
+    pl.off[0] = o_tb; pl.off[1] = o_seg; pl.off[2] = o_enc; pl.off[3] = o_chk; pl.off[4] = o_acc; pl.off[5] = o_scr;
+    pl.off[6] = max_g; pl.off[7] = o_tk; pl.off[8] = o_pt;
     pl.threads[0] = enc_threads; pl.lds[0] = enc_lds;
-    pl.remember(tbs, ntb, salt);
+    pl.remember(tbs, ntb, salt, scr, scr_n);
   }
   if (c.scratch.ensure(pl.scratch_top + 16) != 0) /* (+16: the fused kernel reads whole dwords around a segment's bytes) */
     return -1;
@@ -583,6 +645,7 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
   const int enc_threads = pl.threads[0], enc_lds = pl.lds[0];
   const uint8_t *payload = b->payload;
   uint8_t *coded = static_cast<uint8_t *>(b->coded);
+  uint8_t *out_words = nullptr; /* scrambled, three-kernel path: where the packed words go (coded is then the scratch buffer) */
   if (staged) {
     const size_t pay_lo = pl.ext[0], pay_n = pl.ext[1] - pl.ext[0], cod_lo = pl.ext[2], cod_n = pl.ext[3] - pl.ext[2];
     if (c.io_payload.ensure(pay_n) != 0 || c.io_coded.ensure(cod_n) != 0)
@@ -598,6 +661,10 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     payload = c.io_payload.p - pay_lo;
     coded = c.io_coded.p - cod_lo;
   }
+  if (scr && !fused) {
+    out_words = coded;
+    coded = c.scratch.p; /* the segments' bytes: job out_off = scratch offsets */
+  }
   const tb_tx_tb_job *d_tb = reinterpret_cast<const tb_tx_tb_job *>(pl.jobs_d.p + o_tb);
   const tb_tx_seg_job *d_seg = reinterpret_cast<const tb_tx_seg_job *>(pl.jobs_d.p + o_seg);
   uint32_t *d_acc = reinterpret_cast<uint32_t *>(pl.jobs_d.p + o_acc);
@@ -610,8 +677,13 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
      * a launch that does not even fill the GPU four deep takes 512 and halves the rounds of its long stages */
     const int fused_threads = n_seg <= (size_t)4 * (size_t)G().n_cus ? 512 : enc_threads;
     TB_DEBUG_STAGE("tx: TB CRC launch");
-    HIP_TRY(tb_launch_tx_fused(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS, payload, coded,
-                               G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
+    if (scr)
+      HIP_TRY(tb_launch_tx_fused_scr(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS + TB_TX_FUSED_SCR_LDS, payload,
+                                     coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.off[7]),
+                                     reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.off[8]), s));
+    else
+      HIP_TRY(tb_launch_tx_fused(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS, payload, coded,
+                                 G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
     TB_DEBUG_STAGE("tx: fused segment launch");
   } else {
     HIP_TRY(tb_launch_tx_segment(d_seg, (uint32_t)n_seg, c.scratch.p, G().crc_pow[NR_HIP_CRC24_B], s));
@@ -623,6 +695,11 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     HIP_TRY(ldpc_launch_enc_jobs(ea, enc_threads, enc_lds, (uint32_t)n_seg, s));
     HIP_TRY(tb_launch_tx_ratematch(d_seg, (uint32_t)n_seg, c.scratch.p, coded, s));
     TB_DEBUG_STAGE("tx: segment + rate matching launches");
+  }
+  if (scr && !fused) {
+    HIP_TRY(nr_launch_scramble_bits_tb(reinterpret_cast<const tb_scr_tb_job *>(pl.jobs_d.p + pl.off[5]), ntb, (uint32_t)pl.off[6], c.scratch.p,
+                                       out_words, s));
+    TB_DEBUG_STAGE("tx: packed scrambled store");
   }
   if (staged) {
     uint8_t *hc = static_cast<uint8_t *>(b->coded);
@@ -730,8 +807,10 @@ struct RxHostStage {
   size_t pay_lo, pay_hi;  /* payload bytes the whole call's transport blocks touch */
 };
 
+/* scr != nullptr (nrLDPC_hip_ulsch_decode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the kernels' instantiations that
+ * unscramble the LLRs on their way into LDS (tb_rx_core.h) -- the caller's LLR array is only read */
 int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
-                  const RxHostStage *st = nullptr)
+                  const RxHostStage *st = nullptr, const nrLDPC_hip_tb_scr_t *scr = nullptr)
 {
   hipStream_t s;
   if (tb_begin(s, s_direct, staged) != 0)
@@ -771,7 +850,9 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
                             (uint64_t)(fused_mode & 0xff) | ((uint64_t)(tb_multi_mode() & 0xff) << 8) | ((uint64_t)tb_classes_enabled() << 16) |
                                 ((uint64_t)(tb_fill_mode() & 0xff) << 24) | ((uint64_t)tb_trunc_enabled() << 32) | ((uint64_t)tb_lrow_enabled() << 33),
                             harq_lib ? harq_tbl.gen.load() : 0};
-  TbPlan *hit = c.rx.find(tbs, ntb, salt);
+  salt[1] |= scr ? (uint64_t)1 << 34 : 0; /* scrambled (and the scr bytes in the key): never an unscrambled call's plan */
+  const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
+  TbPlan *hit = c.rx.find(tbs, ntb, salt, scr, scr_n);
   if (hit) {
     for (uint32_t i = 0; i < ntb; i++) /* nr_get_R_ldpc_decoder's state leaves the call as it did the first time */
       tbs[i].llrLen = hit->llr_len[i];
@@ -904,6 +985,10 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         j.clear = t.round == 0; /* harq_to_be_cleared -> d_to_be_cleared[r] (nr_ulsch_decoding.c:418-422) */
         j.K = sg.K; j.F = sg.F; j.Z = sg.Zc; j.num_llr = (uint32_t)hc.num_llr;
         j.c_off = tj.c_off0 + (uint64_t)r * cstride;
+        if (scr) {
+          j.c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
+          j.bit_off = r_offset;
+        }
         const uint32_t lds_elems = tb_rx_lds_elems(E, rm.Fin, rm.Ncb);
         if (!fused_tb)
           rx_lds_elems = std::max(rx_lds_elems, lds_elems);
@@ -942,7 +1027,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         if (!fused_tb && multi_ok && ce->dev_multi) /* candidates for a shared workgroup; sorted into groups below */
           cands.push_back(MultiCand{ce, dj});
         else
-          add_single(ce, dj, fused_tb ? lds_elems * (uint32_t)sizeof(int16_t) : 0u);
+          add_single(ce, dj, fused_tb ? lds_elems * (uint32_t)sizeof(int16_t) + (scr ? TB_RX_SCR_LDS : 0u) : 0u);
         sj.push_back(j);
         if (!fused_tb)
           sj_legacy.push_back(j);
@@ -1137,7 +1222,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     /* the key is the descriptor array as it ARRIVED (llrLen is updated by the loop above); the library's soft buffers as
      * they are now, after this build's allocations */
     salt[2] = harq_lib ? harq_tbl.gen.load() : 0;
-    pl.remember(key_tb.data(), ntb, salt);
+    pl.remember(key_tb.data(), ntb, salt, scr, scr_n);
   }
   if (c.scratch.ensure(pl.scratch_top) != 0)
     return -1;
@@ -1266,7 +1351,8 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     HIP_TRY(hipEventRecord(c.tev[0], s));
   }
   TB_DEBUG_STAGE("entry + copies in (job upload, LLRs, soft buffers)");
-  HIP_TRY(tb_launch_rx_dematch(d_leg, (uint32_t)pl.n_legacy_seg, pl.rx_lds_elems, llr, harq, reinterpret_cast<int8_t *>(c.scratch.p), s,
+  HIP_TRY((scr ? tb_launch_rx_dematch_scr : tb_launch_rx_dematch)(d_leg, (uint32_t)pl.n_legacy_seg, pl.rx_lds_elems, llr, harq,
+                                                                   reinterpret_cast<int8_t *>(c.scratch.p), s,
                                n_seg <= (size_t)G().n_cus));
   TB_DEBUG_STAGE("de-matching launch (segments outside the fused kernel)");
   if (c.timing)
@@ -1294,6 +1380,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
   fx.zc = 0;
   fx.prio_pro = 0;
   fx.trace = nullptr;
+  fx.scr = scr ? 1u : 0u;
   /* A call that mixes code sizes has several decoder launches (TbPlan::DecLaunch); nothing orders them among themselves --
    * disjoint jobs, scratch rows, per-block state.  NRLDPC_HIP_TB_OVERLAP=1 sends them out on side streams, forked from and
    * joined to the call's stream, so that the CUs one launch leaves free could take the next one's workgroups.  Default 0:
@@ -1480,11 +1567,11 @@ void tb_partition(const nrLDPC_hip_tb_batch_t *b, int parts, uint32_t *cut, uint
  * event -- while chunks k+1.. are still on the link, so that what a call costs beyond its transfer is one chunk's decoding
  * and one copy -> kernel edge (the reference overlaps the same way: segments are decoded by the pool while the next
  * symbols are still being demodulated). */
-int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb)
+int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, const nrLDPC_hip_tb_scr_t *scr = nullptr)
 {
   RxHostStage st{nullptr, false, tb0, ntb, 0, 0};
   if (ntb == 0)
-    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st);
+    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st, scr);
   size_t lo = SIZE_MAX, hi = 0;
   st.pay_lo = SIZE_MAX;
   for (uint32_t i = tb0; i < tb0 + ntb; i++) {
@@ -1501,7 +1588,7 @@ int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t nt
   K = std::min<int>(std::min<int>(K, 8), (int)ntb / 2); /* cut[] below holds 8 chunks; the knob is not trusted */
   const bool pinned = host_ptr_is_pinned(static_cast<const int16_t *>(b->coded) + lo, bytes);
   if (K < 2 || (pinned && (mode == 2 || (mode == 1 && bytes < pull_max))))
-    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st);
+    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st, scr);
   hipStream_t s;
   if (tb_begin(s, nullptr, true) != 0)
     return -1;
@@ -1548,7 +1635,7 @@ int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t nt
     if (k + 1 < K && copy_chunk(k + 1) != 0)
       return -1;
     HIP_TRY(hipStreamWaitEvent(s, c.chunk_ev[k], 0));
-    if (tb_rx_enqueue(b, cut[k], cut[k + 1] - cut[k], true, nullptr, &st) != 0)
+    if (tb_rx_enqueue(b, cut[k], cut[k + 1] - cut[k], true, nullptr, &st, scr ? scr + (cut[k] - tb0) : nullptr) != 0)
       return -1;
   }
   return 0;

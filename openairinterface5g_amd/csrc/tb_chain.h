@@ -25,8 +25,16 @@ hipError_t tb_launch_tx_ratematch(const tb_tx_seg_job *jobs, uint32_t n, const u
 struct ldpc_enc_job;
 hipError_t tb_launch_tx_fused(const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
                               const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, hipStream_t s);
+/* the same with the packed, scrambled store (jobs' c_init / bit_off / h_* / t_*): ceil(G/32) words per TB at coded + out_off;
+ * lds_bytes includes TB_TX_FUSED_SCR_LDS; tickets[] zero on entry and on exit, parts[] one slot per (shared word, segment) */
+hipError_t tb_launch_tx_fused_scr(const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
+                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets,
+                                  uint32_t *parts, hipStream_t s);
 hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
                                 int8_t *scratch, hipStream_t s, int wide = 0);
+/* scrambled codewords: each segment's LLRs are unscrambled on the way in (jobs' c_init / bit_off; tb_rx_core.h) */
+hipError_t tb_launch_rx_dematch_scr(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
+                                    int8_t *scratch, hipStream_t s, int wide = 0);
 /* Fused segment kernel (tb_rx_fused.hip): one workgroup takes a code segment from the received LLRs to its payload bytes --
  * de-matching (tb_rx_core.h) as the prologue of the decoder's block body, and instead of an output row the segment's bytes
  * of the payload, its share of the TB CRC and, from the last segment of a transport block to finish, the block's verdict.
@@ -65,6 +73,9 @@ struct tb_rx_fused_args {
    * the last pass, at the end, pass count, after: the LDS image is cleared, the LLRs are scattered, the soft buffer is streamed,
    * the decoder input is visible to the workgroup, 0...} as 16 x uint64; NULL normally */
   unsigned long long *trace;
+  /* != 0: the segments' LLRs are a scrambled codeword (nrLDPC_hip_ulsch_decode_scrambled): the instantiation that unscrambles
+   * them in its prologue (jobs' c_init / bit_off), with TB_RX_SCR_LDS bytes of sequence behind each segment's LDS image */
+  uint32_t scr;
 };
 struct ldpc_dec_args;
 hipError_t tb_launch_rx_fused(const struct ldpc_dec_args &a, const tb_rx_fused_args &x, int n_threads, int lds_bytes, uint32_t n_jobs,
@@ -74,6 +85,9 @@ hipError_t tb_rx_fused_init(void);
  * from `size` bytes holding a bit each (bit 0 of a byte) / `size` int16 LLRs negated in place where the sequence has a one */
 hipError_t nr_launch_scramble_bits(const uint8_t *in, uint32_t size, uint32_t c_init, uint32_t *out, hipStream_t s);
 hipError_t nr_launch_unscramble_llr(int16_t *llr, uint32_t size, uint32_t c_init, hipStream_t s);
+/* the first for every transport block of an encode call in one launch: jobs[i] packs G bits from in + in_off into the words at
+ * out + out_off (4-byte aligned); max_g = the largest G */
+hipError_t nr_launch_scramble_bits_tb(const tb_scr_tb_job *jobs, uint32_t n_tb, uint32_t max_g, const uint8_t *in, uint8_t *out, hipStream_t s);
 /* reassembly per segment (payload copy + partial TB CRC into acc[tb], zero on entry and on exit), then per-TB verdict */
 hipError_t tb_launch_rx_assemble(const tb_rx_tb_job *jobs, uint32_t n_tb, const tb_rx_seg_job *segs, uint32_t n_seg,
                                  const int32_t *n_iter, uint8_t *scratch, uint8_t *payload, uint8_t *ack, int32_t *iter_max,

@@ -319,10 +319,70 @@ __device__ __forceinline__ void tb_tx_store_syms(const uint32_t *sel, uint32_t s
   }
 }
 
+/* A packed word that several segments' bits share (segment boundaries are not word boundaries): each segment leaves its part
+ * in its slot and takes a ticket; the last to arrive ORs the parts, stores the word and resets the ticket.  No workgroup
+ * waits for another, and nobody read-modify-writes the caller's array.  No fences, as in the fused RX kernel
+ * (tb_rx_fused.hip): the part is a device-scope atomic store that has completed (vmcnt) before the ticket is taken, and the
+ * last arrival reads the parts with device-scope atomic loads -- an agent-scope release would write back the XCD's whole L2
+ * for every boundary word (the first version did: 81 us for the slot's 1664 segments against 20 unscrambled). */
+__device__ __forceinline__ void tb_tx_settle_word(uint32_t *dst, uint32_t bits, uint32_t ticket, uint32_t part, uint32_t part0, uint32_t n,
+                                                  uint32_t *tickets, uint32_t *parts)
+{
+  __hip_atomic_store(&parts[part], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const uint32_t before = __hip_atomic_fetch_add(&tickets[ticket], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (before + 1u != n)
+    return;
+  uint32_t v = 0;
+  for (uint32_t k = 0; k < n; k++)
+    v |= __hip_atomic_load(&parts[part0 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  *dst = v;
+  __hip_atomic_store(&tickets[ticket], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); /* zero again for the next call */
+}
+/* Packed, scrambled output of one selection chunk (the scrambled instantiation of tb_tx_fused_kernel, beside
+ * tb_tx_store_syms): codeword bits [b_lo, b_hi) of the TB = f[jj0 Qm ..] of the segment.  A thread forms whole 32-bit words
+ * of interleaved bits from the Qm sub-streams in LDS, XORs the sequence words (seq[0] = word b_lo / 32) over the bits this
+ * chunk holds, and stores a dword.  A word the chunk shares with the previous chunk takes that chunk's part from carry[];
+ * one it shares with the next chunk leaves its part there; one it shares with another segment goes through a ticket.  The
+ * bits behind G in the TB's last word are 0. */
+template <int QM, typename J>
+__device__ __forceinline__ void tb_tx_store_scr(J j, const uint32_t *sel, uint32_t sel_stride, const uint32_t *seq, uint32_t *carry, uint32_t k,
+                                                uint32_t b_lo, uint32_t b_hi, bool last_chunk, uint32_t *out32, uint32_t *tickets,
+                                                uint32_t *parts, int tid, int nt)
+{
+  const bool first_chunk = k == 0, last_seg = j->r + 1u == j->C;
+  const uint32_t w_lo = b_lo >> 5, w_hi = (b_hi + 31u) >> 5, lo = j->bit_off;
+  for (uint32_t w = w_lo + (uint32_t)tid; w < w_hi; w += (uint32_t)nt) {
+    const uint32_t n0 = 32u * w > b_lo ? 32u * w : b_lo, n1 = 32u * w + 32u < b_hi ? 32u * w + 32u : b_hi;
+    uint32_t bits = 0;
+    for (uint32_t n = n0; n < n1; n++) {
+      const uint32_t mc = n - b_lo, sy = mc / (uint32_t)QM, i = mc - sy * (uint32_t)QM;
+      bits |= ((sel[i * sel_stride + (sy >> 5)] >> (sy & 31u)) & 1u) << (n & 31u);
+    }
+    const uint32_t nb = n1 - n0, present = nb == 32u ? ~0u : ((1u << nb) - 1u) << (n0 & 31u);
+    bits ^= seq[w - w_lo] & present;
+    const bool before = 32u * w < b_lo, after = 32u * w + 32u > b_hi && !(last_chunk && last_seg);
+    if (before && !first_chunk)
+      bits |= carry[(k - 1u) & 1u];
+    if (after && !last_chunk) {
+      carry[k & 1u] = bits;
+    } else if ((before && first_chunk) || after) {
+      if (w == (lo >> 5) && (lo & 31u))
+        tb_tx_settle_word(out32 + w, bits, j->h_ticket, j->h_part, j->h_part0, j->h_n, tickets, parts);
+      else
+        tb_tx_settle_word(out32 + w, bits, j->t_ticket, j->t_part, j->t_part0, j->t_n, tickets, parts);
+    } else {
+      out32[w] = bits;
+    }
+  }
+}
+
 typedef uint32_t tb_u32x4_t __attribute__((ext_vector_type(4)));
 template <typename J> __device__ __forceinline__ uint32_t crc_len_of(J j) { return j->crc_len; }
-__global__ void __launch_bounds__(512, 8) tb_tx_fused_kernel(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch,
-                                                          uint8_t *coded, const uint32_t *pow24b, uint32_t *acc)
+/* SCR: the packed, scrambled store (tb_tx_fused_scr_kernel) instead of the bit-per-byte one (tb_tx_fused_kernel) */
+template <bool SCR>
+__device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch, uint8_t *coded,
+                                                 const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets, uint32_t *parts)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
   typedef const tb_tx_seg_job LDPC_CONST_AS *seg_ptr_t;
@@ -538,8 +598,13 @@ __global__ void __launch_bounds__(512, 8) tb_tx_fused_kernel(const tb_tx_seg_job
   const uint32_t v_magic = V > 1u ? 0xffffffffu / V + 1u : 0u; /* (V = 1: every rank is 0) */
   uint32_t *sel = reinterpret_cast<uint32_t *>(c + 1056 + 16); /* [Qm][TB_TX_SEL_SYMS / 32 + 1], behind the segment bytes */
   const uint32_t sel_stride = TB_TX_SEL_SYMS / 32 + 1;
+  uint32_t *seq = sel + 8 * sel_stride, *carry = seq + TB_TX_SCR_WORDS; /* scrambled launch only: TB_TX_FUSED_SCR_LDS */
   for (uint32_t jj0 = 0; jj0 < EQ; jj0 += TB_TX_SEL_SYMS) {
     const uint32_t nsym = EQ - jj0 < TB_TX_SEL_SYMS ? EQ - jj0 : TB_TX_SEL_SYMS, nw = (nsym + 31) >> 5;
+    if constexpr (SCR) { /* the chunk's sequence words, generated while the sub-streams are gathered */
+      const uint32_t b_lo = j->bit_off + jj0 * Qm, b_hi = b_lo + nsym * Qm;
+      tb_rx_scr_fill(seq, j->c_init, b_lo >> 5, ((b_hi + 31u) >> 5) - (b_lo >> 5));
+    }
     for (uint32_t it = tid; it < Qm * nw; it += nt) {
       const uint32_t i = it / nw, w = it - i * nw;
       const uint32_t k = i * EQ + jj0 + 32u * w;
@@ -571,6 +636,21 @@ __global__ void __launch_bounds__(512, 8) tb_tx_fused_kernel(const tb_tx_seg_job
     }
     __syncthreads();
     TB_TLOG();
+    if constexpr (SCR) {
+      const uint32_t b_lo = j->bit_off + jj0 * Qm, b_hi = b_lo + nsym * Qm, k = jj0 / TB_TX_SEL_SYMS;
+      const bool last_chunk = jj0 + nsym == EQ;
+      uint32_t *out32 = reinterpret_cast<uint32_t *>(f);
+      switch (Qm) {
+        case 1: tb_tx_store_scr<1>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
+        case 2: tb_tx_store_scr<2>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
+        case 4: tb_tx_store_scr<4>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
+        case 6: tb_tx_store_scr<6>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
+        default: tb_tx_store_scr<8>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
+      }
+      __syncthreads();
+      TB_TLOG();
+      continue;
+    }
     /* output bytes [jj0 Qm, (jj0 + nsym) Qm) of the segment */
     uint8_t *dst = f + (size_t)jj0 * Qm;
     switch (Qm) {
@@ -595,6 +675,17 @@ __global__ void __launch_bounds__(512, 8) tb_tx_fused_kernel(const tb_tx_seg_job
   }
 #endif
 }
+__global__ void __launch_bounds__(512, 8) tb_tx_fused_kernel(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch,
+                                                          uint8_t *coded, const uint32_t *pow24b, uint32_t *acc)
+{
+  tb_tx_fused_body<false>(jobs, ejobs, scratch, coded, pow24b, acc, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(512, 8) tb_tx_fused_scr_kernel(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch,
+                                                              uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets,
+                                                              uint32_t *parts)
+{
+  tb_tx_fused_body<true>(jobs, ejobs, scratch, coded, pow24b, acc, tickets, parts);
+}
 
 /* ---- RX 1: de-interleave + rate de-match (HARQ combining) + decoder input pack --------------------------------
  * nr_deinterleaving_ldpc (nr_rate_matching.c:310-388): e[i*E/Qm + jj] = f[i + jj*Qm];
@@ -611,6 +702,18 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)
   const job_ptr_t j = (job_ptr_t)jobs + blockIdx.x; /* uniform address: the job stays in SGPRs */
   const tb_rx_geom g = tb_rx_geometry(j);
   tb_rx_dematch_block(g, j->Qm, llr + j->llr_off, harq + j->harq_off, scratch + j->l_off, e_lds);
+}
+/* the same for scrambled codewords (nrLDPC_hip_ulsch_decode_scrambled): the LLRs are unscrambled on their way into LDS; the
+ * launch's LDS has TB_RX_SCR_LDS bytes more */
+/* (not held to 64 VGPRs like the kernel above: the sequence's jump would spill) */
+__global__ void __launch_bounds__(1024) tb_rx_dematch_scr_kernel(const tb_rx_seg_job *jobs, const int16_t *llr,
+                                                                       int16_t *harq, int8_t *scratch)
+{
+  extern __shared__ __attribute__((aligned(16))) int16_t e_lds[];
+  typedef const tb_rx_seg_job LDPC_CONST_AS *job_ptr_t;
+  const job_ptr_t j = (job_ptr_t)jobs + blockIdx.x;
+  const tb_rx_geom g = tb_rx_geometry(j);
+  tb_rx_dematch_block_scr(g, j->Qm, llr + j->llr_off, harq + j->harq_off, scratch + j->l_off, e_lds, j->c_init, j->bit_off);
 }
 
 /* ---- RX 2: reassemble b from the decoded segments, TB CRC, payload out --------------------------------------------
@@ -714,6 +817,15 @@ hipError_t tb_launch_tx_fused(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejo
   hipLaunchKernelGGL(tb_tx_fused_kernel, dim3(n), dim3(n_threads), lds_bytes, s, jobs, ejobs, scratch, coded, pow24b, acc);
   return hipGetLastError();
 }
+hipError_t tb_launch_tx_fused_scr(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
+                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets,
+                                  uint32_t *parts, hipStream_t s)
+{
+  if (n == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(tb_tx_fused_scr_kernel, dim3(n), dim3(n_threads), lds_bytes, s, jobs, ejobs, scratch, coded, pow24b, acc, tickets, parts);
+  return hipGetLastError();
+}
 hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
                                 int8_t *scratch, hipStream_t s, int wide)
 {
@@ -723,6 +835,15 @@ hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t 
    * workgroup -- a segment's time is then the latency of its strided loops, not the GPU's throughput */
   hipLaunchKernelGGL(tb_rx_dematch_kernel, dim3(n), dim3(wide ? 1024 : TB_THREADS), (size_t)lds_elems * sizeof(int16_t), s, jobs, llr, harq,
                      scratch);
+  return hipGetLastError();
+}
+hipError_t tb_launch_rx_dematch_scr(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
+                                    int8_t *scratch, hipStream_t s, int wide)
+{
+  if (n == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(tb_rx_dematch_scr_kernel, dim3(n), dim3(wide ? 1024 : TB_THREADS), (size_t)lds_elems * sizeof(int16_t) + TB_RX_SCR_LDS, s,
+                     jobs, llr, harq, scratch);
   return hipGetLastError();
 }
 hipError_t tb_launch_rx_assemble(const tb_rx_tb_job *jobs, uint32_t n_tb, const tb_rx_seg_job *segs, uint32_t n_seg,

@@ -44,6 +44,14 @@ struct tb_tx_seg_job {     /* one per code block */
    * workgroups crc_chunk0 .. crc_chunk0 + crc_nchunks - 1 left (one plain store each: no atomics, nothing to reset) */
   uint32_t crc_chunk0, crc_nchunks;
   uint32_t pad;
+  /* scrambled calls through the fused kernel (nrLDPC_hip_dlsch_encode_scrambled) only; out_off is then the TB's first output
+   * byte.  c_init: the TB's sequence; bit_off: codeword bit of the segment's first bit = sum of the previous segments' E.
+   * A packed word that other segments' bits share is settled through a ticket (tb_tx_settle_word): h_* for the word the
+   * segment starts in (when bit_off % 32 != 0), t_* for the word it ends in (when that is another word and not complete);
+   * ticket = index into the call's tickets, part = this segment's slot in its parts, part0 / n = the word's slots. */
+  uint32_t c_init, bit_off;
+  uint32_t h_ticket, h_part, h_part0, h_n;
+  uint32_t t_ticket, t_part, t_part0, t_n;
 };
 struct tb_rx_seg_job {
   uint64_t llr_off;        /* int16 units: TB offset + sum of the previous segments' E */
@@ -55,6 +63,9 @@ struct tb_rx_seg_job {
   uint64_t c_off;          /* scratch: this segment's decoded bits */
   uint32_t tb, r;          /* transport block (index into the per-TB jobs) and segment number */
   uint32_t iter_idx, pad;  /* where the decoder reported this segment's pass count */
+  /* scrambled calls (nrLDPC_hip_ulsch_decode_scrambled) only -- the kernels' unscrambled instantiations never read these: */
+  uint32_t c_init;         /* the transport block's sequence (38.211 6.3.1.1) */
+  uint32_t bit_off;        /* codeword bit of the segment's first LLR = sum of the previous segments' E */
 };
 struct tb_rx_tb_job {
   uint64_t payload_off;    /* A/8 bytes out */
@@ -67,6 +78,20 @@ struct tb_rx_tb_job {
   uint32_t fused;          /* 1: every segment of the block runs through the fused segment kernel, which also delivers the payload,
                               the TB CRC and the verdict (tb_rx_fused.hip); the reassembly kernels skip the block */
 };
+
+struct tb_scr_tb_job {      /* scrambled encode: one per transport block (nr_launch_scramble_bits_tb) */
+  uint64_t in_off;         /* scratch: the G coded bits, one per byte */
+  uint64_t out_off;        /* byte offset of the block's first output word (a multiple of 4) */
+  uint32_t G, c_init;
+};
+
+/* scrambled de-matching (tb_rx_core.h): sequence words staged in LDS behind a segment's image, and their bytes */
+#define TB_RX_SCR_WORDS 512u
+#define TB_RX_SCR_LDS (TB_RX_SCR_WORDS * 4u)
+/* scrambled fused TX launch: the sequence words of one selection chunk (TB_TX_SEL_SYMS symbols of up to 8 bits, starting
+ * anywhere in a word: 513 at most) and two carry words, behind the selection buffer (tb_chain.h TB_TX_FUSED_EXTRA_LDS) */
+#define TB_TX_SCR_WORDS 516u
+#define TB_TX_FUSED_SCR_LDS ((TB_TX_SCR_WORDS + 4u) * 4u)
 
 /* lds_elems = the largest tb_rx_lds_elems() over the jobs (int16 slots of LDS a workgroup needs) */
 TB_HD uint32_t tb_rx_lds_elems(uint32_t E, uint32_t Fin, uint32_t Ncb)

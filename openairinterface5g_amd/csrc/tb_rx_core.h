@@ -24,6 +24,9 @@
 #define TB_RX_CORE_H
 #include <stdint.h>
 #include "tb_jobs.h"
+#if defined(__HIPCC__)
+#include "nr_gold_dev.h"
+#endif
 
 #if defined(__HIPCC__)
 #define TB_RX_HD __device__ __forceinline__
@@ -68,6 +71,27 @@ template <class JobPtr> TB_RX_HD tb_rx_geom tb_rx_geometry(JobPtr j)
  * touches min(Ncb, E + Fin) + 8 slots at most (tb_rx_lds_elems); the slots are zeroed first, so a slot that receives
  * nothing (filler positions, the tail of the last lap) simply contributes 0 -- no coverage logic on the way out. */
 TB_RX_HD uint32_t tb_rx_slot(uint32_t p, uint32_t p_align, uint32_t Ncb) { return p >= p_align ? p - p_align : p + Ncb - p_align; }
+
+/* ---- scrambled codewords (nrLDPC_hip_ulsch_decode_scrambled) -----------------------------------------------------------
+ * The LLR of codeword bit n is negated (int16, wrapping: -(-32768) stays -32768, nr_scrambling.c:48-78) where the sequence
+ * c(n) of 38.211 5.2.1 has a one, on its way from the caller's array into the LDS image -- the array itself is never
+ * written.  Phase A reads the sequence from up to TB_RX_SCR_WORDS words staged in LDS behind the image: value i of symbol
+ * jj is bit rel + jj Qm + i of them.  A segment whose symbols do not fit takes them in chunks of tb_rx_scr_chunk() symbols,
+ * with the sequence of each chunk staged in turn. */
+/* (TB_RX_SCR_WORDS, TB_RX_SCR_LDS: tb_jobs.h) */
+struct tb_rx_scr {
+  const uint32_t *seq; /* LDS */
+  uint32_t rel;        /* bit of seq[] that carries symbol 0's first value (modulo 2^32: a later chunk starts behind it) */
+};
+/* symbols per chunk: its bits plus the offset of its first bit in its first word, plus the word the two-word read below
+ * takes behind the last one, fit into the staged words */
+TB_RX_HD uint32_t tb_rx_scr_chunk(uint32_t Qm) { return (TB_RX_SCR_WORDS - 2u) * 32u / Qm; }
+template <int QM> TB_RX_HD uint32_t tb_rx_scr_bits(const tb_rx_scr *sc, uint32_t jj)
+{
+  const uint32_t b = sc->rel + jj * (uint32_t)QM, k = b >> 5;
+  const uint64_t two = (uint64_t)sc->seq[k] | ((uint64_t)sc->seq[k + 1] << 32);
+  return (uint32_t)(two >> (b & 31u)) & ((1u << QM) - 1u);
+}
 
 /* ---- phase Z ---------------------------------------------------------------------------------------------------------- */
 TB_RX_HD void tb_rx_phase_zero(const tb_rx_geom &g, int16_t *e_lds, int8_t *__restrict__ l, uint32_t tid, uint32_t nt)
@@ -115,10 +139,34 @@ TB_RX_HD void tb_rx_phase_load_first(const tb_rx_geom &g, const int16_t *__restr
 /* ONE: the transmission is a single lap of the circular buffer (E <= V: everything but repetition) -- every value is a plain
  * store, and the code is straight-line: the general form below is a branch per value (is k in this lap? first lap or add?), and
  * with two dozen values per thread the branches, not the arithmetic, were the 3.9 us this phase took (profiles/r06) */
-template <int QM, bool ONE = false>
-TB_RX_HD void tb_rx_scatter_symbol(const tb_rx_geom &g, const tb_sym<QM> &sy, uint32_t jj, int16_t *e_lds, uint32_t lap, uint32_t nlaps)
+/* SCR: the values are unscrambled first (sc), and with several laps every value is added (the image is zero from phase Z):
+ * when the symbols come in chunks, a later chunk's first lap may reach a position an earlier chunk's second lap has filled */
+template <int QM, bool ONE = false, bool SCR = false>
+TB_RX_HD void tb_rx_scatter_symbol(const tb_rx_geom &g, const tb_sym<QM> &sy, uint32_t jj, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
+                                   const tb_rx_scr *sc = nullptr)
 {
   const uint32_t V = g.V, rank0 = g.rank0, Foffset = g.Foffset, Fin = g.Fin, p_align = g.p_align, Ncb = g.Ncb, EQ = g.E / QM;
+  if constexpr (SCR) {
+    const uint32_t m = tb_rx_scr_bits<QM>(sc, jj);
+    const uint32_t k_lo = lap * V, k_hi = k_lo + V;
+#pragma unroll
+    for (int i = 0; i < QM; i++) {
+      const uint32_t u = (sy.w[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+      const int16_t v = (int16_t)(uint16_t)(((m >> i) & 1u) ? 0u - u : u);
+      const uint32_t k = (uint32_t)i * EQ + jj;
+      if (ONE) {
+        uint32_t r = rank0 + k;
+        r = r >= V ? r - V : r;
+        e_lds[tb_rx_slot(r < Foffset ? r : r + Fin, p_align, Ncb)] = v;
+      } else if (nlaps == 1 || (k >= k_lo && k < k_hi)) {
+        uint32_t r = rank0 + (k - k_lo);
+        r = r >= V ? r - V : r;
+        const uint32_t q = tb_rx_slot(r < Foffset ? r : r + Fin, p_align, Ncb);
+        e_lds[q] = (int16_t)(e_lds[q] + v);
+      }
+    }
+    return;
+  }
   if (ONE) {
 #pragma unroll
     for (int i = 0; i < QM; i++) {
@@ -142,9 +190,9 @@ TB_RX_HD void tb_rx_scatter_symbol(const tb_rx_geom &g, const tb_sym<QM> &sy, ui
     }
   }
 }
-template <int QM, bool ONE = false>
+template <int QM, bool ONE = false, bool SCR = false>
 TB_RX_HD void tb_rx_phase_scatter_lap(const tb_rx_geom &g, const int16_t *__restrict__ f, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
-                                      uint32_t tid, uint32_t nt, const tb_rx_ahead &first)
+                                      uint32_t tid, uint32_t nt, const tb_rx_ahead &first, const tb_rx_scr *sc = nullptr)
 {
   const uint32_t EQ = g.E / QM;
   const bool vec = (reinterpret_cast<uintptr_t>(f) & 3) == 0;
@@ -156,7 +204,7 @@ TB_RX_HD void tb_rx_phase_scatter_lap(const tb_rx_geom &g, const int16_t *__rest
 #pragma unroll
       for (int i = 0; i < QM / 2; i++)
         sy.w[i] = first.w[u][i];
-      tb_rx_scatter_symbol<QM, ONE>(g, sy, jj, e_lds, lap, nlaps);
+      tb_rx_scatter_symbol<QM, ONE, SCR>(g, sy, jj, e_lds, lap, nlaps, sc);
     }
   }
   for (uint32_t jj0 = tid + TB_RX_U * nt; jj0 < EQ; jj0 += 2 * nt) { /* the rest, two symbols per step */
@@ -177,8 +225,26 @@ TB_RX_HD void tb_rx_phase_scatter_lap(const tb_rx_geom &g, const int16_t *__rest
     for (int u = 0; u < 2; u++) {
       const uint32_t jj = jj0 + (uint32_t)u * nt;
       if (jj < EQ)
-        tb_rx_scatter_symbol<QM, ONE>(g, sy[u], jj, e_lds, lap, nlaps);
+        tb_rx_scatter_symbol<QM, ONE, SCR>(g, sy[u], jj, e_lds, lap, nlaps, sc);
     }
+  }
+}
+/* scrambled, a segment in chunks: the symbols [j_lo, j_hi) of one lap, none loaded ahead */
+template <int QM, bool ONE>
+TB_RX_HD void tb_rx_phase_scatter_chunk(const tb_rx_geom &g, const int16_t *__restrict__ f, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
+                                        uint32_t tid, uint32_t nt, const tb_rx_scr &sc, uint32_t j_lo, uint32_t j_hi)
+{
+  const bool vec = (reinterpret_cast<uintptr_t>(f) & 3) == 0;
+  for (uint32_t jj = j_lo + tid; jj < j_hi; jj += nt) {
+    tb_sym<QM> sy;
+    if (vec) {
+      sy = *reinterpret_cast<const tb_sym<QM> *>(f + (size_t)jj * QM);
+    } else {
+#pragma unroll
+      for (int i = 0; i < QM; i += 2)
+        sy.w[i >> 1] = (uint32_t)(uint16_t)f[(size_t)jj * QM + i] | ((uint32_t)(uint16_t)f[(size_t)jj * QM + i + 1] << 16);
+    }
+    tb_rx_scatter_symbol<QM, ONE, true>(g, sy, jj, e_lds, lap, nlaps, &sc);
   }
 }
 
@@ -329,6 +395,95 @@ __device__ __forceinline__ void tb_rx_dematch_block(const tb_rx_geom &g, uint32_
     stamps[1] = wall_clock64();
   tb_rx_phase_stream(g, e_lds, w, l, tid, nt);
   if (stamps && tid == 0)
+    stamps[2] = wall_clock64();
+}
+
+/* sequence words w0 .. w0 + nw - 1 (nw <= TB_RX_SCR_WORDS) into seq[]: each wave jumps to its first word (nr_gold_dev.h), each
+ * lane moves on to its own pair of words (six column-form products at most) and walks them; the caller synchronises */
+__device__ __forceinline__ void tb_rx_scr_fill(uint32_t *seq, uint32_t c_init, uint32_t w0, uint32_t nw)
+{
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+  for (uint32_t base = wave * 128u; base < nw; base += nwave * 128u) { /* wave-uniform */
+    uint32_t a, b;
+    nr_gold_jump_wave(c_init, w0 + base, lane, a, b);
+#pragma unroll
+    for (int k = 0; k < 6; k++) /* + 2 lane words */
+      if ((lane >> k) & 1u) {
+        a = nr_gold_apply_cols(&nr_gold_tab_dev.col[1 + k][0], a);
+        b = nr_gold_apply_cols(&nr_gold_tab_dev.col[1 + k][32], b);
+      }
+    const uint32_t i = base + 2u * lane;
+    if (i < nw)
+      seq[i] = a ^ b;
+    if (i + 1u < nw)
+      seq[i + 1u] = nr_gold_step1(a) ^ nr_gold_step2(b);
+  }
+}
+/* phases Z and A of a scrambled segment (tb_rx_dematch_block_scr); returns behind the barrier that ends phase A */
+template <int QM>
+__device__ __forceinline__ void tb_rx_scr_phases_za(const tb_rx_geom &g, const int16_t *__restrict__ f, int8_t *__restrict__ l, int16_t *e_lds,
+                                                    uint32_t c_init, uint32_t bit_off, unsigned long long *stamps)
+{
+  const uint32_t tid = threadIdx.x, nt = blockDim.x, EQ = g.E / QM, CH = tb_rx_scr_chunk(QM), nlaps = tb_rx_laps(g);
+  uint32_t *seq = reinterpret_cast<uint32_t *>(e_lds + g.span);
+  tb_rx_ahead first;
+  tb_rx_phase_load_first<QM>(g, f, tid, nt, first);
+  tb_rx_phase_zero(g, e_lds, l, tid, nt);
+  if (EQ <= CH) { /* one chunk (every segment but long repetitions): the symbols loaded ahead are used */
+    const uint32_t w0 = bit_off >> 5, nw = ((bit_off + EQ * QM + 31u) >> 5) - w0 + 1u;
+    tb_rx_scr_fill(seq, c_init, w0, nw);
+    __syncthreads();
+    if (stamps && tid == 0)
+      stamps[0] = wall_clock64();
+    const tb_rx_scr sc{seq, bit_off - 32u * w0};
+    if (nlaps == 1) {
+      tb_rx_phase_scatter_lap<QM, true, true>(g, f, e_lds, 0, 1, tid, nt, first, &sc);
+      __syncthreads();
+    } else {
+      for (uint32_t lap = 0; lap < nlaps; lap++) {
+        tb_rx_phase_scatter_lap<QM, false, true>(g, f, e_lds, lap, nlaps, tid, nt, first, &sc);
+        __syncthreads();
+      }
+    }
+    return;
+  }
+  for (uint32_t c0 = 0; c0 < EQ; c0 += CH) {
+    const uint32_t c1 = EQ - c0 < CH ? EQ : c0 + CH;
+    const uint32_t w0 = (bit_off + c0 * QM) >> 5, nw = ((bit_off + c1 * QM + 31u) >> 5) - w0 + 1u;
+    if (c0)
+      __syncthreads(); /* the previous chunk's sequence has been read */
+    tb_rx_scr_fill(seq, c_init, w0, nw);
+    __syncthreads();
+    if (stamps && tid == 0 && c0 == 0)
+      stamps[0] = wall_clock64();
+    const tb_rx_scr sc{seq, bit_off - 32u * w0};
+    if (nlaps == 1) {
+      tb_rx_phase_scatter_chunk<QM, true>(g, f, e_lds, 0, 1, tid, nt, sc, c0, c1);
+    } else {
+      for (uint32_t lap = 0; lap < nlaps; lap++) {
+        tb_rx_phase_scatter_chunk<QM, false>(g, f, e_lds, lap, nlaps, tid, nt, sc, c0, c1);
+        __syncthreads();
+      }
+    }
+  }
+  __syncthreads();
+}
+/* tb_rx_dematch_block for a scrambled codeword: the segment's LLRs are codeword bits bit_off .. bit_off + E - 1 of the sequence
+ * of c_init.  The LDS behind the image holds TB_RX_SCR_LDS bytes of sequence during phase A. */
+__device__ __forceinline__ void tb_rx_dematch_block_scr(const tb_rx_geom &g, uint32_t Qm, const int16_t *__restrict__ f, int16_t *__restrict__ w,
+                                                        int8_t *__restrict__ l, int16_t *e_lds, uint32_t c_init, uint32_t bit_off,
+                                                        unsigned long long *stamps = nullptr)
+{
+  switch (Qm) {
+    case 2: tb_rx_scr_phases_za<2>(g, f, l, e_lds, c_init, bit_off, stamps); break;
+    case 4: tb_rx_scr_phases_za<4>(g, f, l, e_lds, c_init, bit_off, stamps); break;
+    case 6: tb_rx_scr_phases_za<6>(g, f, l, e_lds, c_init, bit_off, stamps); break;
+    default: tb_rx_scr_phases_za<8>(g, f, l, e_lds, c_init, bit_off, stamps); break;
+  }
+  if (stamps && threadIdx.x == 0)
+    stamps[1] = wall_clock64();
+  tb_rx_phase_stream(g, e_lds, w, l, threadIdx.x, blockDim.x);
+  if (stamps && threadIdx.x == 0)
     stamps[2] = wall_clock64();
 }
 #endif

@@ -219,7 +219,7 @@ template <bool LROW, bool MUTE = false> struct tb_rx_fused_io {
   }
 };
 
-template <bool LROW, bool MUTE, int ZC = 0>
+template <bool LROW, bool MUTE, int ZC = 0, bool SCR = false>
 __global__ void __launch_bounds__(1024) tb_rx_fused_kernel(const ldpc_dec_args a, const tb_rx_fused_args x)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
@@ -250,7 +250,11 @@ __global__ void __launch_bounds__(1024) tb_rx_fused_kernel(const ldpc_dec_args a
       l = reinterpret_cast<int8_t *>(fsm + x.lrow_off);
     else
       l = const_cast<int8_t *>(a.llr) + sj->l_off;
-    tb_rx_dematch_block(g, sj->Qm, x.llr + sj->llr_off, x.harq + sj->harq_off, l, reinterpret_cast<int16_t *>(fsm), tr ? tr + 7 : nullptr);
+    if constexpr (SCR)
+      tb_rx_dematch_block_scr(g, sj->Qm, x.llr + sj->llr_off, x.harq + sj->harq_off, l, reinterpret_cast<int16_t *>(fsm), sj->c_init,
+                              sj->bit_off, tr ? tr + 7 : nullptr);
+    else
+      tb_rx_dematch_block(g, sj->Qm, x.llr + sj->llr_off, x.harq + sj->harq_off, l, reinterpret_cast<int16_t *>(fsm), tr ? tr + 7 : nullptr);
     /* the code's tables go into LDS NOW, their loads in flight beside the de-matching stores -- not behind the barrier, in the
      * decoder's prologue, where nothing hides them.  (Only when the de-matching image, which other waves may still be
      * reading, ends in front of the tables' place: every large code.) */
@@ -287,15 +291,15 @@ __global__ void __launch_bounds__(1024) tb_rx_fused_kernel(const ldpc_dec_args a
     a.n_iter[(uint32_t)job->iter_idx] = n_iter;
 }
 
-hipError_t tb_rx_fused_init(void)
+template <bool SCR> static hipError_t tb_rx_fused_init_t(void)
 {
-  const void *k[] = {reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false>),
+  const void *k[] = {reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false, 0, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false, 0, SCR>),
 #define X(z) \
-                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false, z>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false, z>), \
-                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true, z>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true, z>),
+                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false, z, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false, z, SCR>), \
+                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true, z, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true, z, SCR>),
                      LDPC_FAST_ZC_LIST(X)
 #undef X
-                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true>)};
+                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true, 0, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true, 0, SCR>)};
   for (const void *f : k) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess)
@@ -303,25 +307,27 @@ hipError_t tb_rx_fused_init(void)
   }
   return hipSuccess;
 }
-
-hipError_t tb_launch_rx_fused(const ldpc_dec_args &a, const tb_rx_fused_args &x, int n_threads, int lds_bytes, uint32_t n_jobs, hipStream_t s)
+hipError_t tb_rx_fused_init(void)
 {
-  if (n_jobs == 0)
-    return hipSuccess;
-  if (!a.jobs || !x.segs || !x.tbs)
-    return hipErrorInvalidValue;
+  const hipError_t e = tb_rx_fused_init_t<false>();
+  return e != hipSuccess ? e : tb_rx_fused_init_t<true>();
+}
+
+template <bool SCR>
+static hipError_t tb_launch_rx_fused_t(const ldpc_dec_args &a, const tb_rx_fused_args &x, int n_threads, int lds_bytes, uint32_t n_jobs, hipStream_t s)
+{
   if (ldpc_fast_zc_enabled((int)x.zc)) { /* every job has this lifting size: the instantiations with compile-time row strides */
     switch ((int)x.zc) {
 #define X(z) \
   case z: \
     if (x.lrow_off && x.mute) \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<true, true, z>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<true, true, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     else if (x.lrow_off) \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<true, false, z>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<true, false, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     else if (x.mute) \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<false, true, z>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<false, true, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     else \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<false, false, z>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<false, false, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     return hipGetLastError();
       LDPC_FAST_ZC_LIST(X)
 #undef X
@@ -330,12 +336,21 @@ hipError_t tb_launch_rx_fused(const ldpc_dec_args &a, const tb_rx_fused_args &x,
     }
   }
   if (x.lrow_off && x.mute)
-    hipLaunchKernelGGL((tb_rx_fused_kernel<true, true>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<true, true, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   else if (x.lrow_off)
-    hipLaunchKernelGGL((tb_rx_fused_kernel<true, false>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<true, false, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   else if (x.mute)
-    hipLaunchKernelGGL((tb_rx_fused_kernel<false, true>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<false, true, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   else
-    hipLaunchKernelGGL((tb_rx_fused_kernel<false, false>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<false, false, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   return hipGetLastError();
+}
+
+hipError_t tb_launch_rx_fused(const ldpc_dec_args &a, const tb_rx_fused_args &x, int n_threads, int lds_bytes, uint32_t n_jobs, hipStream_t s)
+{
+  if (n_jobs == 0)
+    return hipSuccess;
+  if (!a.jobs || !x.segs || !x.tbs)
+    return hipErrorInvalidValue;
+  return x.scr ? tb_launch_rx_fused_t<true>(a, x, n_threads, lds_bytes, n_jobs, s) : tb_launch_rx_fused_t<false>(a, x, n_threads, lds_bytes, n_jobs, s);
 }

@@ -411,6 +411,20 @@ class nrLDPC_hip_tb_batch_t(C.Structure):
                 ("mem", C.c_int32), ("stream", C.c_void_p)]
 
 
+class nrLDPC_hip_tb_scr_t(C.Structure):
+    _fields_ = [("n_RNTI", C.c_uint32), ("Nid", C.c_uint16), ("q", C.c_uint8), ("pad", C.c_uint8)]
+
+
+def _scr_array(scrambling, n):
+    """(n_rnti, q, n_id) per transport block -> nrLDPC_hip_tb_scr_t[n] (the library checks the ranges)"""
+    assert len(scrambling) == n
+    arr = (nrLDPC_hip_tb_scr_t * n)()
+    for i, (n_rnti, q, n_id) in enumerate(scrambling):
+        arr[i] = nrLDPC_hip_tb_scr_t(n_RNTI=int(n_rnti) & 0xffffffff, Nid=int(n_id) & 0xffff, q=int(q) & 0xff, pad=0)
+    return arr
+
+
+EXPORTS += ["nrLDPC_hip_dlsch_encode_scrambled", "nrLDPC_hip_ulsch_decode_scrambled"]
 EXPORTS += ["nrLDPC_hip_dlsch_encode", "nrLDPC_hip_ulsch_decode", "nrLDPC_hip_segmentation", "nrLDPC_hip_get_E",
             "nrLDPC_hip_get_R_ldpc_decoder", "nrLDPC_hip_harq_release", "nrLDPC_hip_harq_release_all", "nrLDPC_hip_harq_read",
             "nrLDPC_hip_host_alloc", "nrLDPC_hip_host_free", "nrLDPC_hip_host_register", "nrLDPC_hip_host_unregister",
@@ -422,6 +436,9 @@ def _tb_lib():
     L = load_library()
     L.nrLDPC_hip_dlsch_encode.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t)]
     L.nrLDPC_hip_ulsch_decode.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t)]
+    if hasattr(L, "nrLDPC_hip_dlsch_encode_scrambled"):
+        L.nrLDPC_hip_dlsch_encode_scrambled.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
+        L.nrLDPC_hip_ulsch_decode_scrambled.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
     L.nrLDPC_hip_segmentation.argtypes = [C.c_uint32, C.c_uint8] + [C.POINTER(C.c_uint32)] * 4
     L.nrLDPC_hip_segmentation.restype = C.c_int32
     L.nrLDPC_hip_get_E.argtypes = [C.c_uint32] * 5
@@ -545,10 +562,28 @@ def ulsch_decode_host(tbs, llrs, harq, numMaxIter=8, harq_off=None, harq_ids=Non
     harq=None with harq_ids = one id per TB (MEM_HARQ_LIBRARY: the library keeps them; harq_read() looks at them).
     pinned: the LLR array goes into page-locked memory (nrLDPC_hip_host_alloc) and is pulled by the GPU in place.
     payload_off: explicit byte offsets of the TBs' payloads in the call's payload array (any order) instead of back to back."""
+    return _ulsch_decode_host(tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, None)
+
+
+def ulsch_decode_scrambled_host(tbs, llrs, harq, scrambling, numMaxIter=8, harq_off=None, harq_ids=None, pinned=False,
+                                payload_off=None):
+    """ulsch_decode_host on scrambled LLRs (nrLDPC_hip_ulsch_decode_scrambled): scrambling = one (n_rnti, q, n_id) per TB.
+    The same results as codeword_unscrambling() of every TB's LLRs followed by ulsch_decode_host; `llrs` are only read."""
+    return _ulsch_decode_host(tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, _scr_array(scrambling, len(tbs)))
+
+
+def _decode_call(L, b, scr):
+    if scr is None:
+        _check(L.nrLDPC_hip_ulsch_decode(C.byref(b)), "nrLDPC_hip_ulsch_decode")
+    else:
+        _check(L.nrLDPC_hip_ulsch_decode_scrambled(C.byref(b), scr), "nrLDPC_hip_ulsch_decode_scrambled")
+
+
+def _ulsch_decode_host(tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, scr):
     L = _tb_lib()
     n = len(tbs)
     if harq_ids is not None or not isinstance(harq, np.ndarray):
-        return _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off)
+        return _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, scr)
     po = np.cumsum([0] + [(t["A"] // 8 + 15) // 16 * 16 for t in tbs])
     pay_total = int(po[-1])
     if payload_off is not None:
@@ -572,13 +607,13 @@ def ulsch_decode_host(tbs, llrs, harq, numMaxIter=8, harq_off=None, harq_ids=Non
     b = nrLDPC_hip_tb_batch_t(n_tb=n, tb=arr, payload=pay.ctypes.data, coded=llr.ctypes.data, harq=harq.ctypes.data,
                               harq_stride=HARQ_STRIDE, ack=ack.ctypes.data, iter_max=itm.ctypes.data, mem=MEM_HOST,
                               stream=None)
-    _check(L.nrLDPC_hip_ulsch_decode(C.byref(b)), "nrLDPC_hip_ulsch_decode")
+    _decode_call(L, b, scr)
     for i, t in enumerate(tbs):
         t["llrLen"] = arr[i].llrLen
     return [pay[po[i]:po[i] + tbs[i]["A"] // 8].copy() for i in range(n)], ack.astype(bool), itm
 
 
-def _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off=None):
+def _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off=None, scr=None):
     """host payload / LLRs / verdicts with the soft buffers resident on the GPU (see ulsch_decode_host)"""
     n = len(tbs)
     po = np.cumsum([0] + [(t["A"] // 8 + 15) // 16 * 16 for t in tbs])
@@ -605,7 +640,7 @@ def _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_i
     arr = _tb_array(tbs, po, co, ho, numMaxIter)
     b = nrLDPC_hip_tb_batch_t(n_tb=n, tb=arr, payload=pay.ctypes.data, coded=llr.ctypes.data, harq=hp,
                               harq_stride=HARQ_STRIDE, ack=ack.ctypes.data, iter_max=itm.ctypes.data, mem=mem, stream=None)
-    _check(L.nrLDPC_hip_ulsch_decode(C.byref(b)), "nrLDPC_hip_ulsch_decode")
+    _decode_call(L, b, scr)
     for i, t in enumerate(tbs):
         t["llrLen"] = arr[i].llrLen
     return [pay[po[i]:po[i] + tbs[i]["A"] // 8].copy() for i in range(n)], ack.astype(bool), itm
@@ -618,6 +653,45 @@ def tb_layout(tbs):
     segs = [nr_segmentation(t["A"] + (24 if t["A"] > 3824 else 16), t["BG"])["C"] for t in tbs]
     ho = np.cumsum([0] + [c * HARQ_STRIDE for c in segs])
     return po, co, ho, segs
+
+
+def tb_layout_packed(tbs):
+    """Byte offsets of the TBs' packed words for the *_scrambled encode calls (4-byte aligned, ceil(G/32) words each, 16-byte
+    spacing) and the bytes they span: (offsets, total)."""
+    co = np.cumsum([0] + [((t["G"] + 31) // 32 * 4 + 15) // 16 * 16 for t in tbs])
+    return co[:-1], int(co[-1])
+
+
+def dlsch_encode_scrambled_host(tbs, payloads, scrambling):
+    """dlsch_encode_host with scrambling (nrLDPC_hip_dlsch_encode_scrambled): scrambling = one (n_rnti, q, n_id) per TB.
+    Returns a list of uint32[ceil(G/32)]: the words codeword_scrambling() makes of dlsch_encode_host's bits."""
+    L = _tb_lib()
+    po = np.cumsum([0] + [(t["A"] // 8 + 15) // 16 * 16 for t in tbs])
+    co, total = tb_layout_packed(tbs)
+    pay = np.zeros(int(po[-1]) + 16, np.uint8)
+    for i, p in enumerate(payloads):
+        pay[po[i]:po[i] + tbs[i]["A"] // 8] = np.asarray(p, np.uint8)[:tbs[i]["A"] // 8]
+    coded = np.zeros(total // 4 + 4, np.uint32)
+    arr = _tb_array(tbs, po, co, None)
+    b = nrLDPC_hip_tb_batch_t(n_tb=len(tbs), tb=arr, payload=pay.ctypes.data, coded=coded.ctypes.data, harq=None,
+                              harq_stride=0, ack=None, iter_max=None, mem=MEM_HOST, stream=None)
+    _check(L.nrLDPC_hip_dlsch_encode_scrambled(C.byref(b), _scr_array(scrambling, len(tbs))), "nrLDPC_hip_dlsch_encode_scrambled")
+    return [coded[co[i] // 4:co[i] // 4 + (tbs[i]["G"] + 31) // 32].copy() for i in range(len(tbs))]
+
+
+def dlsch_encode_scrambled_device(tbs, payload, coded, scrambling, stream=None):
+    """payload: torch uint8 [>= tb_layout po[-1]] on the GPU, coded: torch tensor on the GPU of >= tb_layout_packed total
+    bytes (out: TB i's words at byte tb_layout_packed offset i).  Asynchronous."""
+    import torch
+    L = _tb_lib()
+    po, _, _, _ = tb_layout(tbs)
+    co, total = tb_layout_packed(tbs)
+    assert payload.is_cuda and coded.is_cuda and payload.numel() >= po[-1] and coded.numel() * coded.element_size() >= total
+    arr = _tb_array(tbs, po, co, None)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    b = nrLDPC_hip_tb_batch_t(n_tb=len(tbs), tb=arr, payload=payload.data_ptr(), coded=coded.data_ptr(), harq=None,
+                              harq_stride=0, ack=None, iter_max=None, mem=MEM_DEVICE, stream=s)
+    _check(L.nrLDPC_hip_dlsch_encode_scrambled(C.byref(b), _scr_array(scrambling, len(tbs))), "nrLDPC_hip_dlsch_encode_scrambled")
 
 
 def dlsch_encode_device(tbs, payload, coded, stream=None):
@@ -650,12 +724,16 @@ class PreparedTbBatch:
     C calls nrLDPC_hip_dlsch_encode / nrLDPC_hip_ulsch_decode (asynchronous on the batch's stream with device buffers,
     synchronous with host buffers).  Buffers: torch CUDA tensors (mem = MEM_DEVICE, the default), or numpy arrays /
     PinnedArray objects with mem = MEM_HOST, optionally | MEM_HARQ_DEVICE (harq a CUDA tensor) or | MEM_HARQ_LIBRARY
-    (harq None, harq_ids = one id per transport block)."""
+    (harq None, harq_ids = one id per transport block).  scrambling = one (n_rnti, q, n_id) per transport block: the calls
+    are nrLDPC_hip_dlsch_encode_scrambled / nrLDPC_hip_ulsch_decode_scrambled, and an encode's output follows
+    tb_layout_packed."""
 
     def __init__(self, tbs, payload, coded_or_llr, harq=None, ack=None, iter_max=None, numMaxIter=8, stream=None, mem=MEM_DEVICE,
-                 harq_ids=None):
+                 harq_ids=None, scrambling=None):
         self._lib = _tb_lib()
         po, co, ho, _ = tb_layout(tbs)
+        self.scr = None if scrambling is None else _scr_array(scrambling, len(tbs))
+        self._coded_packed = tb_layout_packed(tbs)[0]
         self._keep = (payload, coded_or_llr, harq, ack, iter_max)
         if harq_ids is not None:
             assert mem & MEM_HARQ_LIBRARY and len(harq_ids) == len(tbs)
@@ -665,16 +743,24 @@ class PreparedTbBatch:
         if mem & MEM_DEVICE:
             import torch
             s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        if self.scr is not None:
+            self.arr_enc = _tb_array(tbs, po, self._coded_packed, None, numMaxIter)
         self.batch = nrLDPC_hip_tb_batch_t(
             n_tb=len(tbs), tb=self.arr, payload=_ptr(payload), coded=_ptr(coded_or_llr),
             harq=_ptr(harq), harq_stride=0 if (harq is None and harq_ids is None) else HARQ_STRIDE,
             ack=_ptr(ack), iter_max=_ptr(iter_max), mem=mem, stream=s)
 
     def encode(self):
-        _check(self._lib.nrLDPC_hip_dlsch_encode(C.byref(self.batch)), "nrLDPC_hip_dlsch_encode")
+        if self.scr is None:
+            _check(self._lib.nrLDPC_hip_dlsch_encode(C.byref(self.batch)), "nrLDPC_hip_dlsch_encode")
+        else:
+            if not hasattr(self, "batch_enc"):   # (the packed layout's coded offsets)
+                self.batch_enc = nrLDPC_hip_tb_batch_t.from_buffer_copy(self.batch)
+                self.batch_enc.tb = self.arr_enc
+            _check(self._lib.nrLDPC_hip_dlsch_encode_scrambled(C.byref(self.batch_enc), self.scr), "nrLDPC_hip_dlsch_encode_scrambled")
 
     def decode(self):
-        _check(self._lib.nrLDPC_hip_ulsch_decode(C.byref(self.batch)), "nrLDPC_hip_ulsch_decode")
+        _decode_call(self._lib, self.batch, self.scr)
 
     # HIP graphs: capture on the batch's own stream (torch.cuda.graph(g, stream=<the stream the batch was made on>)) after
     # two warm-up calls there; a call whose descriptors repeat only enqueues kernels and memsets.
@@ -684,6 +770,16 @@ def ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter=8, st
     """llr: torch int16 [>= co[-1]], harq: torch int16 [>= ho[-1]], payload: torch uint8 [>= po[-1]] (out),
     ack: torch uint8 [n], iter_max: torch int32 [n].  Asynchronous; tb dicts get their llrLen updated.
     harq=None with harq_ids: the library keeps the soft buffers (MEM_HARQ_LIBRARY)."""
+    _ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter, stream, harq_ids, None)
+
+
+def ulsch_decode_scrambled_device(tbs, llr, harq, payload, ack, iter_max, scrambling, numMaxIter=8, stream=None, harq_ids=None):
+    """ulsch_decode_device on scrambled LLRs (nrLDPC_hip_ulsch_decode_scrambled): scrambling = one (n_rnti, q, n_id) per TB;
+    `llr` is only read."""
+    _ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter, stream, harq_ids, _scr_array(scrambling, len(tbs)))
+
+
+def _ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter, stream, harq_ids, scr):
     import torch
     L = _tb_lib()
     po, co, ho, _ = tb_layout(tbs)
@@ -699,7 +795,7 @@ def ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter=8, st
     b = nrLDPC_hip_tb_batch_t(n_tb=len(tbs), tb=arr, payload=payload.data_ptr(), coded=llr.data_ptr(), harq=_ptr(harq),
                               harq_stride=HARQ_STRIDE, ack=ack.data_ptr(), iter_max=iter_max.data_ptr(), mem=mem,
                               stream=s)
-    _check(L.nrLDPC_hip_ulsch_decode(C.byref(b)), "nrLDPC_hip_ulsch_decode")
+    _decode_call(L, b, scr)
     for i, t in enumerate(tbs):
         t["llrLen"] = arr[i].llrLen
 

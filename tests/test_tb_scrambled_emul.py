@@ -1,0 +1,81 @@
+"""CPU emulation of the scrambled de-matching (tests/emul/tb_rx_scr_emul.cpp: tb_rx_core.h with the unscrambling flag, a
+workgroup's threads walked phase by phase) against numpy unscrambling followed by the oracle's de-interleaving, rate
+de-matching and pack.  No GPU: the sequence words staged in LDS come from the host jump-ahead of nr_gold.h."""
+import ctypes as C
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+from test_scrambling_host import serial_gold
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "openairinterface5g_amd" / "csrc"
+CXX = "/opt/rocm/lib/llvm/bin/clang++"
+
+
+@pytest.fixture(scope="module")
+def emul(tmp_path_factory):
+    d = tmp_path_factory.mktemp("scr_emul")
+    subprocess.run(["gcc", "-O2", "-fPIC", "-c", str(CSRC / "nr_coding_host.c"), "-o", str(d / "nr_coding_host.o")], check=True)
+    lib = d / "libtb_rx_scr_emul.so"
+    subprocess.run([CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-pass-failed", "-o", str(lib),
+                    str(ROOT / "tests" / "emul" / "tb_rx_scr_emul.cpp"), str(d / "nr_coding_host.o")], check=True)
+    L = C.CDLL(str(lib))
+    L.tb_emul_rx_dematch_scr.argtypes = [C.c_uint32, C.c_int] + [C.c_uint32] * 4 + [C.c_int] + [C.c_uint32] * 3 + \
+        [C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
+    return L
+
+
+def unscramble(f, c_init, bit_off):
+    """the reference's nr_codeword_unscrambling on codeword bits bit_off .. bit_off + len(f) - 1: int16 negation, wrapping"""
+    c = serial_gold(c_init, bit_off + len(f))[bit_off:]
+    out = f.copy()
+    neg = c.astype(bool)
+    out[neg] = (-(f[neg].astype(np.int32))).astype(np.int16)          # -(-32768) wraps to -32768
+    return out
+
+
+def test_rx_dematch_phases_unscramble_against_the_oracle(emul):
+    rng = np.random.default_rng(2026)
+    cases = chunked = 0
+    for BG, A, lbrm in ((1, 30000, 0), (1, 30000, 24000), (2, 3000, 0), (2, 640, 0), (1, 100000, 150000)):
+        s = O.segmentation(None, O.len_with_crc(1, A), BG)
+        Z, K, F, Cn = s["Z"], s["K"], s["F"], s["C"]
+        N = (66 if BG == 1 else 50) * Z
+        for Qm in (2, 4, 6, 8):
+            for rv in (0, 2, 3):
+                for rate in (0.6, 0.92, 0.08):                       # 0.08: E > Ncb, several laps (and several chunks)
+                    E = max(Qm * 4, int((K - F) / rate) // Qm * Qm)
+                    R, _ = O.get_R(rv, E, BG, Z, 0, 0)
+                    ncols = O.NCOLS[(BG, R)]
+                    f = rng.integers(-300, 300, E).astype(np.int16)
+                    f[rng.integers(0, E, 6)] = [-32768, 32767, 0, -32768, 1, -1]
+                    c_init = int(rng.integers(0, 1 << 31))
+                    bit_off = int(rng.integers(0, 200000)) * 2 + 1 if cases % 3 else int(rng.integers(0, 5000)) * 32
+                    for clear in (1, 0):
+                        w0 = rng.integers(-2000, 2000, 66 * 384 + 16).astype(np.int16)
+                        Ncb = N if not lbrm else min(N, (3 * lbrm // (2 * Cn)))
+                        w0[Ncb:N] = 0
+                        e = O.deinterleave(E, Qm, unscramble(f, c_init, bit_off))
+                        d_ref = w0[:N].copy()
+                        rc, d_ref = O.rate_match_rx(lbrm, BG, Z, d_ref, e, Cn, rv, clear, E, F, K - F - 2 * Z)
+                        assert rc == 0
+                        l_ref = O.llr_prepack(d_ref, BG, Z, K, F, ncols)
+                        w = w0.copy()
+                        l = np.full(ncols * Z + 8, 0x11, np.int8)
+                        f_in = f.copy()
+                        span = emul.tb_emul_rx_dematch_scr(lbrm, BG, Z, Cn, F, K, rv, E, Qm, ncols * Z, clear, 256, c_init, bit_off,
+                                                           f_in.ctypes.data, w.ctypes.data, l.ctypes.data)
+                        assert span > 0
+                        key = (BG, A, Qm, rv, rate, clear, bit_off)
+                        assert np.array_equal(f_in, f), key                    # the LLRs are only read
+                        assert np.array_equal(w[:N], d_ref), key
+                        assert np.array_equal(w[N:], w0[N:]), key
+                        assert np.array_equal(l[:ncols * Z], l_ref), key
+                        assert (l[ncols * Z:] == 0x11).all()
+                        cases += 1
+                        chunked += E // Qm > (512 - 2) * 32 // Qm
+    assert cases > 300 and chunked > 10
