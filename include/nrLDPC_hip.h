@@ -317,6 +317,38 @@ int32_t nrLDPC_hip_codeword_scrambling(const uint8_t *in, uint32_t size, uint8_t
 int32_t nrLDPC_hip_codeword_unscrambling(int16_t *llr, uint32_t size, uint8_t q, uint32_t Nid, uint32_t n_RNTI,
                                          int32_t mem, void *stream);
 int32_t nrLDPC_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out);
+/* Modulation mapping and soft demapping, the reference's nr_modulation() (openair1/PHY/MODULATION/nr_modulation.c:115-244)
+ * and nr_ulsch_compute_llr() for one stream (openair1/PHY/NR_TRANSPORT/nr_ulsch_llr_computation.c:316-363) on the GPU.
+ * Qm = 2, 4, 6, 8; the constellations of nr_generate_modulation_table(): bit b of a symbol's index = codeword bit iQm + b,
+ * even bits give re, odd bits im.
+ *   modulation: `in` = packed words (bit k of word w = bit 32w + k: the output of nrLDPC_hip_codeword_scrambling and
+ *     nrLDPC_hip_dlsch_encode_scrambled), `length` bits; out = length/Qm (re, im) int16 pairs, nothing behind them written.
+ *     Symbol i is always bits iQm .. iQm+Qm-1.  Deliberate differences: the reference's 64QAM loop bound length - 192 is
+ *     computed in uint32 (it wraps below 192 bits and the loop reads past the input), and its 12-bit tail writes two
+ *     symbols where one may be valid.
+ *   ulsch_llr: nb_re REs; every array c16, one entry per RE (rxdataF_comp = the equalised y, ul_ch_mag / b / c = the channel
+ *     magnitudes; an array the Qm does not use may be NULL).  Per RE: A = y (QPSK: A >> 3), B = subs(mag, |A|),
+ *     C = subs(magb, |B|), D = subs(magc, |C|) (|-32768| = -32768, subs saturating); llr = A.r A.i B.r B.i C.r C.i D.r D.i
+ *     cut to Qm values -- exactly nb_re*Qm written (for Qm >= 4 the reference rounds nb_re up to a multiple of 8 and reads
+ *     and writes up to 7 REs behind it; not reproduced).
+ * mem = NRLDPC_HIP_MEM_HOST (synchronous) or NRLDPC_HIP_MEM_DEVICE (enqueued on `stream`; every buffer in device memory of
+ * one GPU, the ulsch_llr arrays 4-byte aligned).  0, or negative -- before anything is enqueued or written -- for a bad Qm,
+ * length % Qm != 0, length (nb_re*Qm) > 2^21, another mem value, a NULL buffer or (DEVICE) a buffer that is not device
+ * memory of that GPU; nrLDPC_hip_last_error() names the reason.
+ * mod_table: the 2^Qm points as (re, im) pairs in index order, on the host (for checking); 0, or -1 for a bad Qm. */
+int32_t nrLDPC_hip_mod_table(uint8_t Qm, int16_t *out);
+int32_t nrLDPC_hip_modulation(const uint32_t *in, uint32_t length, uint8_t Qm, int16_t *out, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_llr(const int32_t *rxdataF_comp, const int32_t *ul_ch_mag, const int32_t *ul_ch_magb,
+                             const int32_t *ul_ch_magc, uint32_t nb_re, uint8_t Qm, int16_t *llr, int32_t mem, void *stream);
+/* The UL-SCH chain call from symbols: every output (payload, ack, iter_max, llrLen, soft buffers) as nrLDPC_hip_ulsch_llr on
+ * each block's symbols followed by nrLDPC_hip_ulsch_decode_scrambled on the result; the LLRs never exist in memory.
+ * Block i's symbol record is read as int16 at coded + coded_off (coded 4-byte aligned, coded_off even): with S = G/Qm, Qm/2
+ * planes of S c16 values one after another -- y, mag_a (Qm >= 4), mag_b (Qm >= 6), mag_c (Qm = 8) -- exactly G int16, the
+ * range the block's LLRs would take.  The planes are in codeword symbol order: with Nl layers, symbol k is layer k mod Nl's
+ * RE k div Nl (layer demapping moves whole symbols, so it commutes with demapping).  Every mem mode of the LLR call.
+ * Negative -- before anything is enqueued or written -- for anything decode_scrambled refuses, G % Qm != 0, a bad Qm, a
+ * record that is not 4-byte aligned. */
+int32_t nrLDPC_hip_ulsch_decode_symbols(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr);
 /* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one

@@ -1497,3 +1497,4 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "dec_jobs.inc.cpp"
 #include "tb_offload.inc.cpp"
 #include "scrambling_api.inc.cpp"
+#include "qam_api.inc.cpp"

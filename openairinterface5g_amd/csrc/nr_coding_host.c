@@ -3,6 +3,7 @@
  */
 #include "nr_coding_host.h"
 #include "nr_gold.h"
+#include "nr_qam.h"
 
 int nr_hip_segmentation(uint32_t B, int BG, nr_hip_seg_t *s)
 {
@@ -166,6 +167,21 @@ int nr_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, ui
     out[w] = x1 ^ x2;
     x1 = nr_gold_step1(x1);
     x2 = nr_gold_step2(x2);
+  }
+  return 0;
+}
+
+/* the point of every index of one constellation (nr_qam.h), re then im */
+int nr_hip_mod_table(uint32_t Qm, int16_t *out)
+{
+  if (Qm != 2 && Qm != 4 && Qm != 6 && Qm != 8)
+    return NR_HIP_QAM_BAD_QM;
+  if (!out)
+    return NR_HIP_QAM_NULL_OUT;
+  for (uint32_t x = 0; x < (1u << Qm); x++) {
+    const uint32_t p = nr_qam_point(Qm, x);
+    out[2 * x] = (int16_t)(uint16_t)p;
+    out[2 * x + 1] = (int16_t)(uint16_t)(p >> 16);
   }
   return 0;
 }

@@ -71,6 +71,11 @@ int nr_hip_check_crc(const uint8_t *decoded_bytes, uint32_t n, uint8_t crc_type)
 #define NR_HIP_GOLD_BAD_FIRST_WORD -2 /* first_word >= NR_GOLD_MAX_FIRST_WORD */
 #define NR_HIP_GOLD_NULL_OUT -3       /* n_words > 0 and out NULL */
 int nr_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out);
+/* the 2^Qm points of the constellation of Qm (nr_qam.h) as (re, im) int16 pairs in index order: 0, or one of the negative
+ * codes below (nothing written) */
+#define NR_HIP_QAM_BAD_QM -1   /* Qm not 2, 4, 6 or 8 */
+#define NR_HIP_QAM_NULL_OUT -2 /* out NULL */
+int nr_hip_mod_table(uint32_t Qm, int16_t *out);
 #ifdef __cplusplus
 }
 #endif

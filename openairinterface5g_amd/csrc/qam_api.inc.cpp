@@ -1,0 +1,169 @@
+/*
+ * qam_api.inc.cpp -- modulation mapping, soft demapping and the UL-SCH chain call that takes symbols (included at the end of
+ * ldpc_api.cpp, behind scrambling_api.inc.cpp whose checks it shares).  The constellations and the demapper: nr_qam.h; the
+ * standalone kernels: tb_qam.hip; the demapper inside the chain: tb_rx_core.h (the symbol source of phase A).
+ */
+
+namespace {
+
+int qam_check_qm(uint32_t Qm)
+{
+  if (Qm != 2 && Qm != 4 && Qm != 6 && Qm != 8)
+    return set_error("modulation: Qm must be 2, 4, 6 or 8");
+  return 0;
+}
+
+/* decode_symbols: what decode_scrambled checks, and a record that starts on a symbol and on a 4-byte boundary */
+int sym_check_batch(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
+{
+  if (scr_check_batch(b, scr, false) != 0)
+    return -1;
+  if (b->n_tb && (reinterpret_cast<uintptr_t>(b->coded) & 3u))
+    return set_error("decode_symbols: the symbol records must be 4-byte aligned (coded)");
+  for (uint32_t i = 0; i < b->n_tb; i++) {
+    if (qam_check_qm(b->tb[i].Qm) != 0)
+      return -1;
+    if (b->tb[i].G % b->tb[i].Qm)
+      return set_error("decode_symbols: G must be a multiple of Qm");
+    if (b->tb[i].coded_off & 1u)
+      return set_error("decode_symbols: coded_off must be even");
+  }
+  return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t nrLDPC_hip_mod_table(uint8_t Qm, int16_t *out)
+{
+  switch (nr_hip_mod_table(Qm, out)) {
+    case 0: return 0;
+    case NR_HIP_QAM_BAD_QM: return set_error("mod_table: Qm must be 2, 4, 6 or 8");
+    default: return set_error("null argument");
+  }
+}
+
+int32_t nrLDPC_hip_modulation(const uint32_t *in, uint32_t length, uint8_t Qm, int16_t *out, int32_t mem, void *stream)
+{
+  if (qam_check_qm(Qm) != 0)
+    return -1;
+  if (length % Qm)
+    return set_error("modulation: length must be a multiple of Qm");
+  if (length > NR_SCR_MAX_BITS)
+    return set_error("modulation: length above 2^21 bits");
+  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
+    return set_error("modulation: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (length && (!in || !out))
+    return set_error("null argument");
+  if (length == 0)
+    return 0;
+  const size_t in_bytes = 4u * (size_t)((length + 31u) >> 5), out_bytes = (size_t)(length / Qm) * 4u;
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    const int ord = scr_device_ordinal(in);
+    if (ord < 0 || scr_device_ordinal(out) != ord)
+      return set_error("modulation: DEVICE mem needs `in` and `out` in device memory of one GPU");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    HIP_TRY(nr_launch_modulation(in, length, Qm, out, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  if (c.ensure(align_up(in_bytes, 16), out_bytes) != 0)
+    return -1;
+  memcpy(c.h_in, in, in_bytes);
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, in_bytes, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(nr_launch_modulation(reinterpret_cast<const uint32_t *>(c.d_in), length, Qm, reinterpret_cast<int16_t *>(c.d_out), c.stream));
+  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  memcpy(out, c.h_out, out_bytes);
+  return 0;
+}
+
+int32_t nrLDPC_hip_ulsch_llr(const int32_t *rxdataF_comp, const int32_t *ul_ch_mag, const int32_t *ul_ch_magb, const int32_t *ul_ch_magc,
+                             uint32_t nb_re, uint8_t Qm, int16_t *llr, int32_t mem, void *stream)
+{
+  if (qam_check_qm(Qm) != 0)
+    return -1;
+  if ((uint64_t)nb_re * Qm > NR_SCR_MAX_BITS)
+    return set_error("ulsch_llr: nb_re * Qm above 2^21");
+  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
+    return set_error("ulsch_llr: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  const int32_t *in[4] = {rxdataF_comp, ul_ch_mag, ul_ch_magb, ul_ch_magc};
+  const uint32_t np = Qm / 2u;
+  if (nb_re) {
+    if (!llr)
+      return set_error("null argument");
+    for (uint32_t k = 0; k < np; k++)
+      if (!in[k])
+        return set_error("null argument");
+  }
+  if (nb_re == 0)
+    return 0;
+  const size_t plane_bytes = (size_t)nb_re * 4u, out_bytes = (size_t)nb_re * Qm * 2u;
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    const int ord = scr_device_ordinal(llr);
+    bool ok = ord >= 0;
+    for (uint32_t k = 0; k < np; k++)
+      ok = ok && scr_device_ordinal(in[k]) == ord && (reinterpret_cast<uintptr_t>(in[k]) & 3u) == 0;
+    if (!ok)
+      return set_error("ulsch_llr: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    const uint32_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (uint32_t k = 0; k < np; k++)
+      pl[k] = reinterpret_cast<const uint32_t *>(in[k]);
+    HIP_TRY(nr_launch_ulsch_llr(pl, nb_re, Qm, llr, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  const size_t stride = align_up(plane_bytes, 16);
+  if (c.ensure(stride * np, out_bytes) != 0)
+    return -1;
+  const uint32_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (uint32_t k = 0; k < np; k++) {
+    memcpy(c.h_in + k * stride, in[k], plane_bytes);
+    pl[k] = reinterpret_cast<const uint32_t *>(c.d_in + k * stride);
+  }
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, stride * np, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(nr_launch_ulsch_llr(pl, nb_re, Qm, reinterpret_cast<int16_t *>(c.d_out), c.stream));
+  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  memcpy(llr, c.h_out, out_bytes);
+  return 0;
+}
+
+int32_t nrLDPC_hip_ulsch_decode_symbols(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
+{
+  if (!b || !b->tb || !b->payload || !b->coded)
+    return set_error("null argument");
+  const bool harq_lib = (b->mem & NRLDPC_HIP_MEM_HARQ_LIBRARY) != 0;
+  if ((b->mem & ~(NRLDPC_HIP_MEM_DEVICE | NRLDPC_HIP_MEM_HARQ_DEVICE | NRLDPC_HIP_MEM_HARQ_LIBRARY)) ||
+      (harq_lib && (b->mem & NRLDPC_HIP_MEM_HARQ_DEVICE)))
+    return set_error("decode: invalid mem flags");
+  if ((!b->harq && !harq_lib) || !b->ack || !b->iter_max || b->harq_stride < 66 * 384)
+    return set_error("decode needs harq (stride >= 66*384), ack and iter_max buffers");
+  if (sym_check_batch(b, scr) != 0)
+    return -1;
+  if (b->n_tb == 0)
+    return ensure_ready();
+  return tb_run_sharded(
+      b,
+      [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) {
+        return (staged && !(b->mem & NRLDPC_HIP_MEM_DEVICE)) ? tb_rx_enqueue_host(b, tb0, n, scr + tb0, true)
+                                                              : tb_rx_enqueue(b, tb0, n, staged, s, nullptr, scr + tb0, true);
+      },
+      [&](uint32_t tb0, uint32_t n) { return tb_rx_finish(b, tb0, n); });
+}
+
+} /* extern "C" */

@@ -808,9 +808,11 @@ struct RxHostStage {
 };
 
 /* scr != nullptr (nrLDPC_hip_ulsch_decode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the kernels' instantiations that
- * unscramble the LLRs on their way into LDS (tb_rx_core.h) -- the caller's LLR array is only read */
+ * unscramble the LLRs on their way into LDS (tb_rx_core.h) -- the caller's LLR array is only read.
+ * sym (with scr; nrLDPC_hip_ulsch_decode_symbols): b->coded holds each block's symbol record instead of its LLRs, in the same
+ * G int16 at coded_off -- staging and sharding move it as they move LLRs; the kernels' instantiations that demap it */
 int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
-                  const RxHostStage *st = nullptr, const nrLDPC_hip_tb_scr_t *scr = nullptr)
+                  const RxHostStage *st = nullptr, const nrLDPC_hip_tb_scr_t *scr = nullptr, bool sym = false)
 {
   hipStream_t s;
   if (tb_begin(s, s_direct, staged) != 0)
@@ -851,6 +853,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
                                 ((uint64_t)(tb_fill_mode() & 0xff) << 24) | ((uint64_t)tb_trunc_enabled() << 32) | ((uint64_t)tb_lrow_enabled() << 33),
                             harq_lib ? harq_tbl.gen.load() : 0};
   salt[1] |= scr ? (uint64_t)1 << 34 : 0; /* scrambled (and the scr bytes in the key): never an unscrambled call's plan */
+  salt[1] |= sym ? (uint64_t)1 << 35 : 0; /* symbol records: never an LLR call's plan, nor the reverse */
   const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
   TbPlan *hit = c.rx.find(tbs, ntb, salt, scr, scr_n);
   if (hit) {
@@ -989,6 +992,8 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
           j.c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
           j.bit_off = r_offset;
         }
+        if (sym)
+          j.plane = 2u * (t.G / t.Qm);
         const uint32_t lds_elems = tb_rx_lds_elems(E, rm.Fin, rm.Ncb);
         if (!fused_tb)
           rx_lds_elems = std::max(rx_lds_elems, lds_elems);
@@ -1351,7 +1356,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     HIP_TRY(hipEventRecord(c.tev[0], s));
   }
   TB_DEBUG_STAGE("entry + copies in (job upload, LLRs, soft buffers)");
-  HIP_TRY((scr ? tb_launch_rx_dematch_scr : tb_launch_rx_dematch)(d_leg, (uint32_t)pl.n_legacy_seg, pl.rx_lds_elems, llr, harq,
+  HIP_TRY((sym ? tb_launch_rx_dematch_sym : scr ? tb_launch_rx_dematch_scr : tb_launch_rx_dematch)(d_leg, (uint32_t)pl.n_legacy_seg, pl.rx_lds_elems, llr, harq,
                                                                    reinterpret_cast<int8_t *>(c.scratch.p), s,
                                n_seg <= (size_t)G().n_cus));
   TB_DEBUG_STAGE("de-matching launch (segments outside the fused kernel)");
@@ -1381,6 +1386,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
   fx.prio_pro = 0;
   fx.trace = nullptr;
   fx.scr = scr ? 1u : 0u;
+  fx.sym = sym ? 1u : 0u;
   /* A call that mixes code sizes has several decoder launches (TbPlan::DecLaunch); nothing orders them among themselves --
    * disjoint jobs, scratch rows, per-block state.  NRLDPC_HIP_TB_OVERLAP=1 sends them out on side streams, forked from and
    * joined to the call's stream, so that the CUs one launch leaves free could take the next one's workgroups.  Default 0:
@@ -1567,11 +1573,11 @@ void tb_partition(const nrLDPC_hip_tb_batch_t *b, int parts, uint32_t *cut, uint
  * event -- while chunks k+1.. are still on the link, so that what a call costs beyond its transfer is one chunk's decoding
  * and one copy -> kernel edge (the reference overlaps the same way: segments are decoded by the pool while the next
  * symbols are still being demodulated). */
-int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, const nrLDPC_hip_tb_scr_t *scr = nullptr)
+int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, const nrLDPC_hip_tb_scr_t *scr = nullptr, bool sym = false)
 {
   RxHostStage st{nullptr, false, tb0, ntb, 0, 0};
   if (ntb == 0)
-    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st, scr);
+    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st, scr, sym);
   size_t lo = SIZE_MAX, hi = 0;
   st.pay_lo = SIZE_MAX;
   for (uint32_t i = tb0; i < tb0 + ntb; i++) {
@@ -1588,7 +1594,7 @@ int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t nt
   K = std::min<int>(std::min<int>(K, 8), (int)ntb / 2); /* cut[] below holds 8 chunks; the knob is not trusted */
   const bool pinned = host_ptr_is_pinned(static_cast<const int16_t *>(b->coded) + lo, bytes);
   if (K < 2 || (pinned && (mode == 2 || (mode == 1 && bytes < pull_max))))
-    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st, scr);
+    return tb_rx_enqueue(b, tb0, ntb, true, nullptr, &st, scr, sym);
   hipStream_t s;
   if (tb_begin(s, nullptr, true) != 0)
     return -1;
@@ -1635,7 +1641,7 @@ int tb_rx_enqueue_host(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t nt
     if (k + 1 < K && copy_chunk(k + 1) != 0)
       return -1;
     HIP_TRY(hipStreamWaitEvent(s, c.chunk_ev[k], 0));
-    if (tb_rx_enqueue(b, cut[k], cut[k + 1] - cut[k], true, nullptr, &st, scr ? scr + (cut[k] - tb0) : nullptr) != 0)
+    if (tb_rx_enqueue(b, cut[k], cut[k + 1] - cut[k], true, nullptr, &st, scr ? scr + (cut[k] - tb0) : nullptr, sym) != 0)
       return -1;
   }
   return 0;

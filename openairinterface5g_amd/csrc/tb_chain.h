@@ -35,6 +35,10 @@ hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t 
 /* scrambled codewords: each segment's LLRs are unscrambled on the way in (jobs' c_init / bit_off; tb_rx_core.h) */
 hipError_t tb_launch_rx_dematch_scr(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
                                     int8_t *scratch, hipStream_t s, int wide = 0);
+/* scrambled codewords received as symbol records (nrLDPC_hip_ulsch_decode_symbols): `llr` holds each block's planar record
+ * (jobs' plane), demapped and unscrambled on the way in (tb_rx_core.h) */
+hipError_t tb_launch_rx_dematch_sym(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
+                                    int8_t *scratch, hipStream_t s, int wide = 0);
 /* Fused segment kernel (tb_rx_fused.hip): one workgroup takes a code segment from the received LLRs to its payload bytes --
  * de-matching (tb_rx_core.h) as the prologue of the decoder's block body, and instead of an output row the segment's bytes
  * of the payload, its share of the TB CRC and, from the last segment of a transport block to finish, the block's verdict.
@@ -76,6 +80,9 @@ struct tb_rx_fused_args {
   /* != 0: the segments' LLRs are a scrambled codeword (nrLDPC_hip_ulsch_decode_scrambled): the instantiation that unscrambles
    * them in its prologue (jobs' c_init / bit_off), with TB_RX_SCR_LDS bytes of sequence behind each segment's LDS image */
   uint32_t scr;
+  /* != 0 (with scr): the segments' input is the symbol record of nrLDPC_hip_ulsch_decode_symbols (jobs' plane): the
+   * instantiation that demaps it in its prologue */
+  uint32_t sym;
 };
 struct ldpc_dec_args;
 hipError_t tb_launch_rx_fused(const struct ldpc_dec_args &a, const tb_rx_fused_args &x, int n_threads, int lds_bytes, uint32_t n_jobs,
@@ -85,6 +92,10 @@ hipError_t tb_rx_fused_init(void);
  * from `size` bytes holding a bit each (bit 0 of a byte) / `size` int16 LLRs negated in place where the sequence has a one */
 hipError_t nr_launch_scramble_bits(const uint8_t *in, uint32_t size, uint32_t c_init, uint32_t *out, hipStream_t s);
 hipError_t nr_launch_unscramble_llr(int16_t *llr, uint32_t size, uint32_t c_init, hipStream_t s);
+/* modulation mapping / soft demapping (tb_qam.hip, nr_qam.h): length / Qm points from the packed bits in[] (ceil(length/32)
+ * words); nb_re RE's Qm LLRs from planes[k] = y, mag_a, mag_b, mag_c (k < Qm/2, one c16 word per RE, 4-byte aligned) */
+hipError_t nr_launch_modulation(const uint32_t *in, uint32_t length, uint32_t Qm, int16_t *out, hipStream_t s);
+hipError_t nr_launch_ulsch_llr(const uint32_t *const planes[4], uint32_t nb_re, uint32_t Qm, int16_t *llr, hipStream_t s);
 /* the first for every transport block of an encode call in one launch: jobs[i] packs G bits from in + in_off into the words at
  * out + out_off (4-byte aligned); max_g = the largest G */
 hipError_t nr_launch_scramble_bits_tb(const tb_scr_tb_job *jobs, uint32_t n_tb, uint32_t max_g, const uint8_t *in, uint8_t *out, hipStream_t s);

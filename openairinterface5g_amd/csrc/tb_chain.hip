@@ -715,6 +715,18 @@ __global__ void __launch_bounds__(1024) tb_rx_dematch_scr_kernel(const tb_rx_seg
   const tb_rx_geom g = tb_rx_geometry(j);
   tb_rx_dematch_block_scr(g, j->Qm, llr + j->llr_off, harq + j->harq_off, scratch + j->l_off, e_lds, j->c_init, j->bit_off);
 }
+/* the same for symbol records (nrLDPC_hip_ulsch_decode_symbols): each segment's y and magnitudes are demapped and unscrambled
+ * on their way into LDS; `llr` holds the records (jobs' plane; a block's record starts at llr_off - bit_off) */
+__global__ void __launch_bounds__(1024) tb_rx_dematch_sym_kernel(const tb_rx_seg_job *jobs, const int16_t *llr,
+                                                                       int16_t *harq, int8_t *scratch)
+{
+  extern __shared__ __attribute__((aligned(16))) int16_t e_lds[];
+  typedef const tb_rx_seg_job LDPC_CONST_AS *job_ptr_t;
+  const job_ptr_t j = (job_ptr_t)jobs + blockIdx.x;
+  const tb_rx_geom g = tb_rx_geometry(j);
+  tb_rx_dematch_block_sym(g, j->Qm, llr + (j->llr_off - j->bit_off), j->plane, harq + j->harq_off, scratch + j->l_off, e_lds, j->c_init,
+                          j->bit_off);
+}
 
 /* ---- RX 2: reassemble b from the decoded segments, TB CRC, payload out --------------------------------------------
  * per segment: copy its payload bytes into b and the payload buffer, partial TB CRC of those bytes into acc[tb];
@@ -843,6 +855,15 @@ hipError_t tb_launch_rx_dematch_scr(const tb_rx_seg_job *jobs, uint32_t n, uint3
   if (n == 0)
     return hipSuccess;
   hipLaunchKernelGGL(tb_rx_dematch_scr_kernel, dim3(n), dim3(wide ? 1024 : TB_THREADS), (size_t)lds_elems * sizeof(int16_t) + TB_RX_SCR_LDS, s,
+                     jobs, llr, harq, scratch);
+  return hipGetLastError();
+}
+hipError_t tb_launch_rx_dematch_sym(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
+                                    int8_t *scratch, hipStream_t s, int wide)
+{
+  if (n == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(tb_rx_dematch_sym_kernel, dim3(n), dim3(wide ? 1024 : TB_THREADS), (size_t)lds_elems * sizeof(int16_t) + TB_RX_SCR_LDS, s,
                      jobs, llr, harq, scratch);
   return hipGetLastError();
 }

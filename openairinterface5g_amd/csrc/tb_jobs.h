@@ -66,6 +66,9 @@ struct tb_rx_seg_job {
   /* scrambled calls (nrLDPC_hip_ulsch_decode_scrambled) only -- the kernels' unscrambled instantiations never read these: */
   uint32_t c_init;         /* the transport block's sequence (38.211 6.3.1.1) */
   uint32_t bit_off;        /* codeword bit of the segment's first LLR = sum of the previous segments' E */
+  /* symbol records (nrLDPC_hip_ulsch_decode_symbols) only: int16 units between the record's planes (2 G / Qm).  The record
+   * starts at llr_off - bit_off; the segment's first symbol is bit_off / Qm of every plane */
+  uint32_t plane, pad2;
 };
 struct tb_rx_tb_job {
   uint64_t payload_off;    /* A/8 bytes out */

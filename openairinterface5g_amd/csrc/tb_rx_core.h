@@ -8,7 +8,8 @@
  *   phase Z  request every thread's first symbols (their latency runs under the rest of this phase), zero the image and
  *            the decoder input's punctured columns;
  *   phase A  a thread per modulation symbol jj reads the symbol's Qm LLRs f[jj*Qm .. +Qm) in ONE load -- from device
- *            memory, or over the link from the caller's page-locked array -- and drops each at its soft-buffer position
+ *            memory, or over the link from the caller's page-locked array -- (or the symbol's y and channel magnitudes from
+ *            a symbol record, and demaps them: the source policy below) and drops each at its soft-buffer position
  *            in LDS (e_lds[pos(i*E/Qm + jj)]); one lap of the circular buffer at a time, so that every position receives
  *            at most one value per lap (plain read-modify-write, no atomics, no division);
  *   phase B  a thread per 8 consecutive soft-buffer positions: w (16-byte load / store) + the lap sums from LDS, then the
@@ -24,6 +25,7 @@
 #define TB_RX_CORE_H
 #include <stdint.h>
 #include "tb_jobs.h"
+#include "nr_qam.h"
 #if defined(__HIPCC__)
 #include "nr_gold_dev.h"
 #endif
@@ -42,6 +44,37 @@ template <> struct tb_sym<2> { uint32_t w[1]; };
 template <> struct tb_sym<4> { uint32_t w[2]; };
 template <> struct tb_sym<6> { uint32_t w[3]; };
 template <> struct tb_sym<8> { uint32_t w[4]; };
+
+/* ---- the source of phase A (every load site goes through tb_rx_src_load) -------------------------------------------------
+ *   const int16_t *  the LLR array: symbol jj's Qm values are f[jj*Qm .. +Qm), one load where f is 4-byte aligned;
+ *   tb_rx_sym_src    a symbol record (nrLDPC_hip_ulsch_decode_symbols): symbol jj's y, mag_a, mag_b, mag_c are word jj of
+ *                    Qm/2 planes `plane` words apart -- the same Qm/2 words per symbol, so the loads ahead keep their
+ *                    storage; the raw words become the Qm LLRs (nr_qam_demap) in tb_rx_scatter_symbol, before the
+ *                    unscrambling.  The record is 4-byte aligned (the entry point refuses anything else). */
+struct tb_rx_sym_src {
+  const uint32_t *y; /* plane 0, at the segment's first symbol */
+  uint32_t plane;    /* words from one plane to the next */
+};
+template <class SRC> struct tb_rx_src_raw { static constexpr bool value = false; };
+template <> struct tb_rx_src_raw<tb_rx_sym_src> { static constexpr bool value = true; };
+TB_RX_HD bool tb_rx_src_vec(const int16_t *f) { return (reinterpret_cast<uintptr_t>(f) & 3) == 0; }
+TB_RX_HD bool tb_rx_src_vec(const tb_rx_sym_src &) { return true; }
+template <int QM> TB_RX_HD void tb_rx_src_load(const int16_t *__restrict__ f, bool vec, uint32_t jj, tb_sym<QM> &sy)
+{
+  if (vec) {
+    sy = *reinterpret_cast<const tb_sym<QM> *>(f + (size_t)jj * QM);
+  } else {
+#pragma unroll
+    for (int i = 0; i < QM; i += 2)
+      sy.w[i >> 1] = (uint32_t)(uint16_t)f[(size_t)jj * QM + i] | ((uint32_t)(uint16_t)f[(size_t)jj * QM + i + 1] << 16);
+  }
+}
+template <int QM> TB_RX_HD void tb_rx_src_load(const tb_rx_sym_src &s, bool, uint32_t jj, tb_sym<QM> &sy)
+{
+#pragma unroll
+  for (int i = 0; i < QM / 2; i++)
+    sy.w[i] = s.y[(size_t)i * s.plane + jj];
+}
 
 /* what the phases need of a segment's job (wave-uniform: built from scalar loads of the job record) */
 struct tb_rx_geom {
@@ -114,25 +147,20 @@ TB_RX_HD uint32_t tb_rx_laps(const tb_rx_geom &g) { return (g.E + g.V - 1) / g.V
  * by the loop of tb_rx_phase_scatter_lap. */
 struct tb_rx_ahead { uint32_t w[TB_RX_U > 0 ? TB_RX_U : 1][4]; }; /* up to Qm = 8 values per symbol; the same storage whatever Qm,
                                                                     so that only the loads and the scatter are compiled per Qm */
-template <int QM>
-TB_RX_HD void tb_rx_phase_load_first(const tb_rx_geom &g, const int16_t *__restrict__ f, uint32_t tid, uint32_t nt, tb_rx_ahead &first)
+template <int QM, class SRC = const int16_t *>
+TB_RX_HD void tb_rx_phase_load_first(const tb_rx_geom &g, const SRC f, uint32_t tid, uint32_t nt, tb_rx_ahead &first)
 {
   const uint32_t EQ = g.E / QM;
-  const bool vec = (reinterpret_cast<uintptr_t>(f) & 3) == 0;
+  const bool vec = tb_rx_src_vec(f);
 #pragma unroll
   for (int u = 0; u < TB_RX_U; u++) {
     uint32_t jj = tid + (uint32_t)u * nt;
     jj = jj < EQ ? jj : (EQ ? EQ - 1 : 0);
-    if (vec) {
-      const tb_sym<QM> sy = *reinterpret_cast<const tb_sym<QM> *>(f + (size_t)jj * QM);
+    tb_sym<QM> sy;
+    tb_rx_src_load<QM>(f, vec, jj, sy);
 #pragma unroll
-      for (int i = 0; i < QM / 2; i++)
-        first.w[u][i] = sy.w[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < QM; i += 2)
-        first.w[u][i >> 1] = (uint32_t)(uint16_t)f[(size_t)jj * QM + i] | ((uint32_t)(uint16_t)f[(size_t)jj * QM + i + 1] << 16);
-    }
+    for (int i = 0; i < QM / 2; i++)
+      first.w[u][i] = sy.w[i];
   }
 }
 /* one symbol's Qm values to their slots (lap `lap` of `nlaps`: only the values whose k falls into this lap) */
@@ -141,10 +169,14 @@ TB_RX_HD void tb_rx_phase_load_first(const tb_rx_geom &g, const int16_t *__restr
  * with two dozen values per thread the branches, not the arithmetic, were the 3.9 us this phase took (profiles/r06) */
 /* SCR: the values are unscrambled first (sc), and with several laps every value is added (the image is zero from phase Z):
  * when the symbols come in chunks, a later chunk's first lap may reach a position an earlier chunk's second lap has filled */
-template <int QM, bool ONE = false, bool SCR = false>
-TB_RX_HD void tb_rx_scatter_symbol(const tb_rx_geom &g, const tb_sym<QM> &sy, uint32_t jj, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
+/* RAW: `raw` holds a symbol record's words (y and magnitudes), demapped here into the symbol's Qm LLRs */
+template <int QM, bool ONE = false, bool SCR = false, bool RAW = false>
+TB_RX_HD void tb_rx_scatter_symbol(const tb_rx_geom &g, const tb_sym<QM> &raw, uint32_t jj, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
                                    const tb_rx_scr *sc = nullptr)
 {
+  tb_sym<QM> sy = raw;
+  if constexpr (RAW)
+    nr_qam_demap(QM, sy.w);
   const uint32_t V = g.V, rank0 = g.rank0, Foffset = g.Foffset, Fin = g.Fin, p_align = g.p_align, Ncb = g.Ncb, EQ = g.E / QM;
   if constexpr (SCR) {
     const uint32_t m = tb_rx_scr_bits<QM>(sc, jj);
@@ -190,12 +222,13 @@ TB_RX_HD void tb_rx_scatter_symbol(const tb_rx_geom &g, const tb_sym<QM> &sy, ui
     }
   }
 }
-template <int QM, bool ONE = false, bool SCR = false>
-TB_RX_HD void tb_rx_phase_scatter_lap(const tb_rx_geom &g, const int16_t *__restrict__ f, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
+template <int QM, bool ONE = false, bool SCR = false, class SRC = const int16_t *>
+TB_RX_HD void tb_rx_phase_scatter_lap(const tb_rx_geom &g, const SRC f, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
                                       uint32_t tid, uint32_t nt, const tb_rx_ahead &first, const tb_rx_scr *sc = nullptr)
 {
+  constexpr bool RAW = tb_rx_src_raw<SRC>::value;
   const uint32_t EQ = g.E / QM;
-  const bool vec = (reinterpret_cast<uintptr_t>(f) & 3) == 0;
+  const bool vec = tb_rx_src_vec(f);
 #pragma unroll
   for (int u = 0; u < TB_RX_U; u++) { /* the symbols loaded ahead */
     const uint32_t jj = tid + (uint32_t)u * nt;
@@ -204,7 +237,7 @@ TB_RX_HD void tb_rx_phase_scatter_lap(const tb_rx_geom &g, const int16_t *__rest
 #pragma unroll
       for (int i = 0; i < QM / 2; i++)
         sy.w[i] = first.w[u][i];
-      tb_rx_scatter_symbol<QM, ONE, SCR>(g, sy, jj, e_lds, lap, nlaps, sc);
+      tb_rx_scatter_symbol<QM, ONE, SCR, RAW>(g, sy, jj, e_lds, lap, nlaps, sc);
     }
   }
   for (uint32_t jj0 = tid + TB_RX_U * nt; jj0 < EQ; jj0 += 2 * nt) { /* the rest, two symbols per step */
@@ -213,38 +246,26 @@ TB_RX_HD void tb_rx_phase_scatter_lap(const tb_rx_geom &g, const int16_t *__rest
     for (int u = 0; u < 2; u++) {
       uint32_t jj = jj0 + (uint32_t)u * nt;
       jj = jj < EQ ? jj : EQ - 1;
-      if (vec) {
-        sy[u] = *reinterpret_cast<const tb_sym<QM> *>(f + (size_t)jj * QM);
-      } else {
-#pragma unroll
-        for (int i = 0; i < QM; i += 2)
-          sy[u].w[i >> 1] = (uint32_t)(uint16_t)f[(size_t)jj * QM + i] | ((uint32_t)(uint16_t)f[(size_t)jj * QM + i + 1] << 16);
-      }
+      tb_rx_src_load<QM>(f, vec, jj, sy[u]);
     }
 #pragma unroll
     for (int u = 0; u < 2; u++) {
       const uint32_t jj = jj0 + (uint32_t)u * nt;
       if (jj < EQ)
-        tb_rx_scatter_symbol<QM, ONE, SCR>(g, sy[u], jj, e_lds, lap, nlaps, sc);
+        tb_rx_scatter_symbol<QM, ONE, SCR, RAW>(g, sy[u], jj, e_lds, lap, nlaps, sc);
     }
   }
 }
 /* scrambled, a segment in chunks: the symbols [j_lo, j_hi) of one lap, none loaded ahead */
-template <int QM, bool ONE>
-TB_RX_HD void tb_rx_phase_scatter_chunk(const tb_rx_geom &g, const int16_t *__restrict__ f, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
+template <int QM, bool ONE, class SRC = const int16_t *>
+TB_RX_HD void tb_rx_phase_scatter_chunk(const tb_rx_geom &g, const SRC f, int16_t *e_lds, uint32_t lap, uint32_t nlaps,
                                         uint32_t tid, uint32_t nt, const tb_rx_scr &sc, uint32_t j_lo, uint32_t j_hi)
 {
-  const bool vec = (reinterpret_cast<uintptr_t>(f) & 3) == 0;
+  const bool vec = tb_rx_src_vec(f);
   for (uint32_t jj = j_lo + tid; jj < j_hi; jj += nt) {
     tb_sym<QM> sy;
-    if (vec) {
-      sy = *reinterpret_cast<const tb_sym<QM> *>(f + (size_t)jj * QM);
-    } else {
-#pragma unroll
-      for (int i = 0; i < QM; i += 2)
-        sy.w[i >> 1] = (uint32_t)(uint16_t)f[(size_t)jj * QM + i] | ((uint32_t)(uint16_t)f[(size_t)jj * QM + i + 1] << 16);
-    }
-    tb_rx_scatter_symbol<QM, ONE, true>(g, sy, jj, e_lds, lap, nlaps, &sc);
+    tb_rx_src_load<QM>(f, vec, jj, sy);
+    tb_rx_scatter_symbol<QM, ONE, true, tb_rx_src_raw<SRC>::value>(g, sy, jj, e_lds, lap, nlaps, &sc);
   }
 }
 
@@ -419,9 +440,9 @@ __device__ __forceinline__ void tb_rx_scr_fill(uint32_t *seq, uint32_t c_init, u
       seq[i + 1u] = nr_gold_step1(a) ^ nr_gold_step2(b);
   }
 }
-/* phases Z and A of a scrambled segment (tb_rx_dematch_block_scr); returns behind the barrier that ends phase A */
-template <int QM>
-__device__ __forceinline__ void tb_rx_scr_phases_za(const tb_rx_geom &g, const int16_t *__restrict__ f, int8_t *__restrict__ l, int16_t *e_lds,
+/* phases Z and A of a scrambled segment (tb_rx_dematch_block_scr / _sym); returns behind the barrier that ends phase A */
+template <int QM, class SRC = const int16_t *>
+__device__ __forceinline__ void tb_rx_scr_phases_za(const tb_rx_geom &g, const SRC f, int8_t *__restrict__ l, int16_t *e_lds,
                                                     uint32_t c_init, uint32_t bit_off, unsigned long long *stamps)
 {
   const uint32_t tid = threadIdx.x, nt = blockDim.x, EQ = g.E / QM, CH = tb_rx_scr_chunk(QM), nlaps = tb_rx_laps(g);
@@ -458,10 +479,10 @@ __device__ __forceinline__ void tb_rx_scr_phases_za(const tb_rx_geom &g, const i
       stamps[0] = wall_clock64();
     const tb_rx_scr sc{seq, bit_off - 32u * w0};
     if (nlaps == 1) {
-      tb_rx_phase_scatter_chunk<QM, true>(g, f, e_lds, 0, 1, tid, nt, sc, c0, c1);
+      tb_rx_phase_scatter_chunk<QM, true, SRC>(g, f, e_lds, 0, 1, tid, nt, sc, c0, c1);
     } else {
       for (uint32_t lap = 0; lap < nlaps; lap++) {
-        tb_rx_phase_scatter_chunk<QM, false>(g, f, e_lds, lap, nlaps, tid, nt, sc, c0, c1);
+        tb_rx_phase_scatter_chunk<QM, false, SRC>(g, f, e_lds, lap, nlaps, tid, nt, sc, c0, c1);
         __syncthreads();
       }
     }
@@ -479,6 +500,26 @@ __device__ __forceinline__ void tb_rx_dematch_block_scr(const tb_rx_geom &g, uin
     case 4: tb_rx_scr_phases_za<4>(g, f, l, e_lds, c_init, bit_off, stamps); break;
     case 6: tb_rx_scr_phases_za<6>(g, f, l, e_lds, c_init, bit_off, stamps); break;
     default: tb_rx_scr_phases_za<8>(g, f, l, e_lds, c_init, bit_off, stamps); break;
+  }
+  if (stamps && threadIdx.x == 0)
+    stamps[1] = wall_clock64();
+  tb_rx_phase_stream(g, e_lds, w, l, threadIdx.x, blockDim.x);
+  if (stamps && threadIdx.x == 0)
+    stamps[2] = wall_clock64();
+}
+/* the same for a segment of a symbol record (nrLDPC_hip_ulsch_decode_symbols): rec = the block's record (4-byte aligned),
+ * plane = int16 units between its planes; the segment's symbols start at symbol bit_off / Qm of each plane (E is a multiple of
+ * Qm: every segment starts on a symbol) */
+__device__ __forceinline__ void tb_rx_dematch_block_sym(const tb_rx_geom &g, uint32_t Qm, const int16_t *__restrict__ rec, uint32_t plane,
+                                                        int16_t *__restrict__ w, int8_t *__restrict__ l, int16_t *e_lds, uint32_t c_init,
+                                                        uint32_t bit_off, unsigned long long *stamps = nullptr)
+{
+  const uint32_t *r32 = reinterpret_cast<const uint32_t *>(rec);
+  switch (Qm) {
+    case 2: tb_rx_scr_phases_za<2>(g, tb_rx_sym_src{r32 + bit_off / 2u, plane / 2u}, l, e_lds, c_init, bit_off, stamps); break;
+    case 4: tb_rx_scr_phases_za<4>(g, tb_rx_sym_src{r32 + bit_off / 4u, plane / 2u}, l, e_lds, c_init, bit_off, stamps); break;
+    case 6: tb_rx_scr_phases_za<6>(g, tb_rx_sym_src{r32 + bit_off / 6u, plane / 2u}, l, e_lds, c_init, bit_off, stamps); break;
+    default: tb_rx_scr_phases_za<8>(g, tb_rx_sym_src{r32 + bit_off / 8u, plane / 2u}, l, e_lds, c_init, bit_off, stamps); break;
   }
   if (stamps && threadIdx.x == 0)
     stamps[1] = wall_clock64();

@@ -219,7 +219,8 @@ template <bool LROW, bool MUTE = false> struct tb_rx_fused_io {
   }
 };
 
-template <bool LROW, bool MUTE, int ZC = 0, bool SCR = false>
+/* SCR: a scrambled codeword; SYM (with SCR): received as a symbol record (nrLDPC_hip_ulsch_decode_symbols) */
+template <bool LROW, bool MUTE, int ZC = 0, bool SCR = false, bool SYM = false>
 __global__ void __launch_bounds__(1024) tb_rx_fused_kernel(const ldpc_dec_args a, const tb_rx_fused_args x)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
@@ -250,7 +251,10 @@ __global__ void __launch_bounds__(1024) tb_rx_fused_kernel(const ldpc_dec_args a
       l = reinterpret_cast<int8_t *>(fsm + x.lrow_off);
     else
       l = const_cast<int8_t *>(a.llr) + sj->l_off;
-    if constexpr (SCR)
+    if constexpr (SYM)
+      tb_rx_dematch_block_sym(g, sj->Qm, x.llr + (sj->llr_off - sj->bit_off), sj->plane, x.harq + sj->harq_off, l, reinterpret_cast<int16_t *>(fsm),
+                              sj->c_init, sj->bit_off, tr ? tr + 7 : nullptr);
+    else if constexpr (SCR)
       tb_rx_dematch_block_scr(g, sj->Qm, x.llr + sj->llr_off, x.harq + sj->harq_off, l, reinterpret_cast<int16_t *>(fsm), sj->c_init,
                               sj->bit_off, tr ? tr + 7 : nullptr);
     else
@@ -291,15 +295,15 @@ __global__ void __launch_bounds__(1024) tb_rx_fused_kernel(const ldpc_dec_args a
     a.n_iter[(uint32_t)job->iter_idx] = n_iter;
 }
 
-template <bool SCR> static hipError_t tb_rx_fused_init_t(void)
+template <bool SCR, bool SYM = false> static hipError_t tb_rx_fused_init_t(void)
 {
-  const void *k[] = {reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false, 0, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false, 0, SCR>),
+  const void *k[] = {reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false, 0, SCR, SYM>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false, 0, SCR, SYM>),
 #define X(z) \
-                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false, z, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false, z, SCR>), \
-                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true, z, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true, z, SCR>),
+                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, false, z, SCR, SYM>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, false, z, SCR, SYM>), \
+                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true, z, SCR, SYM>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true, z, SCR, SYM>),
                      LDPC_FAST_ZC_LIST(X)
 #undef X
-                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true, 0, SCR>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true, 0, SCR>)};
+                     reinterpret_cast<const void *>(tb_rx_fused_kernel<false, true, 0, SCR, SYM>), reinterpret_cast<const void *>(tb_rx_fused_kernel<true, true, 0, SCR, SYM>)};
   for (const void *f : k) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess)
@@ -309,11 +313,13 @@ template <bool SCR> static hipError_t tb_rx_fused_init_t(void)
 }
 hipError_t tb_rx_fused_init(void)
 {
-  const hipError_t e = tb_rx_fused_init_t<false>();
-  return e != hipSuccess ? e : tb_rx_fused_init_t<true>();
+  hipError_t e = tb_rx_fused_init_t<false>();
+  if (e == hipSuccess)
+    e = tb_rx_fused_init_t<true>();
+  return e != hipSuccess ? e : tb_rx_fused_init_t<true, true>();
 }
 
-template <bool SCR>
+template <bool SCR, bool SYM = false>
 static hipError_t tb_launch_rx_fused_t(const ldpc_dec_args &a, const tb_rx_fused_args &x, int n_threads, int lds_bytes, uint32_t n_jobs, hipStream_t s)
 {
   if (ldpc_fast_zc_enabled((int)x.zc)) { /* every job has this lifting size: the instantiations with compile-time row strides */
@@ -321,13 +327,13 @@ static hipError_t tb_launch_rx_fused_t(const ldpc_dec_args &a, const tb_rx_fused
 #define X(z) \
   case z: \
     if (x.lrow_off && x.mute) \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<true, true, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<true, true, z, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     else if (x.lrow_off) \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<true, false, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<true, false, z, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     else if (x.mute) \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<false, true, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<false, true, z, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     else \
-      hipLaunchKernelGGL((tb_rx_fused_kernel<false, false, z, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
+      hipLaunchKernelGGL((tb_rx_fused_kernel<false, false, z, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x); \
     return hipGetLastError();
       LDPC_FAST_ZC_LIST(X)
 #undef X
@@ -336,13 +342,13 @@ static hipError_t tb_launch_rx_fused_t(const ldpc_dec_args &a, const tb_rx_fused
     }
   }
   if (x.lrow_off && x.mute)
-    hipLaunchKernelGGL((tb_rx_fused_kernel<true, true, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<true, true, 0, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   else if (x.lrow_off)
-    hipLaunchKernelGGL((tb_rx_fused_kernel<true, false, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<true, false, 0, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   else if (x.mute)
-    hipLaunchKernelGGL((tb_rx_fused_kernel<false, true, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<false, true, 0, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   else
-    hipLaunchKernelGGL((tb_rx_fused_kernel<false, false, 0, SCR>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
+    hipLaunchKernelGGL((tb_rx_fused_kernel<false, false, 0, SCR, SYM>), dim3(n_jobs), dim3(n_threads), lds_bytes, s, a, x);
   return hipGetLastError();
 }
 
@@ -352,5 +358,7 @@ hipError_t tb_launch_rx_fused(const ldpc_dec_args &a, const tb_rx_fused_args &x,
     return hipSuccess;
   if (!a.jobs || !x.segs || !x.tbs)
     return hipErrorInvalidValue;
+  if (x.scr && x.sym)
+    return tb_launch_rx_fused_t<true, true>(a, x, n_threads, lds_bytes, n_jobs, s);
   return x.scr ? tb_launch_rx_fused_t<true>(a, x, n_threads, lds_bytes, n_jobs, s) : tb_launch_rx_fused_t<false>(a, x, n_threads, lds_bytes, n_jobs, s);
 }

@@ -439,6 +439,8 @@ def _tb_lib():
     if hasattr(L, "nrLDPC_hip_dlsch_encode_scrambled"):
         L.nrLDPC_hip_dlsch_encode_scrambled.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
         L.nrLDPC_hip_ulsch_decode_scrambled.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
+    if hasattr(L, "nrLDPC_hip_ulsch_decode_symbols"):
+        L.nrLDPC_hip_ulsch_decode_symbols.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
     L.nrLDPC_hip_segmentation.argtypes = [C.c_uint32, C.c_uint8] + [C.POINTER(C.c_uint32)] * 4
     L.nrLDPC_hip_segmentation.restype = C.c_int32
     L.nrLDPC_hip_get_E.argtypes = [C.c_uint32] * 5
@@ -572,18 +574,29 @@ def ulsch_decode_scrambled_host(tbs, llrs, harq, scrambling, numMaxIter=8, harq_
     return _ulsch_decode_host(tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, _scr_array(scrambling, len(tbs)))
 
 
-def _decode_call(L, b, scr):
-    if scr is None:
+def ulsch_decode_symbols_host(tbs, records, harq, scrambling, numMaxIter=8, harq_off=None, harq_ids=None, pinned=False,
+                              payload_off=None):
+    """ulsch_decode_scrambled_host from symbol records (nrLDPC_hip_ulsch_decode_symbols): records[i] = TB i's int16[G] planar
+    record (pack_symbol_records).  The same results as ulsch_llr() of every TB's symbols followed by
+    ulsch_decode_scrambled_host."""
+    return _ulsch_decode_host(tbs, records, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, _scr_array(scrambling, len(tbs)),
+                              sym=True)
+
+
+def _decode_call(L, b, scr, sym=False):
+    if sym:
+        _check(L.nrLDPC_hip_ulsch_decode_symbols(C.byref(b), scr), "nrLDPC_hip_ulsch_decode_symbols")
+    elif scr is None:
         _check(L.nrLDPC_hip_ulsch_decode(C.byref(b)), "nrLDPC_hip_ulsch_decode")
     else:
         _check(L.nrLDPC_hip_ulsch_decode_scrambled(C.byref(b), scr), "nrLDPC_hip_ulsch_decode_scrambled")
 
 
-def _ulsch_decode_host(tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, scr):
+def _ulsch_decode_host(tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, scr, sym=False):
     L = _tb_lib()
     n = len(tbs)
     if harq_ids is not None or not isinstance(harq, np.ndarray):
-        return _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, scr)
+        return _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off, scr, sym)
     po = np.cumsum([0] + [(t["A"] // 8 + 15) // 16 * 16 for t in tbs])
     pay_total = int(po[-1])
     if payload_off is not None:
@@ -607,13 +620,13 @@ def _ulsch_decode_host(tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, 
     b = nrLDPC_hip_tb_batch_t(n_tb=n, tb=arr, payload=pay.ctypes.data, coded=llr.ctypes.data, harq=harq.ctypes.data,
                               harq_stride=HARQ_STRIDE, ack=ack.ctypes.data, iter_max=itm.ctypes.data, mem=MEM_HOST,
                               stream=None)
-    _decode_call(L, b, scr)
+    _decode_call(L, b, scr, sym)
     for i, t in enumerate(tbs):
         t["llrLen"] = arr[i].llrLen
     return [pay[po[i]:po[i] + tbs[i]["A"] // 8].copy() for i in range(n)], ack.astype(bool), itm
 
 
-def _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off=None, scr=None):
+def _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_ids, pinned, payload_off=None, scr=None, sym=False):
     """host payload / LLRs / verdicts with the soft buffers resident on the GPU (see ulsch_decode_host)"""
     n = len(tbs)
     po = np.cumsum([0] + [(t["A"] // 8 + 15) // 16 * 16 for t in tbs])
@@ -640,7 +653,7 @@ def _ulsch_decode_host_resident(L, tbs, llrs, harq, numMaxIter, harq_off, harq_i
     arr = _tb_array(tbs, po, co, ho, numMaxIter)
     b = nrLDPC_hip_tb_batch_t(n_tb=n, tb=arr, payload=pay.ctypes.data, coded=llr.ctypes.data, harq=hp,
                               harq_stride=HARQ_STRIDE, ack=ack.ctypes.data, iter_max=itm.ctypes.data, mem=mem, stream=None)
-    _decode_call(L, b, scr)
+    _decode_call(L, b, scr, sym)
     for i, t in enumerate(tbs):
         t["llrLen"] = arr[i].llrLen
     return [pay[po[i]:po[i] + tbs[i]["A"] // 8].copy() for i in range(n)], ack.astype(bool), itm
@@ -726,13 +739,16 @@ class PreparedTbBatch:
     PinnedArray objects with mem = MEM_HOST, optionally | MEM_HARQ_DEVICE (harq a CUDA tensor) or | MEM_HARQ_LIBRARY
     (harq None, harq_ids = one id per transport block).  scrambling = one (n_rnti, q, n_id) per transport block: the calls
     are nrLDPC_hip_dlsch_encode_scrambled / nrLDPC_hip_ulsch_decode_scrambled, and an encode's output follows
-    tb_layout_packed."""
+    tb_layout_packed.  symbols=True (with scrambling): coded_or_llr holds the TBs' symbol records (pack_symbol_records) and
+    decode() is nrLDPC_hip_ulsch_decode_symbols."""
 
     def __init__(self, tbs, payload, coded_or_llr, harq=None, ack=None, iter_max=None, numMaxIter=8, stream=None, mem=MEM_DEVICE,
-                 harq_ids=None, scrambling=None):
+                 harq_ids=None, scrambling=None, symbols=False):
         self._lib = _tb_lib()
         po, co, ho, _ = tb_layout(tbs)
         self.scr = None if scrambling is None else _scr_array(scrambling, len(tbs))
+        assert not symbols or self.scr is not None, "symbol records are always scrambled: pass scrambling"
+        self.sym = bool(symbols)
         self._coded_packed = tb_layout_packed(tbs)[0]
         self._keep = (payload, coded_or_llr, harq, ack, iter_max)
         if harq_ids is not None:
@@ -760,7 +776,7 @@ class PreparedTbBatch:
             _check(self._lib.nrLDPC_hip_dlsch_encode_scrambled(C.byref(self.batch_enc), self.scr), "nrLDPC_hip_dlsch_encode_scrambled")
 
     def decode(self):
-        _decode_call(self._lib, self.batch, self.scr)
+        _decode_call(self._lib, self.batch, self.scr, self.sym)
 
     # HIP graphs: capture on the batch's own stream (torch.cuda.graph(g, stream=<the stream the batch was made on>)) after
     # two warm-up calls there; a call whose descriptors repeat only enqueues kernels and memsets.
@@ -779,7 +795,14 @@ def ulsch_decode_scrambled_device(tbs, llr, harq, payload, ack, iter_max, scramb
     _ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter, stream, harq_ids, _scr_array(scrambling, len(tbs)))
 
 
-def _ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter, stream, harq_ids, scr):
+def ulsch_decode_symbols_device(tbs, records, harq, payload, ack, iter_max, scrambling, numMaxIter=8, stream=None, harq_ids=None):
+    """ulsch_decode_scrambled_device from symbol records (nrLDPC_hip_ulsch_decode_symbols): `records` = torch int16 [>= co[-1]]
+    with TB i's planar record (pack_symbol_records) at tb_layout co[i]; only read."""
+    _ulsch_decode_device(tbs, records, harq, payload, ack, iter_max, numMaxIter, stream, harq_ids, _scr_array(scrambling, len(tbs)),
+                         sym=True)
+
+
+def _ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter, stream, harq_ids, scr, sym=False):
     import torch
     L = _tb_lib()
     po, co, ho, _ = tb_layout(tbs)
@@ -795,7 +818,7 @@ def _ulsch_decode_device(tbs, llr, harq, payload, ack, iter_max, numMaxIter, str
     b = nrLDPC_hip_tb_batch_t(n_tb=len(tbs), tb=arr, payload=payload.data_ptr(), coded=llr.data_ptr(), harq=_ptr(harq),
                               harq_stride=HARQ_STRIDE, ack=ack.data_ptr(), iter_max=iter_max.data_ptr(), mem=mem,
                               stream=s)
-    _decode_call(L, b, scr)
+    _decode_call(L, b, scr, sym)
     for i, t in enumerate(tbs):
         t["llrLen"] = arr[i].llrLen
 
@@ -880,3 +903,102 @@ def codeword_unscrambling(llr, q, n_id, n_rnti, size=None, stream=None):
     _check(L.nrLDPC_hip_codeword_unscrambling(llr.data_ptr(), n, q, n_id, n_rnti, MEM_DEVICE, s),
            "nrLDPC_hip_codeword_unscrambling")
     return llr
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Modulation mapping and soft demapping (include/nrLDPC_hip.h: nrLDPC_hip_mod_table / _modulation / _ulsch_llr)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_mod_table", "nrLDPC_hip_modulation", "nrLDPC_hip_ulsch_llr", "nrLDPC_hip_ulsch_decode_symbols"]
+
+
+def _qam_lib():
+    L = load_library()
+    L.nrLDPC_hip_mod_table.argtypes = [C.c_uint8, C.c_void_p]
+    L.nrLDPC_hip_mod_table.restype = C.c_int32
+    L.nrLDPC_hip_modulation.argtypes = [C.c_void_p, C.c_uint32, C.c_uint8, C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_modulation.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_llr.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_uint8, C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_llr.restype = C.c_int32
+    return L
+
+
+def mod_table(Qm):
+    """int16[2^Qm, 2]: the (re, im) point of every index of the constellation of Qm (host only)"""
+    out = np.zeros((1 << Qm if Qm in (2, 4, 6, 8) else 1, 2), np.int16)
+    _check(_qam_lib().nrLDPC_hip_mod_table(Qm, out.ctypes.data), "nrLDPC_hip_mod_table")
+    return out
+
+
+def modulation(words, length, Qm, out=None, stream=None):
+    """nr_modulation: `length` bits of packed words (bit k of word w = bit 32w + k) -> length/Qm (re, im) points.  numpy
+    uint32 -> host call, returns int16[length/Qm, 2]; torch int32/uint32 CUDA tensor -> device call enqueued on `stream` into
+    `out`, a contiguous torch int16 CUDA tensor of at least 2 length/Qm elements on the same GPU; returns `out`."""
+    L = _qam_lib()
+    n_sym = length // Qm if Qm else 0
+    if isinstance(words, np.ndarray):
+        assert words.dtype in (np.uint32, np.int32)
+        src = np.ascontiguousarray(words).reshape(-1)
+        if src.size < (length + 31) // 32:
+            raise ValueError(f"{length} bits need {(length + 31) // 32} words, the array has {src.size}")
+        res = np.zeros((max(n_sym, 1), 2), np.int16)
+        _check(L.nrLDPC_hip_modulation(src.ctypes.data, length, Qm, res.ctypes.data, MEM_HOST, None), "nrLDPC_hip_modulation")
+        return res[:n_sym]
+    import torch
+    assert words.is_cuda and words.is_contiguous() and words.element_size() == 4 and words.numel() >= (length + 31) // 32
+    assert out is not None and out.is_cuda and out.device == words.device and out.is_contiguous()
+    assert out.dtype == torch.int16 and out.numel() >= 2 * n_sym
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_modulation(words.data_ptr(), length, Qm, out.data_ptr(), MEM_DEVICE, s), "nrLDPC_hip_modulation")
+    return out
+
+
+def _c16_count(a):
+    """c16 values in an int16 [n, 2] / [2n] or int32 [n] array or tensor"""
+    nb = a.size * a.itemsize if isinstance(a, np.ndarray) else a.numel() * a.element_size()
+    assert nb % 4 == 0, "c16 arrays hold whole (re, im) pairs"
+    return nb // 4
+
+
+def ulsch_llr(y, mags, Qm, out=None, stream=None):
+    """nr_ulsch_compute_llr for one stream: y = the equalised symbols, mags = (mag_a, mag_b, mag_c)[:Qm/2 - 1], all c16 (int16
+    [nb_re, 2] or int32 [nb_re]).  numpy -> host call, returns int16[nb_re * Qm]; torch CUDA tensors (contiguous, one GPU) ->
+    device call enqueued on `stream` into `out`, a contiguous torch int16 CUDA tensor of at least nb_re * Qm elements."""
+    L = _qam_lib()
+    mags = list(mags)
+    if len(mags) != max(Qm // 2 - 1, 0):
+        raise ValueError(f"Qm {Qm} takes {max(Qm // 2 - 1, 0)} magnitude arrays, got {len(mags)}")
+    nb_re = _c16_count(y)
+    for m in mags:
+        if _c16_count(m) != nb_re:
+            raise ValueError("every magnitude array has one c16 value per RE")
+    if isinstance(y, np.ndarray):
+        arrs = [np.ascontiguousarray(a) for a in [y] + mags]
+        for a in arrs:
+            assert a.dtype in (np.int16, np.int32)
+        ptrs = [a.ctypes.data for a in arrs] + [None] * (4 - len(arrs))
+        res = np.zeros(max(nb_re * Qm, 1), np.int16)
+        _check(L.nrLDPC_hip_ulsch_llr(*ptrs, nb_re, Qm, res.ctypes.data, MEM_HOST, None), "nrLDPC_hip_ulsch_llr")
+        return res[:nb_re * Qm]
+    import torch
+    arrs = [y] + mags
+    for a in arrs:
+        assert a.is_cuda and a.is_contiguous() and a.dtype in (torch.int16, torch.int32) and a.device == y.device
+    assert out is not None and out.is_cuda and out.device == y.device and out.is_contiguous()
+    assert out.dtype == torch.int16 and out.numel() >= nb_re * Qm
+    ptrs = [a.data_ptr() for a in arrs] + [None] * (4 - len(arrs))
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_ulsch_llr(*ptrs, nb_re, Qm, out.data_ptr(), MEM_DEVICE, s), "nrLDPC_hip_ulsch_llr")
+    return out
+
+
+def pack_symbol_records(blocks):
+    """The planar symbol records of nrLDPC_hip_ulsch_decode_symbols: blocks[i] = (y, mag_a, ...) of one TB, Qm/2 c16 arrays of
+    S = G/Qm values each in codeword symbol order (numpy int16 [S, 2] or int32 [S]) -> int16[G] per TB: y's S values, then
+    mag_a's, ... (place record i at tb_layout co[i] of the call's array)."""
+    out = []
+    for planes in blocks:
+        ps = [np.ascontiguousarray(p).view(np.int16).reshape(-1) for p in planes]
+        if any(p.size != ps[0].size for p in ps):
+            raise ValueError("every plane of a record has S c16 values")
+        out.append(np.concatenate(ps).astype(np.int16, copy=False))
+    return out
