@@ -349,6 +349,26 @@ int32_t nrLDPC_hip_ulsch_llr(const int32_t *rxdataF_comp, const int32_t *ul_ch_m
  * Negative -- before anything is enqueued or written -- for anything decode_scrambled refuses, G % Qm != 0, a bad Qm, a
  * record that is not 4-byte aligned. */
 int32_t nrLDPC_hip_ulsch_decode_symbols(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr);
+/* The DL-SCH chain call that ends in layer-mapped symbols: the reference's PDSCH path from the transport block to the hand-off
+ * to resource mapping (openair1/PHY/NR_TRANSPORT/nr_dlsch.c:150-205: nr_dlsch_encoding, nr_codeword_scrambling, nr_modulation,
+ * nr_layer_mapping into tx_layers[Nl][...]) for one codeword per block.  With S = G/Qm, block i's output is written at
+ * coded + coded_off (coded_off a byte offset, a multiple of 4; coded 4-byte aligned): Nl layer planes one after another, each
+ * S/Nl c16 points (int16 re, im) -- exactly 4 G/Qm bytes per block, nothing outside them.  Entry k of plane l is the point of
+ * codeword symbol k Nl + l; the point of symbol s is the nr_qam.h / nrLDPC_hip_mod_table entry of bits sQm .. sQm+Qm-1 of the
+ * scrambled codeword (bit b = index bit b, as nrLDPC_hip_modulation).  Bit for bit: nrLDPC_hip_dlsch_encode_scrambled, then
+ * nrLDPC_hip_modulation(G), then nrLDPC_hip_layer_mapping(Nl, layer_stride = S/Nl).  With Nl = 1 the output is the modulation
+ * output; the layout is that of the UL symbol record.  Every mem mode and the multi-GPU cut of the encode calls.  Negative --
+ * before anything is enqueued or written -- for anything encode_scrambled refuses, Nl > 4 (layers 5-8 carry two codewords in
+ * the reference, and a block here is one), coded_off % 4 != 0, or a `coded` that is not 4-byte aligned.
+ * layer_mapping: nr_layer_mapping for one codeword (openair1/PHY/MODULATION/nr_modulation.c:246-270), Nl = 1..4:
+ * out[l layer_stride + i] = in[Nl i + l] for i < n_symbs/Nl, in c16 units; layer_stride (>= n_symbs/Nl) plays the role of
+ * the reference's layerSz, and nothing between the planes is written.  `in` and `out` must not overlap.  mem as
+ * nrLDPC_hip_modulation (HOST synchronous, DEVICE enqueued on `stream`, both arrays device memory of one GPU).  0, or negative
+ * -- before anything is enqueued or written -- for n_symbs % Nl != 0, a bad Nl, a short stride, n_symbs > 2^21, overlapping
+ * arrays, another mem value, a NULL array or (DEVICE) an array that is not device memory of that GPU. */
+int32_t nrLDPC_hip_dlsch_encode_symbols(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr);
+int32_t nrLDPC_hip_layer_mapping(const int16_t *in, uint32_t n_symbs, uint8_t Nl, int16_t *out, uint32_t layer_stride, int32_t mem,
+                                 void *stream);
 /* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one

@@ -1,7 +1,9 @@
 /*
  * qam_api.inc.cpp -- modulation mapping, soft demapping and the UL-SCH chain call that takes symbols (included at the end of
  * ldpc_api.cpp, behind scrambling_api.inc.cpp whose checks it shares).  The constellations and the demapper: nr_qam.h; the
- * standalone kernels: tb_qam.hip; the demapper inside the chain: tb_rx_core.h (the symbol source of phase A).
+ * standalone kernels: tb_qam.hip; the demapper inside the chain: tb_rx_core.h (the symbol source of phase A).  And the DL-SCH
+ * chain call that ends in layer-mapped symbols (the fused segment kernel's symbol store: tb_tx_sym.h) with the standalone
+ * layer mapping.
  */
 
 namespace {
@@ -27,6 +29,22 @@ int sym_check_batch(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *s
       return set_error("decode_symbols: G must be a multiple of Qm");
     if (b->tb[i].coded_off & 1u)
       return set_error("decode_symbols: coded_off must be even");
+  }
+  return 0;
+}
+
+/* encode_symbols: what encode_scrambled checks, one codeword per block (Nl <= 4), every block valid, a 4-byte aligned array */
+int sym_check_encode(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
+{
+  if (scr_check_batch(b, scr, true) != 0)
+    return -1;
+  if (b->n_tb && (reinterpret_cast<uintptr_t>(b->coded) & 3u))
+    return set_error("encode_symbols: coded must be 4-byte aligned");
+  for (uint32_t i = 0; i < b->n_tb; i++) {
+    if (b->tb[i].Nl > 4)
+      return set_error("encode_symbols: Nl above 4 (layers 5-8 carry two codewords)");
+    if (tb_validate(b->tb[i]) != 0)
+      return -1;
   }
   return 0;
 }
@@ -164,6 +182,71 @@ int32_t nrLDPC_hip_ulsch_decode_symbols(const nrLDPC_hip_tb_batch_t *b, const nr
                                                               : tb_rx_enqueue(b, tb0, n, staged, s, nullptr, scr + tb0, true);
       },
       [&](uint32_t tb0, uint32_t n) { return tb_rx_finish(b, tb0, n); });
+}
+
+int32_t nrLDPC_hip_dlsch_encode_symbols(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
+{
+  if (!b || !b->tb || !b->payload || !b->coded)
+    return set_error("null argument");
+  if (b->mem & ~NRLDPC_HIP_MEM_DEVICE)
+    return set_error("encode: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (sym_check_encode(b, scr) != 0)
+    return -1;
+  if (b->n_tb == 0)
+    return ensure_ready();
+  return tb_run_sharded(
+      b, [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) { return tb_tx_enqueue(b, tb0, n, staged, s, scr + tb0, true); },
+      [&](uint32_t, uint32_t n) { return tb_tx_finish(b, n); });
+}
+
+int32_t nrLDPC_hip_layer_mapping(const int16_t *in, uint32_t n_symbs, uint8_t Nl, int16_t *out, uint32_t layer_stride, int32_t mem, void *stream)
+{
+  if (Nl < 1 || Nl > 4)
+    return set_error("layer_mapping: Nl must be 1..4 (one codeword)");
+  if (n_symbs % Nl)
+    return set_error("layer_mapping: n_symbs must be a multiple of Nl");
+  if (n_symbs > NR_SCR_MAX_BITS)
+    return set_error("layer_mapping: n_symbs above 2^21");
+  const uint32_t per_layer = n_symbs / Nl;
+  if (layer_stride < per_layer)
+    return set_error("layer_mapping: layer_stride below n_symbs / Nl");
+  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
+    return set_error("layer_mapping: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (n_symbs && (!in || !out))
+    return set_error("null argument");
+  if (n_symbs == 0)
+    return 0;
+  const size_t in_bytes = (size_t)n_symbs * 4u, plane_bytes = (size_t)per_layer * 4u;
+  const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+  if (i0 < o0 + ((size_t)(Nl - 1) * layer_stride * 4u + plane_bytes) && o0 < i0 + in_bytes)
+    return set_error("layer_mapping: in and out overlap");
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    const int ord = scr_device_ordinal(in);
+    if (ord < 0 || scr_device_ordinal(out) != ord)
+      return set_error("layer_mapping: DEVICE mem needs `in` and `out` in device memory of one GPU");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    HIP_TRY(nr_launch_layer_mapping(in, n_symbs, Nl, out, layer_stride, static_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  if (c.ensure(align_up(in_bytes, 16), in_bytes) != 0)
+    return -1;
+  memcpy(c.h_in, in, in_bytes);
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, in_bytes, hipMemcpyHostToDevice, c.stream));
+  /* the planes side by side on the device; on the host each goes to its place (nothing between them is written) */
+  HIP_TRY(nr_launch_layer_mapping(reinterpret_cast<const int16_t *>(c.d_in), n_symbs, Nl, reinterpret_cast<int16_t *>(c.d_out), per_layer,
+                                  c.stream));
+  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, in_bytes, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  for (uint32_t l = 0; l < Nl; l++)
+    memcpy(reinterpret_cast<uint8_t *>(out) + (size_t)l * layer_stride * 4u, c.h_out + l * plane_bytes, plane_bytes);
+  return 0;
 }
 
 } /* extern "C" */

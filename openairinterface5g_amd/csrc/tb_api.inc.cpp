@@ -443,9 +443,12 @@ struct TbExtent {
   } while (0)
 
 /* scr != nullptr (nrLDPC_hip_dlsch_encode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the chain's bit-per-byte output goes
- * to scratch, and one more launch packs and scrambles every block into its ceil(G/32) words at coded + coded_off */
+ * to scratch, and one more launch packs and scrambles every block into its ceil(G/32) words at coded + coded_off.
+ * sym (with scr; nrLDPC_hip_dlsch_encode_symbols): each block's output is its scrambled, mapped and layer-mapped points instead,
+ * Nl planes of G / (Qm Nl) c16 words = 4 G / Qm bytes at coded + coded_off -- stored by the fused kernel's symbol instantiation,
+ * or (three-kernel path) by one launch from the bytes in scratch */
 int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
-                  const nrLDPC_hip_tb_scr_t *scr = nullptr)
+                  const nrLDPC_hip_tb_scr_t *scr = nullptr, bool sym = false)
 {
   hipStream_t s;
   if (tb_begin(s, s_direct, staged) != 0)
@@ -455,8 +458,9 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
   const nrLDPC_hip_tb_t *tbs = b->tb + tb0;
   TbCtx &c = tls_tb;
   const bool fused = ldpc_enc_is_packed() != 0;
-  /* bit 2: scrambled (its key also holds the scr bytes: a scrambled and an unscrambled plan never match) */
-  const uint64_t salt[3] = {(fused ? 1u : 0u) | (tb_trunc_enabled() ? 2u : 0u) | (scr ? 4u : 0u), 0, 0};
+  /* bit 2: scrambled (its key also holds the scr bytes: a scrambled and an unscrambled plan never match); bit 3: symbols (never
+   * a packed-word plan, nor the reverse) */
+  const uint64_t salt[3] = {(fused ? 1u : 0u) | (tb_trunc_enabled() ? 2u : 0u) | (scr ? 4u : 0u) | (sym ? 8u : 0u), 0, 0};
   const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
   TbPlan *hit = c.tx.find(tbs, ntb, salt, scr, scr_n);
   TbPlan &pl = hit ? *hit : c.tx.victim();
@@ -466,7 +470,8 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     std::vector<ldpc_enc_job> ej;
     std::vector<tb_crc_chunk_job> cj;
     /* scrambled, three-kernel path: the bytes in scratch, then one packing launch (pj) */
-    std::vector<tb_scr_tb_job> pj(scr && !fused ? ntb : 0);
+    std::vector<tb_scr_tb_job> pj(scr && !sym && !fused ? ntb : 0);
+    std::vector<tb_sym_tb_job> qj(sym && !fused ? ntb : 0); /* ... or, for symbols, one scrambling + mapping launch */
     uint32_t max_g = 0;
     uint32_t n_tickets = 0; /* scrambled, fused path: the words several segments share, and their parts */
     size_t n_parts = 0;
@@ -500,11 +505,19 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       ex.add(ex.pay_lo, ex.pay_hi, (size_t)t.payload_off, (size_t)t.payload_off + t.A / 8);
       /* scrambled: the caller's array takes the packed words.  Fused: the segment kernel stores them itself (out_off = the TB's
        * first byte); three-kernel path: the bytes stay in scratch at byte_base for the packing launch */
-      const size_t out_len = scr ? (size_t)((t.G + 31u) / 32u) * 4u : (size_t)t.G;
+      const size_t out_len = sym ? (size_t)(t.G / t.Qm) * 4u : scr ? (size_t)((t.G + 31u) / 32u) * 4u : (size_t)t.G;
       const bool scr_bytes = scr && !fused;
       const uint64_t byte_base = scr_bytes ? (uint64_t)ar.take(t.G + 16) : t.coded_off;
       const size_t seg_first = sj.size();
-      if (scr_bytes) {
+      if (scr_bytes && sym) {
+        qj[i].in_off = byte_base;
+        qj[i].out_off = t.coded_off;
+        qj[i].G = t.G;
+        qj[i].c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
+        qj[i].Qm = t.Qm;
+        qj[i].Nl = t.Nl;
+        max_g = std::max(max_g, t.G / t.Qm); /* (symbols) */
+      } else if (scr_bytes) {
         pj[i].in_off = byte_base;
         pj[i].out_off = t.coded_off;
         pj[i].G = t.G;
@@ -537,6 +550,10 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         if (scr && fused) {
           j.c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
           j.bit_off = r_offset;
+        }
+        if (sym && fused) {
+          j.Nl = t.Nl;
+          j.plane = t.G / (t.Qm * t.Nl);
         }
         j.r = r; j.C = sg.C; j.Kprime = sg.Kprime; j.L = sg.L; j.K = sg.K;
         j.E = nr_hip_get_E(t.G, sg.C, t.Qm, t.Nl, r);
@@ -573,7 +590,7 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         e.code = ce_seg->dev; e.in_off = j.c_off; e.out_off = j.d_off; e.Kb = (int32_t)sg.Kb; e.pad = 0;
         ej.push_back(e);
       }
-      if (scr && fused) {
+      if (scr && fused && !sym) { /* (a segment's points are its own: nr_hip_get_E gives every segment whole layer groups) */
         /* words the block's segments share (tb_tx_settle_word): a segment's first word when it starts inside a word, its last
          * word when it ends inside one and is not the block's last segment (behind G the last word is 0: complete) -- once
          * per segment and word; each word gets a ticket and one part slot per segment that touches it */
@@ -607,13 +624,14 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
                  o_acc = o_chk + align_up(cj.size() * sizeof(tb_crc_chunk_job), 16),
                  /* CRC accumulators, uploaded as zeros: one per block (unfused path, atomics) / one per chunk (fused) */
                  o_scr = o_acc + align_up(std::max<size_t>(ntb, cj.size()) * sizeof(uint32_t), 16),
-                 o_tk = o_scr + align_up(pj.size() * sizeof(tb_scr_tb_job), 16),  /* tickets: uploaded as zeros, left zero */
+                 o_tk = o_scr + align_up(pj.size() * sizeof(tb_scr_tb_job) + qj.size() * sizeof(tb_sym_tb_job), 16), /* tickets: zeros, left zero */
                  o_pt = o_tk + align_up((size_t)n_tickets * 4, 16),                /* parts */
                  jobs_bytes = o_pt + align_up(n_parts * 4, 16);
     if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_bytes) != 0 || pl.jobs_d.ensure(jobs_bytes) != 0)
       return -1;
     memset(c.jobs_h.p + o_acc, 0, o_scr - o_acc);
     memcpy(c.jobs_h.p + o_scr, pj.data(), pj.size() * sizeof(tb_scr_tb_job));
+    memcpy(c.jobs_h.p + o_scr, qj.data(), qj.size() * sizeof(tb_sym_tb_job)); /* (one of the two is empty) */
     memset(c.jobs_h.p + o_tk, 0, jobs_bytes - o_tk);
     memcpy(c.jobs_h.p + o_chk, cj.data(), cj.size() * sizeof(tb_crc_chunk_job));
     memcpy(c.jobs_h.p + o_tb, tbj.data(), tbj.size() * sizeof(tb_tx_tb_job));
@@ -629,7 +647,7 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       std::vector<size_t> len(ntb);
       for (uint32_t i = 0; i < ntb; i++) {
         off[i] = tbs[i].coded_off;
-        len[i] = scr ? (size_t)((tbs[i].G + 31u) / 32u) * 4u : (size_t)tbs[i].G;
+        len[i] = sym ? (size_t)(tbs[i].G / tbs[i].Qm) * 4u : scr ? (size_t)((tbs[i].G + 31u) / 32u) * 4u : (size_t)tbs[i].G;
       }
       pl.build_out_runs(off.data(), len.data(), ntb);
     }
@@ -677,7 +695,10 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
      * a launch that does not even fill the GPU four deep takes 512 and halves the rounds of its long stages */
     const int fused_threads = n_seg <= (size_t)4 * (size_t)G().n_cus ? 512 : enc_threads;
     TB_DEBUG_STAGE("tx: TB CRC launch");
-    if (scr)
+    if (sym)
+      HIP_TRY(tb_launch_tx_fused_sym(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS + TB_TX_FUSED_SYM_LDS, payload,
+                                     coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
+    else if (scr)
       HIP_TRY(tb_launch_tx_fused_scr(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS + TB_TX_FUSED_SCR_LDS, payload,
                                      coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.off[7]),
                                      reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.off[8]), s));
@@ -696,7 +717,11 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     HIP_TRY(tb_launch_tx_ratematch(d_seg, (uint32_t)n_seg, c.scratch.p, coded, s));
     TB_DEBUG_STAGE("tx: segment + rate matching launches");
   }
-  if (scr && !fused) {
+  if (sym && !fused) {
+    HIP_TRY(nr_launch_scramble_map_tb(reinterpret_cast<const tb_sym_tb_job *>(pl.jobs_d.p + pl.off[5]), ntb, (uint32_t)pl.off[6], c.scratch.p,
+                                      out_words, s));
+    TB_DEBUG_STAGE("tx: scrambled, mapped, layer-mapped store");
+  } else if (scr && !fused) {
     HIP_TRY(nr_launch_scramble_bits_tb(reinterpret_cast<const tb_scr_tb_job *>(pl.jobs_d.p + pl.off[5]), ntb, (uint32_t)pl.off[6], c.scratch.p,
                                        out_words, s));
     TB_DEBUG_STAGE("tx: packed scrambled store");
@@ -765,12 +790,15 @@ int16_t *harq_lookup(uint64_t id, size_t n, bool fresh, hipStream_t s)
       harq_tbl.pool.erase(harq_tbl.pool.begin() + (long)k);
       break;
     }
+  const bool new_mem = !e.p;
   if (!e.p && hipMalloc(reinterpret_cast<void **>(&e.p), n * sizeof(int16_t)) != hipSuccess) {
     set_error("soft buffer allocation");
     return nullptr;
   }
-  hipError_t err = hipSuccess;
-  if (it != harq_tbl.m.end()) {
+  /* new memory holds whatever an earlier allocation of the process left there: zeroed, so that what a first transmission
+   * never touches (a row behind its Ncb values) reads the same for every new id (nrLDPC_hip_harq_read) */
+  hipError_t err = (new_mem && fresh) ? hipMemsetAsync(e.p, 0, n * sizeof(int16_t), s) : hipSuccess;
+  if (err == hipSuccess && it != harq_tbl.m.end()) {
     if (!fresh) {
       const size_t keep = std::min(n, it->second.n);
       err = hipMemcpyAsync(e.p, it->second.p, keep * sizeof(int16_t), hipMemcpyDefault, s);
@@ -780,7 +808,7 @@ int16_t *harq_lookup(uint64_t id, size_t n, bool fresh, hipStream_t s)
         err = hipStreamSynchronize(s); /* the old buffers go back to the pool below */
     }
     harq_tbl.pool.push_back(it->second);
-  } else if (!fresh) {
+  } else if (err == hipSuccess && !fresh) {
     err = hipMemsetAsync(e.p, 0, n * sizeof(int16_t), s);
   }
   if (err != hipSuccess) {

@@ -30,6 +30,10 @@ hipError_t tb_launch_tx_fused(const tb_tx_seg_job *jobs, const struct ldpc_enc_j
 hipError_t tb_launch_tx_fused_scr(const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
                                   const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets,
                                   uint32_t *parts, hipStream_t s);
+/* the same with the symbol store (nrLDPC_hip_dlsch_encode_symbols; jobs' c_init / bit_off / Nl / plane, tb_tx_sym.h): 4 G / Qm
+ * bytes of layer planes per TB at coded + out_off; lds_bytes includes TB_TX_FUSED_SYM_LDS */
+hipError_t tb_launch_tx_fused_sym(const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
+                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, hipStream_t s);
 hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
                                 int8_t *scratch, hipStream_t s, int wide = 0);
 /* scrambled codewords: each segment's LLRs are unscrambled on the way in (jobs' c_init / bit_off; tb_rx_core.h) */
@@ -99,6 +103,11 @@ hipError_t nr_launch_ulsch_llr(const uint32_t *const planes[4], uint32_t nb_re, 
 /* the first for every transport block of an encode call in one launch: jobs[i] packs G bits from in + in_off into the words at
  * out + out_off (4-byte aligned); max_g = the largest G */
 hipError_t nr_launch_scramble_bits_tb(const tb_scr_tb_job *jobs, uint32_t n_tb, uint32_t max_g, const uint8_t *in, uint8_t *out, hipStream_t s);
+/* the symbol encode's three-kernel path: jobs[i] scrambles, maps and layer-maps G bits (one per byte) from in + in_off into Nl
+ * planes of G / (Qm Nl) points at out + out_off (4-byte aligned), every transport block in one launch; max_s = the largest G / Qm */
+hipError_t nr_launch_scramble_map_tb(const tb_sym_tb_job *jobs, uint32_t n_tb, uint32_t max_s, const uint8_t *in, uint8_t *out, hipStream_t s);
+/* nr_layer_mapping for one codeword: out[l stride + i] = in[Nl i + l], c16 words, i < n_symbs / Nl, Nl = 1..4 (tb_qam.hip) */
+hipError_t nr_launch_layer_mapping(const int16_t *in, uint32_t n_symbs, uint32_t Nl, int16_t *out, uint32_t stride, hipStream_t s);
 /* reassembly per segment (payload copy + partial TB CRC into acc[tb], zero on entry and on exit), then per-TB verdict */
 hipError_t tb_launch_rx_assemble(const tb_rx_tb_job *jobs, uint32_t n_tb, const tb_rx_seg_job *segs, uint32_t n_seg,
                                  const int32_t *n_iter, uint8_t *scratch, uint8_t *payload, uint8_t *ack, int32_t *iter_max,

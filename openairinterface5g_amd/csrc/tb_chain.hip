@@ -26,8 +26,12 @@
 #define TB_RX_STORE_WINDOW 2
 #endif
 #include "tb_rx_core.h"
+#include "tb_tx_sym.h"
+#include "nr_qam.h"
 
 #define TB_THREADS 256
+/* the constellations for the symbol store: copied into LDS by every workgroup of tb_tx_fused_sym_kernel */
+static __constant__ nr_qam_tables_t nr_qam_tab_tx = nr_qam_make_tables();
 
 /* XOR-reduce x over the workgroup; every thread gets the result.  red = 2 dwords of LDS. */
 __device__ __forceinline__ uint32_t tb_block_xor(uint32_t x, uint32_t *red)
@@ -379,8 +383,9 @@ __device__ __forceinline__ void tb_tx_store_scr(J j, const uint32_t *sel, uint32
 
 typedef uint32_t tb_u32x4_t __attribute__((ext_vector_type(4)));
 template <typename J> __device__ __forceinline__ uint32_t crc_len_of(J j) { return j->crc_len; }
-/* SCR: the packed, scrambled store (tb_tx_fused_scr_kernel) instead of the bit-per-byte one (tb_tx_fused_kernel) */
-template <bool SCR>
+/* SCR: the packed, scrambled store (tb_tx_fused_scr_kernel) instead of the bit-per-byte one (tb_tx_fused_kernel); SCR + SYM:
+ * the scrambled, mapped and layer-mapped points (tb_tx_fused_sym_kernel, tb_tx_sym.h) */
+template <bool SCR, bool SYM = false>
 __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch, uint8_t *coded,
                                                  const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets, uint32_t *parts)
 {
@@ -634,8 +639,34 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
       }
       sel[i * sel_stride + w] = v;
     }
+#ifndef TB_TX_SYM_TAB_CONST /* (defined: the A/B variant that looks the points up in constant memory) */
+    if constexpr (SYM) {
+      if (jj0 == 0) /* the constellation behind the sequence words, once (published by the barrier below) */
+        for (uint32_t x = tid; x < (1u << Qm); x += nt)
+          seq[TB_TX_SCR_WORDS + x] = nr_qam_tab_tx.pt[nr_qam_table_off(Qm) + x];
+    }
+#endif
     __syncthreads();
     TB_TLOG();
+    if constexpr (SYM) { /* one thread per symbol: plane s mod Nl, entry s div Nl of the TB's record */
+      const uint32_t b_lo = j->bit_off + jj0 * Qm;
+      const tb_tx_sym_chunk ch{sel, sel_stride, seq, b_lo & 31u, j->bit_off / Qm + jj0, j->Nl, j->plane};
+      uint32_t *out32 = reinterpret_cast<uint32_t *>(f);
+#ifdef TB_TX_SYM_TAB_CONST
+      const uint32_t *tab = nr_qam_tab_tx.pt + nr_qam_table_off(Qm);
+#else
+      const uint32_t *tab = seq + TB_TX_SCR_WORDS;
+#endif
+      switch (Qm) {
+        case 2: tb_tx_sym_store<2>(ch, tab, nsym, out32, tid, nt); break;
+        case 4: tb_tx_sym_store<4>(ch, tab, nsym, out32, tid, nt); break;
+        case 6: tb_tx_sym_store<6>(ch, tab, nsym, out32, tid, nt); break;
+        default: tb_tx_sym_store<8>(ch, tab, nsym, out32, tid, nt); break;
+      }
+      __syncthreads();
+      TB_TLOG();
+      continue;
+    }
     if constexpr (SCR) {
       const uint32_t b_lo = j->bit_off + jj0 * Qm, b_hi = b_lo + nsym * Qm, k = jj0 / TB_TX_SEL_SYMS;
       const bool last_chunk = jj0 + nsym == EQ;
@@ -685,6 +716,11 @@ __global__ void __launch_bounds__(512, 8) tb_tx_fused_scr_kernel(const tb_tx_seg
                                                               uint32_t *parts)
 {
   tb_tx_fused_body<true>(jobs, ejobs, scratch, coded, pow24b, acc, tickets, parts);
+}
+__global__ void __launch_bounds__(512, 8) tb_tx_fused_sym_kernel(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch,
+                                                              uint8_t *coded, const uint32_t *pow24b, uint32_t *acc)
+{
+  tb_tx_fused_body<true, true>(jobs, ejobs, scratch, coded, pow24b, acc, nullptr, nullptr);
 }
 
 /* ---- RX 1: de-interleave + rate de-match (HARQ combining) + decoder input pack --------------------------------
@@ -836,6 +872,14 @@ hipError_t tb_launch_tx_fused_scr(const tb_tx_seg_job *jobs, const ldpc_enc_job 
   if (n == 0)
     return hipSuccess;
   hipLaunchKernelGGL(tb_tx_fused_scr_kernel, dim3(n), dim3(n_threads), lds_bytes, s, jobs, ejobs, scratch, coded, pow24b, acc, tickets, parts);
+  return hipGetLastError();
+}
+hipError_t tb_launch_tx_fused_sym(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
+                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, hipStream_t s)
+{
+  if (n == 0)
+    return hipSuccess;
+  hipLaunchKernelGGL(tb_tx_fused_sym_kernel, dim3(n), dim3(n_threads), lds_bytes, s, jobs, ejobs, scratch, coded, pow24b, acc);
   return hipGetLastError();
 }
 hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,

@@ -52,6 +52,9 @@ struct tb_tx_seg_job {     /* one per code block */
   uint32_t c_init, bit_off;
   uint32_t h_ticket, h_part, h_part0, h_n;
   uint32_t t_ticket, t_part, t_part0, t_n;
+  /* symbol store (nrLDPC_hip_dlsch_encode_symbols) only: layers, and words from one layer plane of the TB's record to the next
+   * (S / Nl, S = G / Qm); out_off is the record's first byte, c_init / bit_off as above */
+  uint32_t Nl, plane;
 };
 struct tb_rx_seg_job {
   uint64_t llr_off;        /* int16 units: TB offset + sum of the previous segments' E */
@@ -88,6 +91,12 @@ struct tb_scr_tb_job {      /* scrambled encode: one per transport block (nr_lau
   uint32_t G, c_init;
 };
 
+struct tb_sym_tb_job {      /* symbol encode, three-kernel path: one per transport block (nr_launch_scramble_map_tb) */
+  uint64_t in_off;         /* scratch: the G coded bits, one per byte */
+  uint64_t out_off;        /* byte offset of the block's layer-mapped record (a multiple of 4) */
+  uint32_t G, c_init, Qm, Nl;
+};
+
 /* scrambled de-matching (tb_rx_core.h): sequence words staged in LDS behind a segment's image, and their bytes */
 #define TB_RX_SCR_WORDS 512u
 #define TB_RX_SCR_LDS (TB_RX_SCR_WORDS * 4u)
@@ -95,6 +104,8 @@ struct tb_scr_tb_job {      /* scrambled encode: one per transport block (nr_lau
  * anywhere in a word: 513 at most) and two carry words, behind the selection buffer (tb_chain.h TB_TX_FUSED_EXTRA_LDS) */
 #define TB_TX_SCR_WORDS 516u
 #define TB_TX_FUSED_SCR_LDS ((TB_TX_SCR_WORDS + 4u) * 4u)
+/* symbol store: the same sequence words, then the constellation (2^Qm points, 256 at most) in place of the carries */
+#define TB_TX_FUSED_SYM_LDS ((TB_TX_SCR_WORDS + 256u) * 4u)
 
 /* lds_elems = the largest tb_rx_lds_elems() over the jobs (int16 slots of LDS a workgroup needs) */
 TB_HD uint32_t tb_rx_lds_elems(uint32_t E, uint32_t Fin, uint32_t Ncb)

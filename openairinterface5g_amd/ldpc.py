@@ -441,6 +441,8 @@ def _tb_lib():
         L.nrLDPC_hip_ulsch_decode_scrambled.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
     if hasattr(L, "nrLDPC_hip_ulsch_decode_symbols"):
         L.nrLDPC_hip_ulsch_decode_symbols.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
+    if hasattr(L, "nrLDPC_hip_dlsch_encode_symbols"):
+        L.nrLDPC_hip_dlsch_encode_symbols.argtypes = [C.POINTER(nrLDPC_hip_tb_batch_t), C.POINTER(nrLDPC_hip_tb_scr_t)]
     L.nrLDPC_hip_segmentation.argtypes = [C.c_uint32, C.c_uint8] + [C.POINTER(C.c_uint32)] * 4
     L.nrLDPC_hip_segmentation.restype = C.c_int32
     L.nrLDPC_hip_get_E.argtypes = [C.c_uint32] * 5
@@ -707,6 +709,52 @@ def dlsch_encode_scrambled_device(tbs, payload, coded, scrambling, stream=None):
     _check(L.nrLDPC_hip_dlsch_encode_scrambled(C.byref(b), _scr_array(scrambling, len(tbs))), "nrLDPC_hip_dlsch_encode_scrambled")
 
 
+def tb_layout_symbols(tbs):
+    """Byte offsets of the TBs' layer-mapped points for nrLDPC_hip_dlsch_encode_symbols (4 G/Qm bytes each, 16-byte spacing)
+    and the bytes they span: (offsets, total)."""
+    co = np.cumsum([0] + [(4 * (t["G"] // t["Qm"]) + 15) // 16 * 16 for t in tbs])
+    return co[:-1], int(co[-1])
+
+
+def dlsch_encode_symbols_host(tbs, payloads, scrambling):
+    """dlsch_encode_scrambled_host through modulation and layer mapping (nrLDPC_hip_dlsch_encode_symbols).  Returns a list of
+    int16[Nl, G/(Qm Nl), 2]: TB i's layer planes, entry k of plane l = the point of codeword symbol k Nl + l."""
+    L = _tb_lib()
+    po = np.cumsum([0] + [(t["A"] // 8 + 15) // 16 * 16 for t in tbs])
+    co, total = tb_layout_symbols(tbs)
+    pay = np.zeros(int(po[-1]) + 16, np.uint8)
+    for i, p in enumerate(payloads):
+        pay[po[i]:po[i] + tbs[i]["A"] // 8] = np.asarray(p, np.uint8)[:tbs[i]["A"] // 8]
+    coded = np.zeros(total // 2 + 8, np.int16)
+    arr = _tb_array(tbs, po, co, None)
+    b = nrLDPC_hip_tb_batch_t(n_tb=len(tbs), tb=arr, payload=pay.ctypes.data, coded=coded.ctypes.data, harq=None,
+                              harq_stride=0, ack=None, iter_max=None, mem=MEM_HOST, stream=None)
+    _check(L.nrLDPC_hip_dlsch_encode_symbols(C.byref(b), _scr_array(scrambling, len(tbs))), "nrLDPC_hip_dlsch_encode_symbols")
+    out = []
+    for i, t in enumerate(tbs):
+        S = t["G"] // t["Qm"]
+        out.append(coded[co[i] // 2:co[i] // 2 + 2 * S].reshape(t["Nl"], S // t["Nl"], 2).copy())
+    return out
+
+
+def dlsch_encode_symbols_device(tbs, payload, coded, scrambling, stream=None, coded_off=None):
+    """payload: torch uint8 [>= tb_layout po[-1]] on the GPU, coded: torch tensor on the GPU of >= tb_layout_symbols total bytes
+    (out: TB i's layer planes at byte tb_layout_symbols offset i, or at coded_off[i]).  Asynchronous."""
+    import torch
+    L = _tb_lib()
+    po, _, _, _ = tb_layout(tbs)
+    co, total = tb_layout_symbols(tbs)
+    if coded_off is not None:
+        co = list(coded_off)
+        total = max(int(o) + 4 * (t["G"] // t["Qm"]) for o, t in zip(co, tbs))
+    assert payload.is_cuda and coded.is_cuda and payload.numel() >= po[-1] and coded.numel() * coded.element_size() >= total
+    arr = _tb_array(tbs, po, co, None)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    b = nrLDPC_hip_tb_batch_t(n_tb=len(tbs), tb=arr, payload=payload.data_ptr(), coded=coded.data_ptr(), harq=None,
+                              harq_stride=0, ack=None, iter_max=None, mem=MEM_DEVICE, stream=s)
+    _check(L.nrLDPC_hip_dlsch_encode_symbols(C.byref(b), _scr_array(scrambling, len(tbs))), "nrLDPC_hip_dlsch_encode_symbols")
+
+
 def dlsch_encode_device(tbs, payload, coded, stream=None):
     """payload: torch uint8 [>= tb_layout po[-1]] on the GPU, coded: torch uint8 [>= co[-1]] (out). Asynchronous."""
     import torch
@@ -740,7 +788,8 @@ class PreparedTbBatch:
     (harq None, harq_ids = one id per transport block).  scrambling = one (n_rnti, q, n_id) per transport block: the calls
     are nrLDPC_hip_dlsch_encode_scrambled / nrLDPC_hip_ulsch_decode_scrambled, and an encode's output follows
     tb_layout_packed.  symbols=True (with scrambling): coded_or_llr holds the TBs' symbol records (pack_symbol_records) and
-    decode() is nrLDPC_hip_ulsch_decode_symbols."""
+    decode() is nrLDPC_hip_ulsch_decode_symbols; encode() is nrLDPC_hip_dlsch_encode_symbols, its output following
+    tb_layout_symbols."""
 
     def __init__(self, tbs, payload, coded_or_llr, harq=None, ack=None, iter_max=None, numMaxIter=8, stream=None, mem=MEM_DEVICE,
                  harq_ids=None, scrambling=None, symbols=False):
@@ -760,7 +809,7 @@ class PreparedTbBatch:
             import torch
             s = torch.cuda.current_stream().cuda_stream if stream is None else stream
         if self.scr is not None:
-            self.arr_enc = _tb_array(tbs, po, self._coded_packed, None, numMaxIter)
+            self.arr_enc = _tb_array(tbs, po, tb_layout_symbols(tbs)[0] if self.sym else self._coded_packed, None, numMaxIter)
         self.batch = nrLDPC_hip_tb_batch_t(
             n_tb=len(tbs), tb=self.arr, payload=_ptr(payload), coded=_ptr(coded_or_llr),
             harq=_ptr(harq), harq_stride=0 if (harq is None and harq_ids is None) else HARQ_STRIDE,
@@ -770,10 +819,14 @@ class PreparedTbBatch:
         if self.scr is None:
             _check(self._lib.nrLDPC_hip_dlsch_encode(C.byref(self.batch)), "nrLDPC_hip_dlsch_encode")
         else:
-            if not hasattr(self, "batch_enc"):   # (the packed layout's coded offsets)
+            if not hasattr(self, "batch_enc"):   # (the packed / symbol layout's coded offsets)
                 self.batch_enc = nrLDPC_hip_tb_batch_t.from_buffer_copy(self.batch)
                 self.batch_enc.tb = self.arr_enc
-            _check(self._lib.nrLDPC_hip_dlsch_encode_scrambled(C.byref(self.batch_enc), self.scr), "nrLDPC_hip_dlsch_encode_scrambled")
+            if self.sym:
+                _check(self._lib.nrLDPC_hip_dlsch_encode_symbols(C.byref(self.batch_enc), self.scr), "nrLDPC_hip_dlsch_encode_symbols")
+            else:
+                _check(self._lib.nrLDPC_hip_dlsch_encode_scrambled(C.byref(self.batch_enc), self.scr),
+                       "nrLDPC_hip_dlsch_encode_scrambled")
 
     def decode(self):
         _decode_call(self._lib, self.batch, self.scr, self.sym)
@@ -919,6 +972,9 @@ def _qam_lib():
     L.nrLDPC_hip_modulation.restype = C.c_int32
     L.nrLDPC_hip_ulsch_llr.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_uint8, C.c_void_p, C.c_int32, C.c_void_p]
     L.nrLDPC_hip_ulsch_llr.restype = C.c_int32
+    if hasattr(L, "nrLDPC_hip_layer_mapping"):
+        L.nrLDPC_hip_layer_mapping.argtypes = [C.c_void_p, C.c_uint32, C.c_uint8, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
+        L.nrLDPC_hip_layer_mapping.restype = C.c_int32
     return L
 
 
@@ -1001,4 +1057,32 @@ def pack_symbol_records(blocks):
         if any(p.size != ps[0].size for p in ps):
             raise ValueError("every plane of a record has S c16 values")
         out.append(np.concatenate(ps).astype(np.int16, copy=False))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Layer mapping and the DL-SCH chain call to symbols (include/nrLDPC_hip.h: nrLDPC_hip_layer_mapping / _dlsch_encode_symbols)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_layer_mapping", "nrLDPC_hip_dlsch_encode_symbols"]
+
+
+def layer_mapping(x, Nl, out=None, layer_stride=None, n_symbs=None, stream=None):
+    """nr_layer_mapping for one codeword: the first n_symbs (all by default) c16 points of x (int16 [n, 2] / [2n] or int32 [n])
+    -> Nl planes, out[l layer_stride + i] = x[Nl i + l] in c16 units (layer_stride = n_symbs / Nl by default).  numpy -> host
+    call, returns int16[Nl, layer_stride, 2] (zeros between the planes); torch CUDA tensor -> device call enqueued on `stream`
+    into `out`, a contiguous torch CUDA tensor on the same GPU of at least 4 ((Nl - 1) layer_stride + n_symbs / Nl) bytes;
+    returns `out`."""
+    L = _qam_lib()
+    n = _c16_count(x) if n_symbs is None else int(n_symbs)
+    stride = n // Nl if (layer_stride is None and Nl) else (layer_stride or 0)
+    if isinstance(x, np.ndarray):
+        src = np.ascontiguousarray(x)
+        res = np.zeros((max(Nl, 1), max(stride, 1), 2), np.int16)
+        _check(L.nrLDPC_hip_layer_mapping(src.ctypes.data, n, Nl, res.ctypes.data, stride, MEM_HOST, None), "nrLDPC_hip_layer_mapping")
+        return res[:, :stride]
+    import torch
+    assert x.is_cuda and x.is_contiguous() and out is not None and out.is_cuda and out.is_contiguous() and out.device == x.device
+    assert out.numel() * out.element_size() >= 4 * ((Nl - 1) * stride + n // Nl)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_layer_mapping(x.data_ptr(), n, Nl, out.data_ptr(), stride, MEM_DEVICE, s), "nrLDPC_hip_layer_mapping")
     return out
