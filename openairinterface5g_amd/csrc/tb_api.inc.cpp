@@ -774,8 +774,11 @@ struct HarqTable {
 } harq_tbl;
 
 /* the soft buffers of block `id` on the current device, n int16; `fresh`: the call clears them before use (first
- * transmission).  A block that arrives with round > 0 and no history combines with zeros; one whose buffers live on another
- * GPU (the partition moved it) takes its history along.  Stream-ordered on s. */
+ * transmission).  An id that already holds large enough buffers here keeps them as they are (an OAI HARQ process keeps its
+ * d[r]).  Any other buffer -- a new allocation, one recycled from a released id, a regrow, a move to another GPU -- is handed
+ * over reading zero wherever this id has written nothing (nrLDPC_hip_harq_read): a block that arrives with
+ * round > 0 and no history combines with zeros; one whose buffers live on another GPU (the partition moved it), or that
+ * regrows, takes its history along.  Stream-ordered on s. */
 int16_t *harq_lookup(uint64_t id, size_t n, bool fresh, hipStream_t s)
 {
   const int di = cur_dev_index();
@@ -790,32 +793,24 @@ int16_t *harq_lookup(uint64_t id, size_t n, bool fresh, hipStream_t s)
       harq_tbl.pool.erase(harq_tbl.pool.begin() + (long)k);
       break;
     }
-  const bool new_mem = !e.p;
   if (!e.p && hipMalloc(reinterpret_cast<void **>(&e.p), n * sizeof(int16_t)) != hipSuccess) {
     set_error("soft buffer allocation");
     return nullptr;
   }
-  /* new memory holds whatever an earlier allocation of the process left there: zeroed, so that what a first transmission
-   * never touches (a row behind its Ncb values) reads the same for every new id (nrLDPC_hip_harq_read) */
-  hipError_t err = (new_mem && fresh) ? hipMemsetAsync(e.p, 0, n * sizeof(int16_t), s) : hipSuccess;
-  if (err == hipSuccess && it != harq_tbl.m.end()) {
-    if (!fresh) {
-      const size_t keep = std::min(n, it->second.n);
-      err = hipMemcpyAsync(e.p, it->second.p, keep * sizeof(int16_t), hipMemcpyDefault, s);
-      if (err == hipSuccess && keep < n)
-        err = hipMemsetAsync(e.p + keep, 0, (n - keep) * sizeof(int16_t), s);
-      if (err == hipSuccess)
-        err = hipStreamSynchronize(s); /* the old buffers go back to the pool below */
-    }
-    harq_tbl.pool.push_back(it->second);
-  } else if (err == hipSuccess && !fresh) {
-    err = hipMemsetAsync(e.p, 0, n * sizeof(int16_t), s);
-  }
+  /* e.n int16 (a pooled buffer may be larger than n): the id's history in front, zeros behind */
+  const size_t keep = (it != harq_tbl.m.end() && !fresh) ? std::min(e.n, it->second.n) : 0;
+  hipError_t err = keep ? hipMemcpyAsync(e.p, it->second.p, keep * sizeof(int16_t), hipMemcpyDefault, s) : hipSuccess;
+  if (err == hipSuccess)
+    err = hipMemsetAsync(e.p + keep, 0, (e.n - keep) * sizeof(int16_t), s);
+  if (err == hipSuccess && keep)
+    err = hipStreamSynchronize(s); /* the old buffers go back to the pool below */
   if (err != hipSuccess) {
     harq_tbl.pool.push_back(e);
     set_error("soft buffer set-up", err);
     return nullptr;
   }
+  if (it != harq_tbl.m.end())
+    harq_tbl.pool.push_back(it->second);
   harq_tbl.m[id] = e;
   harq_tbl.gen.fetch_add(1);
   return e.p;
@@ -989,6 +984,9 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         nr_hip_rm_t rm;
         if (nr_hip_rate_match_geometry(t.tbslbrm, t.BG, sg.Zc, sg.C, sg.F, sg.K, t.rv, E, &rm) != 0)
           return set_error("nr_rate_matching_rx: invalid parameters");
+        /* the positions the round's rate mode reads, uncut: a first round clears [0, max(Ncb, np_mode)) of the soft buffer on
+         * every path, so that a retransmission decoded on the whole mode finds zeros behind Ncb whether or not this round was cut */
+        const uint32_t np_mode = (uint32_t)ce->host.num_llr - 2 * sg.Zc;
         if (tb_trunc_enabled() && t.round == 0) {
           /* A first transmission leaves every soft-buffer position behind the last one it reaches at 0 (the buffer is cleared,
            * nr_ulsch_decoding.c:418-422), and with them whole degree-1 columns at the end of the rate mode's graph -- at MCS 27 eight
@@ -1014,7 +1012,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         j.l_off = ar.take(hc.num_llr);
         j.E = E; j.Qm = t.Qm; j.Ncb = rm.Ncb; j.Foffset = rm.Foffset; j.Fin = rm.Fin; j.V = rm.V; j.rank0 = rm.rank0;
         j.clear = t.round == 0; /* harq_to_be_cleared -> d_to_be_cleared[r] (nr_ulsch_decoding.c:418-422) */
-        j.K = sg.K; j.F = sg.F; j.Z = sg.Zc; j.num_llr = (uint32_t)hc.num_llr;
+        j.K = sg.K; j.F = sg.F; j.Z = sg.Zc; j.num_llr = (uint32_t)hc.num_llr; j.np_mode = np_mode;
         j.c_off = tj.c_off0 + (uint64_t)r * cstride;
         if (scr) {
           j.c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
@@ -1026,9 +1024,8 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         if (!fused_tb)
           rx_lds_elems = std::max(rx_lds_elems, lds_elems);
         j.tb = i; j.r = r; j.iter_idx = (uint32_t)sj.size();
-        if (harq_staged) { /* rows of the caller's array that travel: what the kernels look at of this segment's row */
-          const uint32_t np = (uint32_t)hc.num_llr > 2 * sg.Zc ? (uint32_t)hc.num_llr - 2 * sg.Zc : 0u;
-          const uint32_t width = std::min<uint32_t>(std::max(rm.Ncb, np), b->harq_stride);
+        if (harq_staged) { /* rows of the caller's array that travel: what the kernels look at of this segment's row (tb_rx_geometry) */
+          const uint32_t width = std::min<uint32_t>(std::max(rm.Ncb, np_mode), b->harq_stride);
           const size_t first = (size_t)t.harq_off + (size_t)r * b->harq_stride;
           if (!runs.empty() && runs.back().width == width && runs.back().upload == (t.round != 0) &&
               runs.back().first + (size_t)runs.back().rows * b->harq_stride == first)

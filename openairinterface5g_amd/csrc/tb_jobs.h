@@ -65,7 +65,9 @@ struct tb_rx_seg_job {
   /* reassembly (tb_rx_assemble_kernel): */
   uint64_t c_off;          /* scratch: this segment's decoded bits */
   uint32_t tb, r;          /* transport block (index into the per-TB jobs) and segment number */
-  uint32_t iter_idx, pad;  /* where the decoder reported this segment's pass count */
+  uint32_t iter_idx;       /* where the decoder reported this segment's pass count */
+  uint32_t np_mode;        /* soft-buffer positions the round's rate mode reads UNCUT (ncols(R)*Z - 2Z): a first round clears
+                              [0, max(Ncb, np_mode)) whatever graph the decoder runs on; 0: num_llr's */
   /* scrambled calls (nrLDPC_hip_ulsch_decode_scrambled) only -- the kernels' unscrambled instantiations never read these: */
   uint32_t c_init;         /* the transport block's sequence (38.211 6.3.1.1) */
   uint32_t bit_off;        /* codeword bit of the segment's first LLR = sum of the previous segments' E */

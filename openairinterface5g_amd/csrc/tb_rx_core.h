@@ -80,8 +80,8 @@ template <int QM> TB_RX_HD void tb_rx_src_load(const tb_rx_sym_src &s, bool, uin
 struct tb_rx_geom {
   uint32_t E, Ncb, Foffset, Fin, V, rank0, clear;
   uint32_t twoZ, num_llr, Klo, Khi;
-  uint32_t np;      /* soft-buffer positions the decoder reads */
-  uint32_t n;       /* positions this call looks at: max(Ncb, np) */
+  uint32_t np;      /* soft-buffer positions the decoder reads (of the cut graph, on a first transmission) */
+  uint32_t n;       /* positions this call looks at: max(Ncb, np, np_mode) -- a first round clears all of them */
   uint32_t p_align; /* first position of the LDS image (multiple of 8) */
   uint32_t span;    /* LDS slots in use, a multiple of 8 */
 };
@@ -92,6 +92,7 @@ template <class JobPtr> TB_RX_HD tb_rx_geom tb_rx_geometry(JobPtr j)
   g.twoZ = 2 * j->Z; g.num_llr = j->num_llr; g.Klo = j->K - j->F; g.Khi = j->K;
   g.np = g.num_llr > g.twoZ ? g.num_llr - g.twoZ : 0;
   g.n = g.Ncb > g.np ? g.Ncb : g.np;
+  g.n = g.n > j->np_mode ? g.n : j->np_mode;
   const uint32_t p_base = g.rank0 < g.Foffset ? g.rank0 : g.rank0 + g.Fin;
   g.p_align = p_base & ~7u;
   g.span = tb_rx_lds_elems(g.E, g.Fin, g.Ncb);

@@ -410,8 +410,11 @@ template <int QM> static void emul_scatter(const tb_rx_geom &g, const int16_t *f
       tb_rx_phase_scatter_lap<QM>(g, f, e_lds, lap, nlaps, (uint32_t)tid, (uint32_t)nt, first[tid]);
 }
 
-extern "C" int tb_emul_rx_dematch(uint32_t Tbslbrm, int BG, uint32_t Zc, uint32_t C, uint32_t F, uint32_t K, int rv, uint32_t E, uint32_t Qm,
-                                  uint32_t num_llr, int clear, int nt, const int16_t *f, int16_t *w, int8_t *l)
+/* num_llr: the int8 decoder input the segment's graph reads (cut, on a first transmission: tb_api.inc.cpp); np_mode: the soft-
+ * buffer positions the round's rate mode reads uncut (tb_rx_seg_job::np_mode) */
+extern "C" int tb_emul_rx_dematch_cut(uint32_t Tbslbrm, int BG, uint32_t Zc, uint32_t C, uint32_t F, uint32_t K, int rv, uint32_t E,
+                                      uint32_t Qm, uint32_t num_llr, uint32_t np_mode, int clear, int nt, const int16_t *f, int16_t *w,
+                                      int8_t *l)
 {
   nr_hip_rm_t rm;
   if (nr_hip_rate_match_geometry(Tbslbrm, BG, Zc, C, F, K, rv, E, &rm) != 0)
@@ -420,7 +423,7 @@ extern "C" int tb_emul_rx_dematch(uint32_t Tbslbrm, int BG, uint32_t Zc, uint32_
   memset(&j, 0, sizeof(j));
   j.E = E; j.Qm = Qm; j.Ncb = rm.Ncb; j.Foffset = rm.Foffset; j.Fin = rm.Fin; j.V = rm.V; j.rank0 = rm.rank0;
   j.clear = clear ? 1u : 0u;
-  j.K = K; j.F = F; j.Z = Zc; j.num_llr = num_llr;
+  j.K = K; j.F = F; j.Z = Zc; j.num_llr = num_llr; j.np_mode = np_mode;
   const tb_rx_geom g = tb_rx_geometry(&j);
   std::vector<tb_u32x4> lds(g.span / 8 + 1);
   memset(lds.data(), 0x5a, lds.size() * sizeof(tb_u32x4)); /* poison: phase Z must initialise what is read */
@@ -434,4 +437,20 @@ extern "C" int tb_emul_rx_dematch(uint32_t Tbslbrm, int BG, uint32_t Zc, uint32_
   for (int tid = 0; tid < nt; tid++)
     tb_rx_phase_stream(g, e_lds, w, l, (uint32_t)tid, (uint32_t)nt);
   return (int)g.span;
+}
+
+/* the whole rate mode: num_llr = ncols(R) * Zc */
+extern "C" int tb_emul_rx_dematch(uint32_t Tbslbrm, int BG, uint32_t Zc, uint32_t C, uint32_t F, uint32_t K, int rv, uint32_t E, uint32_t Qm,
+                                  uint32_t num_llr, int clear, int nt, const int16_t *f, int16_t *w, int8_t *l)
+{
+  return tb_emul_rx_dematch_cut(Tbslbrm, BG, Zc, C, F, K, rv, E, Qm, num_llr, num_llr - 2 * Zc, clear, nt, f, w, l);
+}
+
+/* columns a first transmission reaches (nr_coding_host.c), -1 on invalid parameters */
+extern "C" int tb_emul_first_tx_columns(uint32_t Tbslbrm, int BG, uint32_t Zc, uint32_t C, uint32_t F, uint32_t K, int rv, uint32_t E)
+{
+  nr_hip_rm_t rm;
+  if (nr_hip_rate_match_geometry(Tbslbrm, BG, Zc, C, F, K, rv, E, &rm) != 0)
+    return -1;
+  return (int)nr_hip_first_tx_columns(&rm, E, Zc);
 }

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import softbuf_np as SB
 from common import ALL_RATES, kbits, load_survey_decoder_vectors, make_llr, random_info
 
 
@@ -136,10 +137,11 @@ def test_rx_dematch_phases_against_the_oracle(emul):
                     for clear, misalign in ((1, 0), (0, 0), (0, 1)):
                         w0 = rng.integers(-2000, 2000, 66 * 384 + 16).astype(np.int16)
                         Ncb = N if not lbrm else min(N, (3 * lbrm // (2 * Cn)))
-                        w0[misalign + Ncb:misalign + N] = 0      # the reference's d[r] is calloc'ed and never written behind Ncb
-                        # oracle: the reference's three steps
+                        # oracle: the reference's three steps, on a buffer dirty behind Ncb too (R0 on round 0: DESIGN 5)
                         e = O.deinterleave(E, Qm, f)
                         d_ref = w0[misalign:misalign + N].copy()
+                        if clear:
+                            SB.clear_segment(d_ref, Ncb, BG, Z, R)
                         rc, d_ref = O.rate_match_rx(lbrm, BG, Z, d_ref, e, Cn, rv, clear, E, F, K - F - 2 * Z)
                         assert rc == 0
                         l_ref = O.llr_prepack(d_ref, BG, Z, K, F, ncols)
@@ -156,3 +158,60 @@ def test_rx_dematch_phases_against_the_oracle(emul):
                         assert (l[ncols * Z:] == 0x11).all()
                         cases += 1
     assert cases > 1000
+
+
+def test_rx_dematch_first_round_clear_does_not_follow_the_cut(emul):
+    """A first transmission is decoded on the rate mode's graph cut behind the last column it reaches (tb_api.inc.cpp), but its
+    soft buffer is cleared over [0, max(Ncb, np(R))) of the UNCUT mode R (rule R0): with limited-buffer rate matching
+    np(R) - Ncb is thousands of positions the retransmissions read on the whole mode.  The workgroup's phases with the cut
+    num_llr and the mode's extent given separately, on soft buffers dirty everywhere: w[0:N] equals the oracle with R0
+    applied, nothing behind N is touched, and the decoder input over the cut columns equals the oracle's pack of them.
+    Both base graphs, LBRM on and off, every Qm, rv 0-3, repetition; round 0 and a combining round."""
+    emul.tb_emul_rx_dematch_cut.argtypes = ([C.c_uint32, C.c_int] + [C.c_uint32] * 4 + [C.c_int] + [C.c_uint32] * 4 +
+                                            [C.c_int, C.c_int] + [C.c_void_p] * 3)
+    emul.tb_emul_first_tx_columns.argtypes = [C.c_uint32, C.c_int] + [C.c_uint32] * 4 + [C.c_int, C.c_uint32]
+    rng = np.random.default_rng(1717)
+    cases = cut = beyond = 0
+    for BG, A, lbrm in ((1, 30000, 0), (1, 30000, 24000), (1, 9608, 9000), (2, 5000, 6000), (2, 3000, 0), (1, 100000, 150000)):
+        s = O.segmentation(None, O.len_with_crc(1, A), BG)
+        Z, K, F, Cn = s["Z"], s["K"], s["F"], s["C"]
+        N = (66 if BG == 1 else 50) * Z
+        Ncb = N if not lbrm else min(N, (3 * lbrm // (2 * Cn)))
+        ncore = 26 if BG == 1 else 14
+        for Qm in (2, 4, 6, 8):
+            for rv in range(4):
+                for rate in (0.25, 0.6, 0.92, 0.08):                # 0.08: E > Ncb, several laps
+                    E = max(Qm * 4, int((K - F) / rate) // Qm * Qm)
+                    R, _ = O.get_R(rv, E, BG, Z, 0, 0)
+                    ncols = O.NCOLS[(BG, R)]
+                    reach = emul.tb_emul_first_tx_columns(lbrm, BG, Z, Cn, F, K, rv, E)
+                    assert reach > 0
+                    ncut = min(ncols, max(reach, ncore + 1))          # the decoder's graph (nrLDPC_hip_ulsch_decoder_columns)
+                    np_mode = ncols * Z - 2 * Z
+                    f = rng.integers(-300, 300, E).astype(np.int16)
+                    e = O.deinterleave(E, Qm, f)
+                    for clear in (1, 0):
+                        nc = ncut if clear else ncols                 # a retransmission is never cut
+                        w0 = rng.integers(-2000, 2000, 66 * 384 + 16).astype(np.int16)
+                        d_ref = w0[:N].copy()
+                        if clear:
+                            SB.clear_segment(d_ref, Ncb, BG, Z, R)
+                        rc, d_ref = O.rate_match_rx(lbrm, BG, Z, d_ref, e, Cn, rv, clear, E, F, K - F - 2 * Z)
+                        assert rc == 0
+                        l_ref = O.llr_prepack(d_ref, BG, Z, K, F, nc)
+                        w = w0.copy()
+                        l = np.full(ncols * Z + 8, 0x11, np.int8)
+                        span = emul.tb_emul_rx_dematch_cut(lbrm, BG, Z, Cn, F, K, rv, E, Qm, nc * Z, np_mode, clear, 256,
+                                                           f.ctypes.data, w.ctypes.data, l.ctypes.data)
+                        assert span > 0
+                        key = (BG, A, lbrm, Qm, rv, rate, clear, nc, ncols)
+                        bad = np.flatnonzero(w[:N] != d_ref)
+                        assert bad.size == 0, key + (bad[:4].tolist(), Ncb, np_mode)
+                        assert np.array_equal(w[N:], w0[N:]), key          # nothing behind the row's N positions
+                        assert np.array_equal(l[:nc * Z], l_ref), key
+                        assert (l[nc * Z:] == 0x11).all(), key              # nothing behind the cut graph's input
+                        cases += 1
+                        cut += clear and nc < ncols
+                        beyond += clear and max(Ncb, nc * Z - 2 * Z) < np_mode
+    assert cases > 700 and cut > 50 and beyond > 50, (cases, cut, beyond)
+

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import softbuf_np as SB
 from test_gpu_tb_chain import make_tbs, valid_tbs
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +23,8 @@ def _noisy(rng, f, sigma):
 def test_host_llrs_with_device_resident_harq(hip, where, pinned):
     """Two HARQ rounds (rv 0 at a noise level where several blocks fail, then rv 2) and a fresh first transmission on the
     same buffers: LLRs, payloads and verdicts in host memory (page-locked: pulled by the segments' workgroups in place;
-    pageable: staged copy), soft buffers never leaving the GPU.  Soft values are read back after every call and compared
-    value for value with the oracle chain's."""
+    pageable: staged copy), soft buffers never leaving the GPU.  Soft values of whole rows are read back after every call and
+    compared value for value with the oracle chain's, R0 applied on round 0 (tests/softbuf_np.py)."""
     import torch
     m = hip.ldpc
     rng = np.random.default_rng(11)
@@ -56,6 +57,8 @@ def test_host_llrs_with_device_resident_harq(hip, where, pinned):
         out, ack, itm = m.ulsch_decode_host(tbs, llrs, harq_dev, numMaxIter=8, pinned=pinned,
                                             harq_ids=ids if where == "library" else None)
         for i, t in enumerate(tbs):
+            if rnd == 0:                                             # R0: the clear reaches np(R0)
+                SB.clear_first_round(t, harq_ref[i], 0)
             p_ref, ack_ref, its, state_ref[i] = O.ulsch_decode(t, llrs[i], harq_ref[i], 8, rnd, state_ref[i])
             assert bool(ack[i]) == ack_ref and itm[i] == max(its), (step, t, its, int(itm[i]))
             assert t["llrLen"] == state_ref[i]
@@ -63,12 +66,9 @@ def test_host_llrs_with_device_resident_harq(hip, where, pinned):
                 assert np.array_equal(out[i], p_ref) and np.array_equal(out[i], pays[i])
             else:
                 assert not out[i].any()                              # a lost block delivers zeros
-            sg = O.segmentation(None, O.len_with_crc(1, t["A"]), t["BG"])
-            N = (66 if t["BG"] == 1 else 50) * sg["Z"]
-            ncb = N if not t["tbslbrm"] else min(N, 3 * t["tbslbrm"] // (2 * sg["C"]))    # nr_rate_matching.c:445-450
             for r in range(segs[i]):
                 got, ref = soft(i, r), harq_ref[i][r]
-                assert np.array_equal(got[:ncb], ref[:ncb]), (step, i, r)
+                assert np.array_equal(got, ref), (step, i, r)                  # the whole row
         acks.append(ack.copy())
     assert not acks[0].all() and acks[1].sum() > acks[0].sum() and acks[2].all()      # combining recovers blocks
     if where == "library":
@@ -148,10 +148,14 @@ def test_fused_segment_kernel_against_the_four_launch_path(hip):
 
 def test_first_transmissions_never_upload_host_soft_buffers(hip):
     """Host-resident soft buffers (the legacy layout): a call whose blocks are all first transmissions uploads nothing of
-    them -- they are cleared on the device -- and brings back max(Ncb, positions the decoder reads) values per segment: the
-    Ncb soft values it produced and, with limited-buffer rate matching (Ncb < N), ZEROS in [Ncb, np) -- the reference memsets
-    Ncb entries only (nr_rate_matching.c:554-555) and its decoder input reads what its calloc'ed buffer holds behind them,
-    which is zero as well.  What lies behind the circular buffer's N positions is never touched."""
+    them -- they are cleared on the device -- and brings back max(Ncb, np(R0)) values per segment:
+      R0  the Ncb soft values it produced and, with limited-buffer rate matching (Ncb < N), ZEROS in exactly [Ncb, np(R0)),
+          R0 the round's rate mode UNCUT -- also where the decoder runs on a graph cut behind the last column the
+          transmission reaches -- so that a retransmission decoded on the whole mode reads zeros there (the reference
+          memsets Ncb entries only, nr_rate_matching.c:554-555, and leaves the rest as its caller's buffer holds it);
+          everything behind max(Ncb, np(R0)) is exactly as the caller left it;
+      R1  later rounds use the rows as they are, stale values beyond Ncb included (test_gpu_tb_softbuf.py);
+      L   library-kept buffers an id did not hold before read zero wherever a call does not write (test_gpu_tb_softbuf.py)."""
     m = hip.ldpc
     rng = np.random.default_rng(5)
     tbs = [dict(t, rv=0) for t in make_tbs() if t["tbslbrm"]] + make_tbs()[:3]
@@ -165,20 +169,18 @@ def test_first_transmissions_never_upload_host_soft_buffers(hip):
         t["round"] = 0
     out, ack, itm = m.ulsch_decode_host(tbs, llrs, harq, numMaxIter=8)
     assert ack.all()
-    row = 0
+    row = n_zero = 0
     for i, t in enumerate(tbs):
         href = [before[row + r].copy() for r in range(segs[i])]
         O.ulsch_decode(t, llrs[i], href, 8, 0, 0)
-        s = O.segmentation(None, O.len_with_crc(1, t["A"]), t["BG"])
-        N = (66 if t["BG"] == 1 else 50) * s["Z"]
-        ncb = N if not t["tbslbrm"] else min(N, 3 * t["tbslbrm"] // (2 * s["C"]))
-        for r in range(segs[i]):
+        for r, (ncb, np0) in enumerate(SB.first_round_extents(t)[0]):
+            hi = max(ncb, np0)
             assert np.array_equal(harq[row + r, :ncb], href[r][:ncb]), (i, r)
-            tail = harq[row + r, ncb:N]                                                # [Ncb, N): zeros up to the decoder's reach, else untouched
-            nz = int(np.argmax(tail != 0)) if (tail != 0).any() else tail.size
-            assert not tail[:nz].any() and np.array_equal(tail[nz:], before[row + r, ncb + nz:N]), (i, r)
-            assert np.array_equal(harq[row + r, N:], before[row + r, N:]), (i, r)       # behind the circular buffer: never touched
+            assert not harq[row + r, ncb:hi].any(), (i, r, ncb, np0)                   # [Ncb, np(R0)): zeros
+            assert np.array_equal(harq[row + r, hi:], before[row + r, hi:]), (i, r)   # behind: never touched
+            n_zero += hi > ncb
         row += segs[i]
+    assert n_zero >= 4
 
 
 def test_device_resident_batches_sharded_over_logical_devices(hip, tmp_path):
