@@ -27,6 +27,7 @@
 #include "nr_coding_host.h"
 #include "nr_gold.h"
 #include "tb_chain.h"
+#include "tb_tx_scr.h"
 #include "ldpc_enc_packed_core.h"
 
 namespace {

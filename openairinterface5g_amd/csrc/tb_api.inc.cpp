@@ -590,32 +590,10 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         e.code = ce_seg->dev; e.in_off = j.c_off; e.out_off = j.d_off; e.Kb = (int32_t)sg.Kb; e.pad = 0;
         ej.push_back(e);
       }
-      if (scr && fused && !sym) { /* (a segment's points are its own: nr_hip_get_E gives every segment whole layer groups) */
-        /* words the block's segments share (tb_tx_settle_word): a segment's first word when it starts inside a word, its last
-         * word when it ends inside one and is not the block's last segment (behind G the last word is 0: complete) -- once
-         * per segment and word; each word gets a ticket and one part slot per segment that touches it */
-        std::map<uint32_t, std::vector<std::pair<size_t, int>>> shared;
-        for (size_t q = seg_first; q < sj.size(); q++) {
-          const uint32_t lo = sj[q].bit_off, hi = lo + sj[q].E;
-          const bool head = (lo & 31u) != 0, last = sj[q].r + 1 == sj[q].C;
-          if (head)
-            shared[lo >> 5].push_back({q, 0});
-          if (!last && (hi & 31u) && !(head && ((hi - 1) >> 5) == (lo >> 5)))
-            shared[(hi - 1) >> 5].push_back({q, 1});
-        }
-        for (const auto &kv : shared) {
-          const uint32_t tk = n_tickets++, p0 = (uint32_t)n_parts, n = (uint32_t)kv.second.size();
-          for (uint32_t k = 0; k < n; k++) {
-            tb_tx_seg_job &q = sj[kv.second[k].first];
-            if (kv.second[k].second == 0) {
-              q.h_ticket = tk; q.h_part = p0 + k; q.h_part0 = p0; q.h_n = n;
-            } else {
-              q.t_ticket = tk; q.t_part = p0 + k; q.t_part0 = p0; q.t_n = n;
-            }
-          }
-          n_parts += n;
-        }
-      }
+      /* the words the block's segments share (tb_tx_settle_word), their tickets and part slots.  (Symbol store: a segment's
+       * points are its own: nr_hip_get_E gives every segment whole layer groups) */
+      if (scr && fused && !sym)
+        tb_tx_scr_plan(&sj[seg_first], sj.size() - seg_first, &n_tickets, &n_parts);
     }
     const size_t n_seg = sj.size();
     const size_t o_tb = 0, o_seg = align_up(tbj.size() * sizeof(tb_tx_tb_job), 16),

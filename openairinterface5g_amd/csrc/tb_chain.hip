@@ -27,6 +27,7 @@
 #endif
 #include "tb_rx_core.h"
 #include "tb_tx_sym.h"
+#include "tb_tx_scr.h"
 #include "nr_qam.h"
 
 #define TB_THREADS 256
@@ -323,67 +324,9 @@ __device__ __forceinline__ void tb_tx_store_syms(const uint32_t *sel, uint32_t s
   }
 }
 
-/* A packed word that several segments' bits share (segment boundaries are not word boundaries): each segment leaves its part
- * in its slot and takes a ticket; the last to arrive ORs the parts, stores the word and resets the ticket.  No workgroup
- * waits for another, and nobody read-modify-writes the caller's array.  No fences, as in the fused RX kernel
- * (tb_rx_fused.hip): the part is a device-scope atomic store that has completed (vmcnt) before the ticket is taken, and the
- * last arrival reads the parts with device-scope atomic loads -- an agent-scope release would write back the XCD's whole L2
- * for every boundary word (the first version did: 81 us for the slot's 1664 segments against 20 unscrambled). */
-__device__ __forceinline__ void tb_tx_settle_word(uint32_t *dst, uint32_t bits, uint32_t ticket, uint32_t part, uint32_t part0, uint32_t n,
-                                                  uint32_t *tickets, uint32_t *parts)
-{
-  __hip_atomic_store(&parts[part], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const uint32_t before = __hip_atomic_fetch_add(&tickets[ticket], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (before + 1u != n)
-    return;
-  uint32_t v = 0;
-  for (uint32_t k = 0; k < n; k++)
-    v |= __hip_atomic_load(&parts[part0 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  *dst = v;
-  __hip_atomic_store(&tickets[ticket], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); /* zero again for the next call */
-}
-/* Packed, scrambled output of one selection chunk (the scrambled instantiation of tb_tx_fused_kernel, beside
- * tb_tx_store_syms): codeword bits [b_lo, b_hi) of the TB = f[jj0 Qm ..] of the segment.  A thread forms whole 32-bit words
- * of interleaved bits from the Qm sub-streams in LDS, XORs the sequence words (seq[0] = word b_lo / 32) over the bits this
- * chunk holds, and stores a dword.  A word the chunk shares with the previous chunk takes that chunk's part from carry[];
- * one it shares with the next chunk leaves its part there; one it shares with another segment goes through a ticket.  The
- * bits behind G in the TB's last word are 0. */
-template <int QM, typename J>
-__device__ __forceinline__ void tb_tx_store_scr(J j, const uint32_t *sel, uint32_t sel_stride, const uint32_t *seq, uint32_t *carry, uint32_t k,
-                                                uint32_t b_lo, uint32_t b_hi, bool last_chunk, uint32_t *out32, uint32_t *tickets,
-                                                uint32_t *parts, int tid, int nt)
-{
-  const bool first_chunk = k == 0, last_seg = j->r + 1u == j->C;
-  const uint32_t w_lo = b_lo >> 5, w_hi = (b_hi + 31u) >> 5, lo = j->bit_off;
-  for (uint32_t w = w_lo + (uint32_t)tid; w < w_hi; w += (uint32_t)nt) {
-    const uint32_t n0 = 32u * w > b_lo ? 32u * w : b_lo, n1 = 32u * w + 32u < b_hi ? 32u * w + 32u : b_hi;
-    uint32_t bits = 0;
-    for (uint32_t n = n0; n < n1; n++) {
-      const uint32_t mc = n - b_lo, sy = mc / (uint32_t)QM, i = mc - sy * (uint32_t)QM;
-      bits |= ((sel[i * sel_stride + (sy >> 5)] >> (sy & 31u)) & 1u) << (n & 31u);
-    }
-    const uint32_t nb = n1 - n0, present = nb == 32u ? ~0u : ((1u << nb) - 1u) << (n0 & 31u);
-    bits ^= seq[w - w_lo] & present;
-    const bool before = 32u * w < b_lo, after = 32u * w + 32u > b_hi && !(last_chunk && last_seg);
-    if (before && !first_chunk)
-      bits |= carry[(k - 1u) & 1u];
-    if (after && !last_chunk) {
-      carry[k & 1u] = bits;
-    } else if ((before && first_chunk) || after) {
-      if (w == (lo >> 5) && (lo & 31u))
-        tb_tx_settle_word(out32 + w, bits, j->h_ticket, j->h_part, j->h_part0, j->h_n, tickets, parts);
-      else
-        tb_tx_settle_word(out32 + w, bits, j->t_ticket, j->t_part, j->t_part0, j->t_n, tickets, parts);
-    } else {
-      out32[w] = bits;
-    }
-  }
-}
-
 typedef uint32_t tb_u32x4_t __attribute__((ext_vector_type(4)));
 template <typename J> __device__ __forceinline__ uint32_t crc_len_of(J j) { return j->crc_len; }
-/* SCR: the packed, scrambled store (tb_tx_fused_scr_kernel) instead of the bit-per-byte one (tb_tx_fused_kernel); SCR + SYM:
+/* SCR: the packed, scrambled store (tb_tx_fused_scr_kernel, tb_tx_scr.h) instead of the bit-per-byte one (tb_tx_fused_kernel); SCR + SYM:
  * the scrambled, mapped and layer-mapped points (tb_tx_fused_sym_kernel, tb_tx_sym.h) */
 template <bool SCR, bool SYM = false>
 __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch, uint8_t *coded,

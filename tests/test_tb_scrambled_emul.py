@@ -2,6 +2,7 @@
 workgroup's threads walked phase by phase) against numpy unscrambling followed by the oracle's de-interleaving, rate
 de-matching and pack.  No GPU: the sequence words staged in LDS come from the host jump-ahead of nr_gold.h."""
 import ctypes as C
+import re
 import subprocess
 from pathlib import Path
 
@@ -39,45 +40,75 @@ def unscramble(f, c_init, bit_off):
     return out
 
 
+def check_segment(emul, rng, BG, A, lbrm, Qm, rv, E, c_init, bit_off):
+    """one segment of E LLRs at codeword bit bit_off through the emulated phases, first round (clear) and a later one, against
+    numpy unscrambling and the oracle's de-interleaving, rate de-matching and pack"""
+    s = O.segmentation(None, O.len_with_crc(1, A), BG)
+    Z, K, F, Cn = s["Z"], s["K"], s["F"], s["C"]
+    N = (66 if BG == 1 else 50) * Z
+    R, _ = O.get_R(rv, E, BG, Z, 0, 0)
+    ncols = O.NCOLS[(BG, R)]
+    f = rng.integers(-300, 300, E).astype(np.int16)
+    f[rng.integers(0, E, 6)] = [-32768, 32767, 0, -32768, 1, -1]
+    for clear in (1, 0):
+        w0 = rng.integers(-2000, 2000, 66 * 384 + 16).astype(np.int16)
+        Ncb = N if not lbrm else min(N, (3 * lbrm // (2 * Cn)))
+        e = O.deinterleave(E, Qm, unscramble(f, c_init, bit_off))
+        d_ref = w0[:N].copy()                    # dirty behind Ncb too: R0 on round 0, as it is otherwise
+        if clear:
+            SB.clear_segment(d_ref, Ncb, BG, Z, R)
+        rc, d_ref = O.rate_match_rx(lbrm, BG, Z, d_ref, e, Cn, rv, clear, E, F, K - F - 2 * Z)
+        assert rc == 0
+        l_ref = O.llr_prepack(d_ref, BG, Z, K, F, ncols)
+        w = w0.copy()
+        l = np.full(ncols * Z + 8, 0x11, np.int8)
+        f_in = f.copy()
+        span = emul.tb_emul_rx_dematch_scr(lbrm, BG, Z, Cn, F, K, rv, E, Qm, ncols * Z, clear, 256, c_init, bit_off,
+                                           f_in.ctypes.data, w.ctypes.data, l.ctypes.data)
+        assert span > 0
+        key = (BG, A, Qm, rv, E, clear, bit_off)
+        assert np.array_equal(f_in, f), key                    # the LLRs are only read
+        assert np.array_equal(w[:N], d_ref), key
+        assert np.array_equal(w[N:], w0[N:]), key
+        assert np.array_equal(l[:ncols * Z], l_ref), key
+        assert (l[ncols * Z:] == 0x11).all()
+
+
 def test_rx_dematch_phases_unscramble_against_the_oracle(emul):
     rng = np.random.default_rng(2026)
     cases = chunked = 0
     for BG, A, lbrm in ((1, 30000, 0), (1, 30000, 24000), (2, 3000, 0), (2, 640, 0), (1, 100000, 150000)):
         s = O.segmentation(None, O.len_with_crc(1, A), BG)
-        Z, K, F, Cn = s["Z"], s["K"], s["F"], s["C"]
-        N = (66 if BG == 1 else 50) * Z
+        Z, K, F = s["Z"], s["K"], s["F"]
         for Qm in (2, 4, 6, 8):
             for rv in (0, 2, 3):
                 for rate in (0.6, 0.92, 0.08):                       # 0.08: E > Ncb, several laps (and several chunks)
                     E = max(Qm * 4, int((K - F) / rate) // Qm * Qm)
-                    R, _ = O.get_R(rv, E, BG, Z, 0, 0)
-                    ncols = O.NCOLS[(BG, R)]
-                    f = rng.integers(-300, 300, E).astype(np.int16)
-                    f[rng.integers(0, E, 6)] = [-32768, 32767, 0, -32768, 1, -1]
                     c_init = int(rng.integers(0, 1 << 31))
                     bit_off = int(rng.integers(0, 200000)) * 2 + 1 if cases % 3 else int(rng.integers(0, 5000)) * 32
-                    for clear in (1, 0):
-                        w0 = rng.integers(-2000, 2000, 66 * 384 + 16).astype(np.int16)
-                        Ncb = N if not lbrm else min(N, (3 * lbrm // (2 * Cn)))
-                        e = O.deinterleave(E, Qm, unscramble(f, c_init, bit_off))
-                        d_ref = w0[:N].copy()                    # dirty behind Ncb too: R0 on round 0, as it is otherwise
-                        if clear:
-                            SB.clear_segment(d_ref, Ncb, BG, Z, R)
-                        rc, d_ref = O.rate_match_rx(lbrm, BG, Z, d_ref, e, Cn, rv, clear, E, F, K - F - 2 * Z)
-                        assert rc == 0
-                        l_ref = O.llr_prepack(d_ref, BG, Z, K, F, ncols)
-                        w = w0.copy()
-                        l = np.full(ncols * Z + 8, 0x11, np.int8)
-                        f_in = f.copy()
-                        span = emul.tb_emul_rx_dematch_scr(lbrm, BG, Z, Cn, F, K, rv, E, Qm, ncols * Z, clear, 256, c_init, bit_off,
-                                                           f_in.ctypes.data, w.ctypes.data, l.ctypes.data)
-                        assert span > 0
-                        key = (BG, A, Qm, rv, rate, clear, bit_off)
-                        assert np.array_equal(f_in, f), key                    # the LLRs are only read
-                        assert np.array_equal(w[:N], d_ref), key
-                        assert np.array_equal(w[N:], w0[N:]), key
-                        assert np.array_equal(l[:ncols * Z], l_ref), key
-                        assert (l[ncols * Z:] == 0x11).all()
-                        cases += 1
-                        chunked += E // Qm > (512 - 2) * 32 // Qm
+                    check_segment(emul, rng, BG, A, lbrm, Qm, rv, E, c_init, bit_off)
+                    cases += 2
+                    chunked += 2 * (E // Qm > (512 - 2) * 32 // Qm)
     assert cases > 300 and chunked > 10
+
+
+def scr_chunk(Qm):
+    """symbols per sequence chunk of the scrambled de-matching (tb_rx_core.h tb_rx_scr_chunk), from TB_RX_SCR_WORDS"""
+    words = int(re.search(r"#define TB_RX_SCR_WORDS (\d+)u", (CSRC / "tb_jobs.h").read_text()).group(1))
+    return (words - 2) * 32 // Qm
+
+
+def test_rx_dematch_unscramble_at_the_sequence_chunk_edges(emul):
+    """segments of exactly c - 1, c, c + 1 and 2c symbols (c = the symbols of one staged sequence chunk) for every Qm, at a
+    word-aligned and at an odd codeword offset, rv 0 and 3, a plain and an LBRM code"""
+    rng = np.random.default_rng(8160)
+    hit = {}
+    for BG, A, lbrm in ((1, 30000, 0), (2, 3000, 0), (1, 30000, 24000)):
+        for Qm in (2, 4, 6, 8):
+            c = scr_chunk(Qm)
+            for edge, EQ in (("c-1", c - 1), ("c", c), ("c+1", c + 1), ("2c", 2 * c)):
+                for rv, odd in ((0, True), (3, False), (3, True)):
+                    bit_off = int(rng.integers(0, 100000)) * 2 + 1 if odd else int(rng.integers(0, 5000)) * 32
+                    check_segment(emul, rng, BG, A, lbrm, Qm, rv, EQ * Qm, int(rng.integers(0, 1 << 31)), bit_off)
+                    hit[(Qm, edge, odd)] = hit.get((Qm, edge, odd), 0) + 1
+    assert len(hit) == 4 * 4 * 2 and min(hit.values()) >= 3
