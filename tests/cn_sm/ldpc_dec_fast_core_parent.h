@@ -9,12 +9,9 @@
  *   - the circularly shifted 4-byte window of a neighbour is fetched as two aligned dwords +
  *     v_alignbyte_b32; APP rows are stored twice back to back (no modulo on t + shift), message rows
  *     carry 4 wrap-around pad bytes;
- *   - arithmetic runs on packed 16-bit pairs: biased bytes are zero-extended (lanes (0,2) with an and, lanes (1,3)
- *     with v_perm_b32 or a shift), the bias cancels in a' - r', sums of biased bytes cannot overflow 16 bits
- *     (<= 31 * 255), saturation is done once per result;
- *   - the check node takes a' - r' as ONE packed f16 subtract: zero-extended bytes are f16 denormals, their difference
- *     is exact and an f16 is sign-magnitude, which is what min-sum wants (ldpc_psub_sm); the minima are f16 maxima of
- *     negative keys (ldpc_pmin3_keys).  No floating-point rounding takes place anywhere.
+ *   - arithmetic runs on packed 16-bit pairs (v_pk_*_i16/u16): biased bytes are zero-extended with
+ *     v_perm_b32, the bias cancels in a' - r', sums of biased bytes cannot overflow 16 bits
+ *     (<= 31 * 255), saturation is done once per result.
  * Bit-exactness argument for the rewritten min-sum (DESIGN.md "Kernel arithmetic"):
  *   q = clamp(app - r, -127, 127) only enters as |q| (capped at 127) and sign(q); |q| = min(|app - r|, 127)
  *   and sign(q) = sign(app - r), so the clamp is applied to the magnitude only.
@@ -37,15 +34,12 @@ LDPC_HD uint32_t ldpc_alignbyte(uint32_t hi, uint32_t lo, uint32_t sh) { return 
 LDPC_HD uint32_t ldpc_umulhi(uint32_t a, uint32_t b) { return __umulhi(a, b); }
 #else
 LDPC_HD uint32_t ldpc_perm(uint32_t s0, uint32_t s1, uint32_t sel)
-{ /* v_perm_b32: byte i of the result = byte sel[i] of {s0 (4..7), s1 (0..3)}; 0x08 .. 0x0b -> 0x00 / 0xff = bit 7 of byte
-   * 1 / 3 / 5 / 7 spread over the byte; 0x0c -> 0x00; above -> 0xff */
+{ /* v_perm_b32: byte i of the result = byte sel[i] of {s0 (4..7), s1 (0..3)}; 0x0c -> 0x00 */
   const uint64_t src = ((uint64_t)s0 << 32) | s1;
   uint32_t r = 0;
   for (int i = 0; i < 4; i++) {
     const uint32_t s = (sel >> (8 * i)) & 0xff;
-    const uint32_t b = s <= 7    ? (uint32_t)((src >> (8 * s)) & 0xff)
-                       : s <= 11 ? (((src >> (16 * (s - 8) + 15)) & 1) ? 0xffu : 0u)
-                                 : (s == 0x0c ? 0u : 0xffu);
+    const uint32_t b = s <= 7 ? (uint32_t)((src >> (8 * s)) & 0xff) : (s == 0x0c ? 0u : 0xffu);
     r |= b << (8 * i);
   }
   return r;
@@ -80,33 +74,6 @@ LDPC_HD ldpc_v2u ldpc_pmin3_keys(ldpc_v2u a, ldpc_v2u b, ldpc_v2u c)
   return __builtin_elementwise_min(__builtin_elementwise_min(a, b), c);
 #endif
 }
-/* a - r of two zero-extended bytes per 16-bit half, as SIGN-MAGNITUDE: bit 15 = (a < r), bits 7..0 = |a - r|, rest 0.  A half
- * 0x00bb is the f16 denormal bb * 2^-24; the difference of two of them is again a denormal (|a - r| <= 255 < 1024), exact, and
- * an f16 is sign-magnitude; a == r gives +0 under round-to-nearest.  One packed f16 subtract where the integer form took a
- * subtract, a negate and a maximum (tools/ubench/pk_add_f16_sm.hip: all 65 536 byte pairs in both halves, and the issue rate;
- * f16 denormals are not flushed in HIP kernels). */
-LDPC_HD uint32_t ldpc_psub_sm(uint32_t a, uint32_t r)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-  /* v_pk_add_f16 d, a, r neg_lo:[0,1] neg_hi:[0,1]; written as a vector subtract so that the compiler places constants
-   * in scalar registers and schedules it like any other op (no fast-math flag is in force: the subtract is IEEE) */
-  typedef _Float16 ldpc_v2h __attribute__((ext_vector_type(2)));
-  const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_bit_cast(ldpc_v2h, a) - __builtin_bit_cast(ldpc_v2h, r));
-  return d;
-#else
-  uint32_t d = 0;
-  for (int h = 0; h < 32; h += 16) {
-    const uint32_t x = (a >> h) & 0xffffu, y = (r >> h) & 0xffffu;
-    d |= (x < y ? 0x8000u | (y - x) : x - y) << h;
-  }
-  return d;
-#endif
-}
-/* the key of the minimum network (ldpc_pmin3_keys) from a sign-magnitude difference: 0x8000 + |d| per half */
-LDPC_HD ldpc_v2u ldpc_sm_key(uint32_t d) { return __builtin_bit_cast(ldpc_v2u, d | 0x80008000u); }
-/* bytes 0,2 resp. 1,3 of w zero-extended into the two 16-bit halves: lanes (0,2) and (1,3), the bit-node side's pairing */
-LDPC_HD uint32_t ldpc_unpack_even(uint32_t w) { return w & 0x00ff00ffu; }
-LDPC_HD uint32_t ldpc_unpack_odd(uint32_t w) { return ldpc_perm(0u, w, 0x0c030c01u); }
 LDPC_HD uint32_t ldpc_as_u32(ldpc_v2i x) { return __builtin_bit_cast(uint32_t, x); }
 LDPC_HD ldpc_v2i ldpc_splat(int v) { return (ldpc_v2i){(short)v, (short)v}; }
 LDPC_HD ldpc_v2i ldpc_pmin(ldpc_v2i a, ldpc_v2i b) { return __builtin_elementwise_min(a, b); }
@@ -152,18 +119,11 @@ LDPC_HD uint32_t ldpc_window(const uint8_t *base, uint32_t off) { return ldpc_wi
  * half = "not negative", cnProc.h:940) -- the bytes that hold those bits are gathered with one v_perm.  Parity of the hard
  * decisions = parity of the not-negative ones ^ (D & 1).  (Until round 6 the bodies returned a 4-bit mask: seven shifts and ors
  * to pack it and ten for the degree-1 bit, per item -- 4.6 % of the headline kernel's VALU instructions.) */
-/* SEL = where the four lanes' halves sit in (extl, exth): lanes (0,1)/(2,3) -- ldpc_fast_pc -- or, LDPC_SEL_EO, lanes
- * (0,2)/(1,3) -- the check-node bodies. */
-#define LDPC_SEL_EO 0x07030501u
-/* v_perm selector that spreads bit 15 of the four halves of (odd lanes, even lanes) over one byte each, in lane order:
- * 0xff = the lane's sign-magnitude difference is negative, 0x00 = it is not */
-#define LDPC_SEL_SIGNS 0x0b090a08u
-template <uint32_t SEL = 0x07050301u>
 LDPC_HD uint32_t ldpc_fast_odd_lanes(uint32_t parw, bool ext, uint32_t extl, uint32_t exth, int D)
 {
   uint32_t np = parw >> 7;
   if (ext)
-    np ^= ldpc_perm(exth, extl, SEL);
+    np ^= ldpc_perm(exth, extl, 0x07050301u);
   if (D & 1)
     np = ~np;
   return np & 0x01010101u;
@@ -180,50 +140,51 @@ LDPC_HD uint32_t ldpc_fast_valid_lanes(int valid) { return valid > 0 ? 0x0101010
  * the parity of the previous pass' hard decisions of lane t+i is odd.
  *
  * Arithmetic, per 16-bit half (two lanes per register, a' = app + 128, r' = r + 128 as stored):
- *   a', r' zero-extended: lanes (0,2) with one and, lanes (1,3) with one v_perm -- no bias to or in
- *   d  = a' - r' as sign-magnitude  (ldpc_psub_sm: ONE packed f16 subtract)   d = app - r in [-255, 255]; bit 15 = (d < 0)
- *   M  = d | 0x8000         = 0x8000 + |d|        the key of the minimum network; running two smallest m1 <= m2
+ *   D1 = (0x8000 | a') - r' = 0x8000 + d          d = app - r in [-255, 255]; bit 15 of D1 = (d >= 0)
+ *   D2 = 0x10000 - D1       = 0x8000 - d          (one 32-bit subtract: the low half always borrows)
+ *   M  = max_u16(D1, D2)    = 0x8000 + |d|        biased magnitude; running two smallest m1 <= m2
  *   cap m1, m2 at 0x8000 + 127 once per check node (min(127, min_k |q_k|) = min_k min(127, |q_k|))
  *   o_k = m1 + m2 - min(M_k, m2)  (= m2 if edge k holds the minimum, else m1), bias folded into the sum
- *   sign_k = parity of the negative inputs among the other edges = bit 15 of (xor of all d) ^ d_k
- * (Until round 7: D1 = (0x8000 | a') - r', D2 = 0x10000 - D1, M = max_u16(D1, D2) -- four v_perm, four subtracts and two
- * packed maxima per edge where there are now two ands, two v_perm, two packed subtracts and two ors.) */
-/* Sign-magnitude differences of one edge (see above) for lanes (0,2) -- de -- and (1,3) -- dod -- from the LDS words; `first`
- * additionally folds the edge into the syndrome accumulators (only wanted once per edge). */
+ *   sign_k = parity of the negative inputs among the other edges = bit 15 of (xor of all D1) ^ D1_k,
+ *            flipped when D-1 is odd (bit 15 counts the NON-negative ones)
+ * Only the packed min/max/shift/negate run on the half-rate packed-16 pipe; the rest are full-rate
+ * 32-bit ALU ops that cannot carry between the halves by construction. */
+/* D1 pairs of one edge (see above) from the LDS words; `first` additionally folds the edge into the syndrome
+ * accumulators (only wanted once per edge). */
 /* P1 = first pass of a block: every message is still 0, `rw` is not looked at (the caller has not loaded it and the
  * message array need not be initialised) */
 template <bool IS_EXT, bool P1 = false>
-LDPC_HD void ldpc_fast_cn_edge(const ldpc_fast_lds &L, uint32_t info, int t, uint32_t rw, bool first, uint32_t &de, uint32_t &dod,
-                               uint32_t &parw, uint32_t &exte, uint32_t &exto)
+LDPC_HD void ldpc_fast_cn_edge(const ldpc_fast_lds &L, uint32_t info, int t, uint32_t rw, bool first, uint32_t &dl, uint32_t &dh,
+                               uint32_t &parw, uint32_t &extl, uint32_t &exth)
 {
+  uint32_t al, ah, rl, rh;
   if (IS_EXT) {
     const uint32_t lw = L.ext_global ? (*reinterpret_cast<const uint32_t *>(L.gllr + info + (uint32_t)t) ^ 0x80808080u)
                                      : ldpc_lds_ld32(L.base, info + (uint32_t)t);
-    const uint32_t ae = ldpc_unpack_even(lw), ao = ldpc_unpack_odd(lw);
+    al = ldpc_perm(0x80808080u, lw, 0x05010400u);
+    ah = ldpc_perm(0x80808080u, lw, 0x05030402u);
     if (first) { /* hard decision of the degree-1 bit: sat8(llr + r) < 0 <=> llr' + r' < 256 (cnProc.h:940) */
-      exte = ae + (P1 ? 0x00800080u : ldpc_unpack_even(rw));
-      exto = ao + (P1 ? 0x00800080u : ldpc_unpack_odd(rw));
+      extl = al + (P1 ? 0x00800080u : ldpc_perm(0u, rw, 0x0c010c00u));
+      exth = ah + (P1 ? 0x00800080u : ldpc_perm(0u, rw, 0x0c030c02u));
     }
-    de = ldpc_psub_sm(ae, 0x00800080u); /* this edge's CN input is the channel LLR itself (mPass.h:306-388) */
-    dod = ldpc_psub_sm(ao, 0x00800080u);
+    rl = 0x00800080u; /* this edge's CN input is the channel LLR itself (mPass.h:306-388) */
+    rh = 0x00800080u;
   } else {
     const uint32_t aw = ldpc_window(L.base, info + (uint32_t)t);
     if (first)
       parw ^= aw;
-    if (P1) {
-      de = ldpc_psub_sm(ldpc_unpack_even(aw), 0x00800080u);
-      dod = ldpc_psub_sm(ldpc_unpack_odd(aw), 0x00800080u);
-    } else {
-      de = ldpc_psub_sm(ldpc_unpack_even(aw), ldpc_unpack_even(rw));
-      dod = ldpc_psub_sm(ldpc_unpack_odd(aw), ldpc_unpack_odd(rw));
-    }
+    al = ldpc_perm(0x80808080u, aw, 0x05010400u); /* (0x8000 | byte 0), (0x8000 | byte 1) */
+    ah = ldpc_perm(0x80808080u, aw, 0x05030402u);
+    rl = P1 ? 0x00800080u : ldpc_perm(0u, rw, 0x0c010c00u);
+    rh = P1 ? 0x00800080u : ldpc_perm(0u, rw, 0x0c030c02u);
   }
+  dl = al - rl;
+  dh = ah - rh;
 }
 
-/* MODE 0: d and the keys of every edge stay in registers between the two sweeps; 1: d only (keys
- * recomputed); 2: nothing (the second sweep re-reads LDS and recomputes d) -- for the degree-19 rows, whose 38+
- * live registers would otherwise spill at 16 waves per workgroup.
- * In all the check-node bodies the suffixes l / h (_lo / _hi) of a packed register stand for lanes (0,2) / (1,3). */
+/* MODE 0: D1 and the magnitudes of every edge stay in registers between the two sweeps; 1: D1 only (magnitudes
+ * recomputed); 2: nothing (the second sweep re-reads LDS and recomputes D1) -- for the degree-19 rows, whose 38+
+ * live registers would otherwise spill at 16 waves per workgroup. */
 /* boff_r / boff_a (several blocks per workgroup, ldpc_dec_fast_mblock.h): byte offset of the item's block inside a
  * message / extension-LLR row resp. inside an APP row; 0 in the one-block kernels, where they fold away. */
 template <int D, bool EXT, int MODE, bool P1 = false>
@@ -249,8 +210,8 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
       d_lo[k] = dl;
       d_hi[k] = dh;
     }
-    const ldpc_v2u ml = ldpc_sm_key(dl);
-    const ldpc_v2u mh = ldpc_sm_key(dh);
+    const ldpc_v2u ml = ldpc_pmaxu(ldpc_as_v2u(dl), ldpc_as_v2u(0x00010000u - dl));
+    const ldpc_v2u mh = ldpc_pmaxu(ldpc_as_v2u(dh), ldpc_as_v2u(0x00010000u - dh));
     if (KEEP) {
       g_lo[k] = ldpc_u2u32(ml);
       g_hi[k] = ldpc_u2u32(mh);
@@ -266,12 +227,16 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
   m1l = ldpc_pminu(m1l, cap); m2l = ldpc_pminu(m2l, cap);
   m1h = ldpc_pminu(m1h, cap); m2h = ldpc_pminu(m2h, cap);
   const uint32_t sl = (ldpc_u2u32(m1l) - 0x80008000u) + ldpc_u2u32(m2l), sh = (ldpc_u2u32(m1h) - 0x80008000u) + ldpc_u2u32(m2h);
-  /* Signs are applied to the four output bytes at once.  Bit 15 of a half of (sx ^ d_k) says "negative"; the bytes
+  if ((D - 1) & 1) {
+    sxl ^= 0x80008000u;
+    sxh ^= 0x80008000u;
+  }
+  /* Signs are applied to the four output bytes at once.  Bit 15 of a half of (sx ^ D1_k) says "negative"; the bytes
    * that hold those bits (1 and 3 of each register) are gathered with one v_perm, for the row's xor once and per edge
    * once.  With n = 0 / 1 per byte and a magnitude o <= 127, the biased byte is 128 + o = o ^ 0x80 for n = 0 and
    * 128 - o = (o ^ 0x7f) + 1 for n = 1, i.e. (o ^ (0x80 - n)) + n: three plain 32-bit ops for four lanes, no carry
    * between the bytes (the largest value is 0x80). */
-  const uint32_t sx4 = ldpc_perm(sxh, sxl, LDPC_SEL_EO);
+  const uint32_t sx4 = ldpc_perm(sxh, sxl, 0x07050301u);
 #pragma unroll
   for (int k = 0; k < D; k++) {
     uint32_t dl, dh;
@@ -286,18 +251,18 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
       else
         ldpc_fast_cn_edge<false, P1>(L, info, ta, rw, false, dl, dh, parw, extl, exth);
     }
-    const ldpc_v2u ml = KEEP ? ldpc_as_v2u(g_lo[k]) : ldpc_sm_key(dl);
-    const ldpc_v2u mh = KEEP ? ldpc_as_v2u(g_hi[k]) : ldpc_sm_key(dh);
+    const ldpc_v2u ml = KEEP ? ldpc_as_v2u(g_lo[k]) : ldpc_pmaxu(ldpc_as_v2u(dl), ldpc_as_v2u(0x00010000u - dl));
+    const ldpc_v2u mh = KEEP ? ldpc_as_v2u(g_hi[k]) : ldpc_pmaxu(ldpc_as_v2u(dh), ldpc_as_v2u(0x00010000u - dh));
     const uint32_t ol = sl - ldpc_u2u32(ldpc_pminu(ml, m2l)), oh = sh - ldpc_u2u32(ldpc_pminu(mh, m2h)); /* magnitudes, 0..127 per half */
-    const uint32_t o4 = ldpc_perm(oh, ol, 0x06020400u);
-    const uint32_t n4 = ((sx4 ^ ldpc_perm(dh, dl, LDPC_SEL_EO)) >> 7) & 0x01010101u;
+    const uint32_t o4 = ldpc_perm(oh, ol, 0x06040200u);
+    const uint32_t n4 = ((sx4 ^ ldpc_perm(dh, dl, 0x07050301u)) >> 7) & 0x01010101u;
     const uint32_t w = (o4 ^ (0x80808080u - n4)) + n4;
     *reinterpret_cast<uint32_t *>(rrow + k * rstride) = w;
     *reinterpret_cast<uint32_t *>(rpad + k * rstride) = w;
   }
   /* per lane: number of "not negative" neighbours mod 2, from bit 7 of the biased APP bytes and bit 8 of
    * the extension sums; parity of the hard decisions = that ^ (D & 1) */
-  return ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw, EXT, extl, exth, D);
+  return ldpc_fast_odd_lanes(parw, EXT, extl, exth, D);
 }
 
 /* The same check-node item with the "minimum of the OTHER edges" taken from prefixes and suffixes instead of through the
@@ -308,7 +273,7 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
  * i.e. per pair of edges and 16-bit half FOUR packed ops (prefix, suffix, two outputs) + two for the magnitudes, where
  * the two-minima form needs five plus a subtract per EDGE and six more per row -- and the packed ops are the slow ones
  * (tools/ubench/valu_rate.hip).  The sign bytes of an edge are gathered once in the forward sweep (one v_perm, needed
- * anyway) and kept instead of the two difference words.  Registers per edge: M per half + signs, P per half and pair.
+ * anyway) and kept instead of the two D1 words.  Registers per edge: M per half + signs, P per half and pair.
  * Bit-identical outputs: the minimum over the other edges is the same number whichever way it is found. */
 template <int D, bool EXT, bool P1 = false>
 LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, int rstride, int boff_r = 0, int boff_a = 0)
@@ -329,11 +294,11 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
       ldpc_fast_cn_edge<true, P1>(L, info, t, rw, true, dl, dh, parw, extl, exth);
     else
       ldpc_fast_cn_edge<false, P1>(L, info, ta, rw, true, dl, dh, parw, extl, exth);
-    const ldpc_v2u ml = ldpc_sm_key(dl);
-    const ldpc_v2u mh = ldpc_sm_key(dh);
+    const ldpc_v2u ml = ldpc_pmaxu(ldpc_as_v2u(dl), ldpc_as_v2u(0x00010000u - dl));
+    const ldpc_v2u mh = ldpc_pmaxu(ldpc_as_v2u(dh), ldpc_as_v2u(0x00010000u - dh));
     m_lo[k] = ldpc_u2u32(ml);
     m_hi[k] = ldpc_u2u32(mh);
-    s4[k] = ldpc_perm(dh, dl, LDPC_SEL_SIGNS); /* bit 15 of the four halves, a byte each */
+    s4[k] = ldpc_perm(dh, dl, 0x07050301u); /* the bytes that carry bit 15 of the four D1 halves */
     sx4 ^= s4[k];
     if ((k & 1) && k < D - 1) { /* P of pair k / 2: wanted by the pairs (and the single edge) behind it */
       const int i = k / 2;
@@ -341,13 +306,15 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
       p_hi[i] = ldpc_u2u32(ldpc_pmin3_keys(i ? ldpc_as_v2u(p_hi[i - 1]) : cap, ldpc_as_v2u(m_hi[k - 1]), mh));
     }
   }
-  /* Signs.  The byte of s4 that stands for a lane is 0xff (d < 0) or 0x00 (LDPC_SEL_SIGNS), so the xor over the OTHER edges
-   * is 0xff = "an odd number of them is negative" or 0x00; 0x80 is xor-ed in once per row: x = 0x7f (odd) or 0x80.  The
-   * biased output byte 128 + o (x = 0x80) or 128 - o = (o ^ 0x7f) + 1 (x = 0x7f) is (o ^ x) + (x & 1): four plain 32-bit
-   * ops per edge for four lanes, no carry between the bytes (the largest value is 0x80 + 0x7f resp. 0x7f + 1). */
-  sx4 ^= 0x80808080u;
+  /* Signs.  The byte of s4 that stands for a lane is the high byte of 0x8000 + d, d in [-255, 255]: 0x80 (d >= 0) or 0x7f
+   * (d < 0), nothing else.  The xor over the OTHER edges is therefore 0x80 / 0x7f (odd count) or 0x00 / 0xff (even count:
+   * xor 0x80 in) per byte -- 0x7f = "an odd number of them is negative".  With x that byte, the biased output byte
+   * 128 + o (x = 0x80) or 128 - o = (o ^ 0x7f) + 1 (x = 0x7f) is (o ^ x) + (x & 1): four plain 32-bit ops per edge for
+   * four lanes, no carry between the bytes (the largest value is 0x80 + 0x7f resp. 0x7f + 1). */
+  if (!((D - 1) & 1))
+    sx4 ^= 0x80808080u;
   auto put = [&](int k, ldpc_v2u ol, ldpc_v2u oh) {
-    const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06020400u); /* low bytes: the magnitudes 0..127 */
+    const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06040200u); /* low bytes: the magnitudes 0..127 */
     const uint32_t x4 = sx4 ^ s4[k];
     const uint32_t w = (o4 ^ x4) + (x4 & 0x01010101u);
     *reinterpret_cast<uint32_t *>(rrow + k * rstride) = w;
@@ -372,7 +339,7 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
       sh = last ? ldpc_pminu(a0h, a1h) : ldpc_pmin3_keys(sh, a0h, a1h);
     }
   }
-  return ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw, EXT, extl, exth, D);
+  return ldpc_fast_odd_lanes(parw, EXT, extl, exth, D);
 }
 
 /* TWO items of one degree group per thread (a double task, ldpc_graph.h f_cn_task), walked edge by edge TOGETHER: the same
@@ -409,11 +376,11 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
         ldpc_fast_cn_edge<true, P1>(L, info[n], t[n], rw[n], true, dl, dh, parw[n], extl[n], exth[n]);
       else
         ldpc_fast_cn_edge<false, P1>(L, info[n], t[n], rw[n], true, dl, dh, parw[n], extl[n], exth[n]);
-      const ldpc_v2u ml = ldpc_sm_key(dl);
-      const ldpc_v2u mh = ldpc_sm_key(dh);
+      const ldpc_v2u ml = ldpc_pmaxu(ldpc_as_v2u(dl), ldpc_as_v2u(0x00010000u - dl));
+      const ldpc_v2u mh = ldpc_pmaxu(ldpc_as_v2u(dh), ldpc_as_v2u(0x00010000u - dh));
       m_lo[n][k] = ldpc_u2u32(ml);
       m_hi[n][k] = ldpc_u2u32(mh);
-      s4[n][k] = ldpc_perm(dh, dl, LDPC_SEL_SIGNS);
+      s4[n][k] = ldpc_perm(dh, dl, 0x07050301u);
       sx4[n] ^= s4[n][k];
       if ((k & 1) && k < D - 1) {
         const int i = k / 2;
@@ -422,10 +389,12 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
       }
     }
   }
-  sx4[0] ^= 0x80808080u;
-  sx4[1] ^= 0x80808080u;
+  if (!((D - 1) & 1)) {
+    sx4[0] ^= 0x80808080u;
+    sx4[1] ^= 0x80808080u;
+  }
   auto put = [&](int n, int k, ldpc_v2u ol, ldpc_v2u oh) {
-    const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06020400u);
+    const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06040200u);
     const uint32_t x4 = sx4[n] ^ s4[n][k];
     const uint32_t w = (o4 ^ x4) + (x4 & 0x01010101u);
     *reinterpret_cast<uint32_t *>(rrow[n] + k * rstride) = w;
@@ -459,7 +428,7 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
   uint32_t out[N];
 #pragma unroll
   for (int n = 0; n < N; n++) {
-    out[n] = ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw[n], EXT, extl[n], exth[n], D);
+    out[n] = ldpc_fast_odd_lanes(parw[n], EXT, extl[n], exth[n], D);
   }
   mask_b = out[1];
   return out[0];
@@ -508,9 +477,9 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
     const uint32_t rw = P1 ? 0u : *reinterpret_cast<const uint32_t *>(rrow + kk * rstride);
     uint32_t dl, dh, pw = 0;
     ldpc_fast_cn_edge<false, P1>(L, info, t, rw, true, dl, dh, pw, extl, exth);
-    ldpc_v2u ml = ldpc_sm_key(dl);
-    ldpc_v2u mh = ldpc_sm_key(dh);
-    uint32_t sg = ldpc_perm(dh, dl, LDPC_SEL_SIGNS);
+    ldpc_v2u ml = ldpc_pmaxu(ldpc_as_v2u(dl), ldpc_as_v2u(0x00010000u - dl));
+    ldpc_v2u mh = ldpc_pmaxu(ldpc_as_v2u(dh), ldpc_as_v2u(0x00010000u - dh));
+    uint32_t sg = ldpc_perm(dh, dl, 0x07050301u);
     if (!live) {
       ml = mh = ldpc_splatu(LDPC_KEY_NEUTRAL);
       sg = 0u;
@@ -539,7 +508,7 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
       const int k = 2 * i + q, ko = 2 * i + 1 - q;
       const bool live = k < N - 1 || !half;
       const ldpc_v2u ol = ldpc_pmin3_keys(pvl, ldpc_as_v2u(m_lo[ko]), sl), oh = ldpc_pmin3_keys(pvh, ldpc_as_v2u(m_hi[ko]), sh);
-      const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06020400u);
+      const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06040200u);
       const uint32_t x4 = sx4 ^ s4[k];
       const uint32_t w = (o4 ^ x4) + (x4 & 0x01010101u);
       if (live) {

@@ -24,6 +24,7 @@ OPK(xor_b32, "v_xor_b32 %0, %1, %2")
 OPK(add_u32, "v_add_u32 %0, %1, %2")
 OPK(sub_u32, "v_sub_u32 %0, %1, %2")
 OPK(and_b32, "v_and_b32 %0, %1, %2")
+OPK(or_b32, "v_or_b32 %0, %1, %2")
 OPK(min_i32, "v_min_i32 %0, %1, %2")
 OPK(max_i32, "v_max_i32 %0, %1, %2")
 OPK(min_u32, "v_min_u32 %0, %1, %2")
@@ -44,6 +45,9 @@ OPK(pk_ashr_i16, "v_pk_ashrrev_i16 %0, 15, %1 op_sel_hi:[0,1]")
 OPK(pk_lshl_b16, "v_pk_lshlrev_b16 %0, 1, %1 op_sel_hi:[0,1]")
 OPK(pk_mul_lo, "v_pk_mul_lo_u16 %0, %1, %2")
 OPK(pk_mad_i16, "v_pk_mad_i16 %0, %1, %2, %1")
+OPK(pk_max_u16, "v_pk_max_u16 %0, %1, %2")
+OPK(pk_add_f16, "v_pk_add_f16 %0, %1, %2")
+OPK(pk_add_f16_neg, "v_pk_add_f16 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]")
 OPK(perm_b32, "v_perm_b32 %0, %1, %2, %2")
 OPK(alignbyte, "v_alignbyte_b32 %0, %1, %2, 1")
 OPK(alignbit, "v_alignbit_b32 %0, %1, %2, 8")
@@ -79,9 +83,9 @@ int main()
   uint32_t *d; (void)hipMalloc(&d, 64);
   for (int bpc : {8}) {
     fma_ns = 0;
-    RUN(fma_f32); RUN(xor_b32); RUN(add_u32); RUN(sub_u32); RUN(and_b32); RUN(min_i32); RUN(max_i32); RUN(min_u32); RUN(med3_i32); RUN(min3_u32);
+    RUN(fma_f32); RUN(xor_b32); RUN(add_u32); RUN(sub_u32); RUN(and_b32); RUN(or_b32); RUN(min_i32); RUN(max_i32); RUN(min_u32); RUN(med3_i32); RUN(min3_u32);
     RUN(lshrrev); RUN(ashrrev); RUN(bfe_i32); RUN(bfi_b32); RUN(and_or); RUN(lshl_or); RUN(cndmask);
-    RUN(pk_add_u16); RUN(pk_sub_i16); RUN(pk_min_i16); RUN(pk_max_i16); RUN(pk_ashr_i16); RUN(pk_lshl_b16); RUN(pk_mul_lo); RUN(pk_mad_i16);
+    RUN(pk_add_u16); RUN(pk_sub_i16); RUN(pk_min_i16); RUN(pk_max_i16); RUN(pk_ashr_i16); RUN(pk_lshl_b16); RUN(pk_mul_lo); RUN(pk_mad_i16); RUN(pk_max_u16); RUN(pk_add_f16); RUN(pk_add_f16_neg);
     RUN(perm_b32); RUN(alignbyte); RUN(alignbit); RUN(sad_u8); RUN(sub_sdwa); RUN(max_i16); RUN(sub_i16); RUN(mul_u24); RUN(mul_lo_u32); RUN(mul_hi_u32); RUN(dot4_i8); RUN(mov_dpp);
   }
   return 0;
