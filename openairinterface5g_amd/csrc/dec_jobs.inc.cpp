@@ -1,6 +1,6 @@
 /*
  * dec_jobs.inc.cpp -- LDPCdecoder_jobs: a mixed batch of code blocks (every block with its own code and buffers) in one
- * call (included at the end of ldpc_api.cpp, after tb_api.inc.cpp whose per-thread context and plan cache it shares).
+ * call (included at the end of ldpc_api.cpp, after tb_api.inc.cpp whose per-thread context, plan cache and launch cutter it shares).
  * The reference decodes such a mix one LDPCdecoder() call per segment on its worker pool (nr_ulsch_decoding.c:435-468);
  * here the segments of all codes share job-array launches of the decoder kernels, cut by workgroup shape.
  */
@@ -22,7 +22,6 @@ int dec_jobs_enqueue(const nrLDPC_hip_dec_job_t *jobs, uint32_t n, int32_t *n_it
   const t_nrLDPC_dec_params &p0 = jobs[0].params;
   const int out_mode = p0.outMode == nrLDPC_outMode_BIT ? 0 : 1, use_crc = p0.check_crc != nullptr;
   if (!hit) {
-    struct ShapedJob { ldpc_dec_job dj; int kind, threads, lds; double cost; int zc; };
     std::vector<ShapedJob> v(n);
     const bool lat_shape = n <= (uint32_t)G().n_cus;
     const bool classes = tb_classes_enabled() && !lat_shape;
@@ -58,47 +57,7 @@ int dec_jobs_enqueue(const nrLDPC_hip_dec_job_t *jobs, uint32_t n, int32_t *n_it
       v[i].cost = (double)hc.num_llr * p.numMaxIter;
       v[i].zc = (fast && shape.f_mb == 1 && shape.f_rstride == shape.Z + 4 && shape.f_astride == 2 * shape.Z) ? shape.Z : 0;
     }
-    auto per_cu_of = [&](int kind, int threads, int lds) {
-      const int waves = kind == 0 ? 16 : 32;
-      return std::max(1, std::min(waves * 64 / std::max(threads, 64), (160 * 1024) / std::max(lds, 1024)));
-    };
-    auto wg_class = [&](const ShapedJob &j) {
-      if (!classes)
-        return 0;
-      const int per_cu = per_cu_of(j.kind, j.threads, j.lds);
-      return per_cu >= 16 ? 4 : per_cu >= 8 ? 3 : per_cu >= 4 ? 2 : per_cu >= 2 ? 1 : 0;
-    };
-    std::stable_sort(v.begin(), v.end(), [&](const ShapedJob &x, const ShapedJob &y) {
-      const int cx = x.kind * 8 + wg_class(x), cy = y.kind * 8 + wg_class(y);
-      return cx != cy ? cx < cy : (classes && x.cost > y.cost);
-    });
-    std::vector<TbPlan::DecLaunch> dec;
-    for (size_t q = 0; q < v.size();) { /* as in the transport-block chain's plan (tb_api.inc.cpp): class by class, last rounds filled */
-      const int kind = v[q].kind, cls = wg_class(v[q]);
-      size_t e = q;
-      int threads = 64, lds = 0;
-      while (e < v.size() && v[e].kind == kind && wg_class(v[e]) == cls) {
-        threads = std::max(threads, v[e].threads);
-        lds = std::max(lds, v[e].lds);
-        e++;
-      }
-      if (classes && tb_fill_mode()) {
-        const size_t slots = (size_t)G().n_cus * (size_t)per_cu_of(kind, threads, lds);
-        const size_t rem = (e - q) % slots;
-        size_t room = rem ? slots - rem : 0;
-        while (room && e < v.size() && v[e].kind == kind && v[e].threads <= threads && v[e].lds <= lds) {
-          e++;
-          room--;
-        }
-      }
-      TbPlan::DecLaunch dl{kind, q * sizeof(ldpc_dec_job), 0, (uint32_t)(e - q), threads, lds, false};
-      dl.zc = v[q].zc;
-      for (size_t i = q; i < e; i++)
-        if (v[i].zc != dl.zc)
-          dl.zc = 0;
-      dec.push_back(dl);
-      q = e;
-    }
+    std::vector<TbPlan::DecLaunch> dec = tb_cut_dec_launches(v, classes, tb_fill_mode(), G().n_cus); /* (v leaves in launch order) */
     const size_t bytes = align_up((size_t)n * sizeof(ldpc_dec_job), 16);
     if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 || pl.jobs_d.ensure(bytes) != 0)
       return -1;

@@ -64,40 +64,12 @@ extern "C" {
 
 int32_t nrLDPC_hip_dlsch_encode_scrambled(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
 {
-  if (!b || !b->tb || !b->payload || !b->coded)
-    return set_error("null argument");
-  if (b->mem & ~NRLDPC_HIP_MEM_DEVICE)
-    return set_error("encode: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
-  if (scr_check_batch(b, scr, true) != 0)
-    return -1;
-  if (b->n_tb == 0)
-    return ensure_ready();
-  return tb_run_sharded(
-      b, [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) { return tb_tx_enqueue(b, tb0, n, staged, s, scr + tb0); },
-      [&](uint32_t, uint32_t n) { return tb_tx_finish(b, n); });
+  return (tb_check_encode_batch(b) != 0 || scr_check_batch(b, scr, true) != 0) ? -1 : tb_encode_sharded(b, scr, false);
 }
 
 int32_t nrLDPC_hip_ulsch_decode_scrambled(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
 {
-  if (!b || !b->tb || !b->payload || !b->coded)
-    return set_error("null argument");
-  const bool harq_lib = (b->mem & NRLDPC_HIP_MEM_HARQ_LIBRARY) != 0;
-  if ((b->mem & ~(NRLDPC_HIP_MEM_DEVICE | NRLDPC_HIP_MEM_HARQ_DEVICE | NRLDPC_HIP_MEM_HARQ_LIBRARY)) ||
-      (harq_lib && (b->mem & NRLDPC_HIP_MEM_HARQ_DEVICE)))
-    return set_error("decode: invalid mem flags");
-  if ((!b->harq && !harq_lib) || !b->ack || !b->iter_max || b->harq_stride < 66 * 384)
-    return set_error("decode needs harq (stride >= 66*384), ack and iter_max buffers");
-  if (scr_check_batch(b, scr, false) != 0)
-    return -1;
-  if (b->n_tb == 0)
-    return ensure_ready();
-  return tb_run_sharded(
-      b,
-      [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) {
-        return (staged && !(b->mem & NRLDPC_HIP_MEM_DEVICE)) ? tb_rx_enqueue_host(b, tb0, n, scr + tb0)
-                                                              : tb_rx_enqueue(b, tb0, n, staged, s, nullptr, scr + tb0);
-      },
-      [&](uint32_t tb0, uint32_t n) { return tb_rx_finish(b, tb0, n); });
+  return (tb_check_decode_batch(b) != 0 || scr_check_batch(b, scr, false) != 0) ? -1 : tb_decode_sharded(b, scr, false);
 }
 
 int32_t nrLDPC_hip_gold_words(uint32_t c_init, uint32_t first_word, uint32_t n_words, uint32_t *out)

@@ -48,11 +48,14 @@ struct TbPlan {
   DevBuf jobs_d;
   bool valid = false;
   size_t n_seg = 0, n_aux = 0, scratch_top = 0;
-  size_t ext[6] = {0, 0, 0, 0, 0, 0}; /* [lo, hi) of the payload, coded and harq ranges the blocks touch */
+  size_t pay_lo = 0, pay_hi = 0, cod_lo = 0, cod_hi = 0, harq_lo = 0, harq_hi = 0; /* [lo, hi) of the payload, coded and harq (decode) ranges the blocks touch */
   uint32_t rx_lds_elems = 8; /* LDS the de-matching kernel needs per workgroup (int16 slots) */
   bool out_dense = true; /* the blocks' outputs tile their range: one copy back; else one per block (nothing between them is touched) */
-  size_t off[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int threads[4] = {64, 64, 64, 64}, lds[4] = {0, 0, 0, 0};
+  size_t o_tb = 0, o_seg = 0, o_acc = 0; /* where the job arrays start in jobs_d: per TB, per segment, the zeroed per-TB state */
+  size_t o_enc = 0, o_chk = 0, o_scr = 0, o_tickets = 0, o_parts = 0; /* encode */
+  size_t o_iter = 0, o_slots = 0; /* decode */
+  uint32_t max_g = 0; /* encode: the longest block of the scrambling launch (bits, or symbols) */
+  int enc_threads = 64, enc_lds = 0; /* encode */
   size_t n_fast = 0, n_gen = 0; /* encode */
   /* decode: the decoder launches of the batch.  A job-array launch has ONE workgroup shape (threads, LDS) = the maxima over
    * its jobs, so a batch that mixes code sizes is cut into launches by how many workgroups of a job's shape a CU holds
@@ -618,7 +621,7 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     if (tb_upload_jobs(c, pl.jobs_d.p, jobs_bytes, s) != 0)
       return -1;
     pl.n_seg = n_seg; pl.n_aux = cj.size(); pl.scratch_top = ar.top;
-    pl.ext[0] = ex.pay_lo; pl.ext[1] = ex.pay_hi; pl.ext[2] = ex.cod_lo; pl.ext[3] = ex.cod_hi;
+    pl.pay_lo = ex.pay_lo; pl.pay_hi = ex.pay_hi; pl.cod_lo = ex.cod_lo; pl.cod_hi = ex.cod_hi;
     pl.out_dense = ex.cod_sum == ex.cod_hi - ex.cod_lo;
     {
       std::vector<uint64_t> off(ntb);
@@ -629,21 +632,21 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       }
       pl.build_out_runs(off.data(), len.data(), ntb);
     }
-    pl.off[0] = o_tb; pl.off[1] = o_seg; pl.off[2] = o_enc; pl.off[3] = o_chk; pl.off[4] = o_acc; pl.off[5] = o_scr;
-    pl.off[6] = max_g; pl.off[7] = o_tk; pl.off[8] = o_pt;
-    pl.threads[0] = enc_threads; pl.lds[0] = enc_lds;
+    pl.o_tb = o_tb; pl.o_seg = o_seg; pl.o_enc = o_enc; pl.o_chk = o_chk; pl.o_acc = o_acc; pl.o_scr = o_scr;
+    pl.max_g = max_g; pl.o_tickets = o_tk; pl.o_parts = o_pt;
+    pl.enc_threads = enc_threads; pl.enc_lds = enc_lds;
     pl.remember(tbs, ntb, salt, scr, scr_n);
   }
   if (c.scratch.ensure(pl.scratch_top + 16) != 0) /* (+16: the fused kernel reads whole dwords around a segment's bytes) */
     return -1;
   const size_t n_seg = pl.n_seg;
-  const size_t o_tb = pl.off[0], o_seg = pl.off[1], o_enc = pl.off[2], o_chk = pl.off[3], o_acc = pl.off[4];
-  const int enc_threads = pl.threads[0], enc_lds = pl.lds[0];
+  const size_t o_tb = pl.o_tb, o_seg = pl.o_seg, o_enc = pl.o_enc, o_chk = pl.o_chk, o_acc = pl.o_acc;
+  const int enc_threads = pl.enc_threads, enc_lds = pl.enc_lds;
   const uint8_t *payload = b->payload;
   uint8_t *coded = static_cast<uint8_t *>(b->coded);
   uint8_t *out_words = nullptr; /* scrambled, three-kernel path: where the packed words go (coded is then the scratch buffer) */
   if (staged) {
-    const size_t pay_lo = pl.ext[0], pay_n = pl.ext[1] - pl.ext[0], cod_lo = pl.ext[2], cod_n = pl.ext[3] - pl.ext[2];
+    const size_t pay_lo = pl.pay_lo, pay_n = pl.pay_hi - pl.pay_lo, cod_lo = pl.cod_lo, cod_n = pl.cod_hi - pl.cod_lo;
     if (c.io_payload.ensure(pay_n) != 0 || c.io_coded.ensure(cod_n) != 0)
       return -1;
     const uint8_t *pay_src = b->payload + pay_lo;
@@ -678,8 +681,8 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
                                      coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
     else if (scr)
       HIP_TRY(tb_launch_tx_fused_scr(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS + TB_TX_FUSED_SCR_LDS, payload,
-                                     coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.off[7]),
-                                     reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.off[8]), s));
+                                     coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.o_tickets),
+                                     reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.o_parts), s));
     else
       HIP_TRY(tb_launch_tx_fused(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS, payload, coded,
                                  G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
@@ -696,17 +699,17 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
     TB_DEBUG_STAGE("tx: segment + rate matching launches");
   }
   if (sym && !fused) {
-    HIP_TRY(nr_launch_scramble_map_tb(reinterpret_cast<const tb_sym_tb_job *>(pl.jobs_d.p + pl.off[5]), ntb, (uint32_t)pl.off[6], c.scratch.p,
+    HIP_TRY(nr_launch_scramble_map_tb(reinterpret_cast<const tb_sym_tb_job *>(pl.jobs_d.p + pl.o_scr), ntb, pl.max_g, c.scratch.p,
                                       out_words, s));
     TB_DEBUG_STAGE("tx: scrambled, mapped, layer-mapped store");
   } else if (scr && !fused) {
-    HIP_TRY(nr_launch_scramble_bits_tb(reinterpret_cast<const tb_scr_tb_job *>(pl.jobs_d.p + pl.off[5]), ntb, (uint32_t)pl.off[6], c.scratch.p,
+    HIP_TRY(nr_launch_scramble_bits_tb(reinterpret_cast<const tb_scr_tb_job *>(pl.jobs_d.p + pl.o_scr), ntb, pl.max_g, c.scratch.p,
                                        out_words, s));
     TB_DEBUG_STAGE("tx: packed scrambled store");
   }
   if (staged) {
     uint8_t *hc = static_cast<uint8_t *>(b->coded);
-    const size_t cod_lo = pl.ext[2], cod_n = pl.ext[3] - pl.ext[2];
+    const size_t cod_lo = pl.cod_lo, cod_n = pl.cod_hi - pl.cod_lo;
     uint8_t *out = hc; /* where the copies go: the caller's array, or (pageable array) this thread's page-locked mirror of it */
     if (!(b->mem & NRLDPC_HIP_MEM_DEVICE) && needs_bounce(hc + cod_lo, cod_n)) {
       if (c.coded_h.ensure(cod_n) != 0)
@@ -794,6 +797,86 @@ int16_t *harq_lookup(uint64_t id, size_t n, bool fresh, hipStream_t s)
   return e.p;
 }
 
+/* ---- decoder launches of a job array (the transport-block chain's plan and LDPCdecoder_jobs) ---------------------------------
+ * a decoder job with its workgroup shape (kind 0: fast kernel, 1: generic kernel), its cost (the order inside a class) and what
+ * a launch folds over its jobs besides the shape: num_llr, zc (TbPlan::DecLaunch max_llr, zc) */
+struct ShapedJob { ldpc_dec_job dj; int kind, threads, lds; double cost; int num_llr; int zc; };
+
+/* workgroups of a shape that a CU holds */
+int per_cu_of(int kind, int threads, int lds)
+{
+  const int waves = kind == 0 ? 16 : 32; /* the fast kernel's 128 VGPRs allow 16 waves per CU */
+  return std::max(1, std::min(waves * 64 / std::max(threads, 64), (160 * 1024) / std::max(lds, 1024)));
+}
+
+/* A job-array launch has ONE workgroup shape (threads, LDS = the maxima over its jobs), so the jobs
+ * are sorted by kernel and by how many workgroups of their shape a CU holds (1, 2, 4, 8, 16+; the heaviest first inside
+ * a class) and cut into launches class by class -- and a launch whose last workgroup round would be partly empty takes
+ * jobs of the following, smaller classes along until that round is full: they run in slots that would otherwise idle
+ * (a smaller job fits any larger shape), and the smaller classes' own launches get shorter.  Round 3 gave every class
+ * its own launch: 9 workgroup rounds for the 93 small TBS x 64 where 4.3 rounds of work exist.
+ * NRLDPC_HIP_TB_FILL=0 (fill_env): no filling.  `single` leaves sorted into launch order, the order its jobs are uploaded in;
+ * jobs_off counts from the first of them. */
+std::vector<TbPlan::DecLaunch> tb_cut_dec_launches(std::vector<ShapedJob> &single, bool classes, int fill_env, int n_cus)
+{
+  auto wg_class = [&](const ShapedJob &j) {
+    if (!classes)
+      return 0;
+    const int per_cu = per_cu_of(j.kind, j.threads, j.lds);
+    return per_cu >= 16 ? 4 : per_cu >= 8 ? 3 : per_cu >= 4 ? 2 : per_cu >= 2 ? 1 : 0;
+  };
+  std::stable_sort(single.begin(), single.end(), [&](const ShapedJob &x, const ShapedJob &y) {
+    const int cx = x.kind * 8 + wg_class(x), cy = y.kind * 8 + wg_class(y);
+    return cx != cy ? cx < cy : (classes && x.cost > y.cost);
+  });
+  std::vector<TbPlan::DecLaunch> dec;
+  for (size_t q = 0; q < single.size();) {
+    const int kind = single[q].kind, cls = wg_class(single[q]);
+    size_t e = q;
+    int threads = 64, lds = 0;
+    while (e < single.size() && single[e].kind == kind && wg_class(single[e]) == cls) {
+      threads = std::max(threads, single[e].threads);
+      lds = std::max(lds, single[e].lds);
+      e++;
+    }
+    if (classes && fill_env) {
+      const size_t slots = (size_t)n_cus * (size_t)per_cu_of(kind, threads, lds);
+      const size_t rem = (e - q) % slots;
+      size_t room = rem ? slots - rem : 0;
+      /* (jobs of the classes behind: they fit when neither their threads nor their LDS exceed the launch's) */
+      while (room && e < single.size() && single[e].kind == kind && single[e].threads <= threads && single[e].lds <= lds) {
+        e++;
+        room--;
+      }
+    }
+    TbPlan::DecLaunch dl{kind, q * sizeof(ldpc_dec_job), 0, (uint32_t)(e - q), threads, lds, false};
+    dl.all_fused = true;
+    dl.zc = single[q].zc;
+    for (size_t i = q; i < e; i++) {
+      if (single[i].zc != dl.zc)
+        dl.zc = 0;
+      dl.fused |= single[i].dj.seg_idx >= 0;
+      dl.all_fused &= single[i].dj.seg_idx >= 0;
+      dl.mute |= (single[i].dj.crc_type & LDPC_JOB_MUTE_CHECK) != 0;
+      dl.max_llr = std::max(dl.max_llr, single[i].num_llr);
+    }
+    dec.push_back(dl);
+    q = e;
+  }
+  return dec;
+}
+
+/* the rows of a soft-buffer run, piece by piece: fn(first int16 of the piece, its rows).  in_pieces: ~8 MB each (a bounced run:
+ * the CPU works on one piece while the link has another); else the whole run at once */
+template <typename Fn> int tb_harq_run_pieces(const TbPlan::HarqRun &r, uint32_t harq_stride, bool in_pieces, Fn fn)
+{
+  const uint32_t step = in_pieces ? std::max<uint32_t>(1, (uint32_t)(((size_t)8 << 20) / ((size_t)r.width * 2))) : r.rows;
+  for (uint32_t q0 = 0; q0 < r.rows; q0 += step)
+    if (fn(r.first + (size_t)q0 * harq_stride, std::min(step, r.rows - q0)) != 0)
+      return -1;
+  return 0;
+}
+
 /* ---- RX: transport blocks [tb0, tb0+ntb) of b on the current device ----------------------------------------------------
  * staged = the caller's buffers are not this device's memory (host buffers; or, for a device-resident batch cut over
  * several GPUs, the owning GPU's memory): the device works on copies of exactly the ranges its blocks touch.  Two things are
@@ -808,96 +891,159 @@ struct RxHostStage {
   size_t pay_lo, pay_hi;  /* payload bytes the whole call's transport blocks touch */
 };
 
-/* scr != nullptr (nrLDPC_hip_ulsch_decode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the kernels' instantiations that
- * unscramble the LLRs on their way into LDS (tb_rx_core.h) -- the caller's LLR array is only read.
- * sym (with scr; nrLDPC_hip_ulsch_decode_symbols): b->coded holds each block's symbol record instead of its LLRs, in the same
- * G int16 at coded_off -- staging and sharding move it as they move LLRs; the kernels' instantiations that demap it */
-int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
-                  const RxHostStage *st = nullptr, const nrLDPC_hip_tb_scr_t *scr = nullptr, bool sym = false)
-{
-  hipStream_t s;
-  if (tb_begin(s, s_direct, staged) != 0)
-    return -1;
-  if (ntb == 0)
-    return 0;
-  nrLDPC_hip_tb_t *tbs = b->tb + tb0;
-  TbCtx &c = tls_tb;
-  const bool harq_lib = (b->mem & NRLDPC_HIP_MEM_HARQ_LIBRARY) != 0;
-  /* soft buffers usable in place: the caller's device memory on THIS GPU */
-  bool harq_here = false;
-  if (!harq_lib && (!staged || (b->mem & (NRLDPC_HIP_MEM_HARQ_DEVICE | NRLDPC_HIP_MEM_DEVICE)))) {
-    hipPointerAttribute_t at;
-    bool harq_is_dev = false;
-    /* (hipMalloc memory, or hipMallocManaged memory -- the kernels and the peer copies reach both: ADVICE r05) */
-    if (hipPointerGetAttributes(&at, b->harq) == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged)) {
-      harq_is_dev = true;
-      harq_here = at.device == G().id;
-    } else {
-      (void)hipGetLastError();
+/* the job lists of a plan build, on the host until they are uploaded */
+struct RxJobLists {
+  std::vector<tb_rx_tb_job> tbj;
+  std::vector<tb_rx_seg_job> sj, sj_legacy;
+  std::vector<ShapedJob> single; /* segments that get a workgroup of their own */
+  struct MultiCand { const CodeEntry *ce; ldpc_dec_job dj; };
+  std::vector<MultiCand> cands; /* segments that may share a workgroup; group_multi() sorts them into ... */
+  std::vector<ldpc_dec_job> mjobs[2]; std::vector<ldpc_dec_mgroup> mgrp[2]; /* ... groups ([0] / [1]: f_sub = 1 / 4) */
+  int m_threads[2] = {64, 64}, m_lds[2] = {0, 0};
+  bool lat_shape = false, multi_ok = false;
+  void add_single(const CodeEntry *ce, const ldpc_dec_job &dj, uint32_t fused_lds)
+  {
+    const ldpc_code_desc_t &hc = ce->host, &shape = lat_shape ? ce->host_lat : ce->host;
+    const double cost = (double)hc.num_llr * dj.num_max_iter;
+    if (hc.f_ok)
+      single.push_back(ShapedJob{dj, 0, shape.f_n_threads, std::max(shape.f_lds_total, (int)fused_lds), cost, hc.num_llr,
+                                 (shape.f_mb == 1 && shape.f_rstride == shape.Z + 4 && shape.f_astride == 2 * shape.Z) ? shape.Z : 0});
+    else
+      single.push_back(ShapedJob{dj, 1, hc.n_threads, hc.lds_total, cost, hc.num_llr, 0});
+  }
+  /* the candidates, grouped by (code, iteration cap, CRC length and type): a group of at least four shares workgroups of
+   * f_mb * f_sub segments each; smaller groups go back to one workgroup per segment */
+  void group_multi(int multi_mode)
+  {
+    if (multi_mode != 2 && cands.size() < (size_t)TB_MULTI_MIN_PER_CU * (size_t)G().n_cus) { /* they all fit side by side as they are */
+      for (const MultiCand &q : cands)
+        add_single(q.ce, q.dj, 0u);
+      cands.clear();
     }
-    if (!staged && !harq_here)
-      return set_error("soft buffers must be memory of the GPU that holds the LLRs");
-    /* whatever the number of GPUs the call is cut over: a host pointer under this flag would be handed to peer copies */
-    if ((b->mem & NRLDPC_HIP_MEM_HARQ_DEVICE) && !harq_is_dev)
-      return set_error("NRLDPC_HIP_MEM_HARQ_DEVICE: harq is not device memory");
-    /* test hook: logical devices that alias one GPU (the GPU box has one) treat the owner's soft buffers as a peer's */
-    static const bool stage_env = [] { const char *e = getenv("NRLDPC_HIP_TEST_STAGE_HARQ"); return e && atoi(e) != 0; }();
-    if (staged && stage_env)
-      harq_here = false;
-    if ((b->mem & NRLDPC_HIP_MEM_HARQ_DEVICE) && !(b->mem & NRLDPC_HIP_MEM_DEVICE) && !harq_here && g.n_shard == 1)
-      return set_error("NRLDPC_HIP_MEM_HARQ_DEVICE: harq is not device memory of the library's GPU");
+    std::stable_sort(cands.begin(), cands.end(), [](const MultiCand &x, const MultiCand &y) {
+      if (x.ce != y.ce) return x.ce < y.ce;
+      if (x.dj.num_max_iter != y.dj.num_max_iter) return x.dj.num_max_iter < y.dj.num_max_iter;
+      if (x.dj.E != y.dj.E) return x.dj.E < y.dj.E;
+      return (x.dj.crc_type & 3) < (y.dj.crc_type & 3);
+    });
+    for (size_t i0 = 0; i0 < cands.size();) {
+      size_t i1 = i0;
+      while (i1 < cands.size() && cands[i1].ce == cands[i0].ce && cands[i1].dj.num_max_iter == cands[i0].dj.num_max_iter &&
+             cands[i1].dj.E == cands[i0].dj.E && (cands[i1].dj.crc_type & 3) == (cands[i0].dj.crc_type & 3))
+        i1++;
+      const CodeEntry *ce = cands[i0].ce;
+      const ldpc_code_desc_t &hm = ce->host_multi;
+      if (i1 - i0 >= 4) {
+        const int cls = hm.f_sub == 4 ? 1 : 0;
+        const size_t per_wg = (size_t)hm.f_mb * (size_t)hm.f_sub;
+        for (size_t k = i0; k < i1; k += per_wg) {
+          ldpc_dec_mgroup gq;
+          memset(&gq, 0, sizeof(gq));
+          gq.code = ce->dev_multi;
+          gq.first_job = (uint32_t)mjobs[cls].size();
+          gq.n_valid = (uint32_t)std::min(per_wg, i1 - k);
+          gq.num_max_iter = cands[i0].dj.num_max_iter; gq.E = cands[i0].dj.E; gq.crc_type = cands[i0].dj.crc_type & 3;
+          for (size_t q = k; q < k + gq.n_valid; q++)
+            mjobs[cls].push_back(cands[q].dj);
+          mgrp[cls].push_back(gq);
+        }
+        m_threads[cls] = std::max(m_threads[cls], hm.f_n_threads);
+        m_lds[cls] = std::max(m_lds[cls], hm.f_lds_total);
+      } else {
+        for (size_t q = i0; q < i1; q++)
+          add_single(ce, cands[q].dj, 0u);
+      }
+      i0 = i1;
+    }
   }
-  const bool harq_staged = !harq_lib && !harq_here;
-  const int fused_mode = tb_fused_mode();
-  uint64_t salt[3] = {(uint64_t)b->harq_stride | ((uint64_t)(harq_lib ? 2 : (harq_staged ? 1 : 0)) << 32),
-                            (uint64_t)(fused_mode & 0xff) | ((uint64_t)(tb_multi_mode() & 0xff) << 8) | ((uint64_t)tb_classes_enabled() << 16) |
-                                ((uint64_t)(tb_fill_mode() & 0xff) << 24) | ((uint64_t)tb_trunc_enabled() << 32) | ((uint64_t)tb_lrow_enabled() << 33),
-                            harq_lib ? harq_tbl.gen.load() : 0};
-  salt[1] |= scr ? (uint64_t)1 << 34 : 0; /* scrambled (and the scr bytes in the key): never an unscrambled call's plan */
-  salt[1] |= sym ? (uint64_t)1 << 35 : 0; /* symbol records: never an LLR call's plan, nor the reverse */
-  const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
-  TbPlan *hit = c.rx.find(tbs, ntb, salt, scr, scr_n);
-  if (hit) {
-    for (uint32_t i = 0; i < ntb; i++) /* nr_get_R_ldpc_decoder's state leaves the call as it did the first time */
-      tbs[i].llrLen = hit->llr_len[i];
+};
+
+/* the two passes over the cut launches that only the transport-block chain makes */
+void tb_rx_shape_launches(std::vector<TbPlan::DecLaunch> &dec)
+{
+  /* a launch too short to be worth its own tail (one segment's latency at the end of every launch) joins the launch of
+   * the next larger shape before it: the jobs are consecutive */
+  for (size_t k = 1; k < dec.size();) {
+    if (dec[k].kind == dec[k - 1].kind && dec[k].n < (uint32_t)G().n_cus / 2) {
+      dec[k - 1].n += dec[k].n;
+      dec[k - 1].threads = std::max(dec[k - 1].threads, dec[k].threads);
+      dec[k - 1].lds = std::max(dec[k - 1].lds, dec[k].lds);
+      dec[k - 1].fused |= dec[k].fused;
+      dec[k - 1].all_fused &= dec[k].all_fused;
+      dec[k - 1].mute |= dec[k].mute;
+      if (dec[k - 1].zc != dec[k].zc)
+        dec[k - 1].zc = 0;
+      dec[k - 1].max_llr = std::max(dec[k - 1].max_llr, dec[k].max_llr);
+      dec.erase(dec.begin() + (long)k);
+    } else {
+      k++;
+    }
   }
-  TbPlan &pl = hit ? *hit : c.rx.victim();
-  if (!hit) {
-    std::vector<uint8_t> key_tb((const uint8_t *)tbs, (const uint8_t *)tbs + (size_t)ntb * sizeof(nrLDPC_hip_tb_t));
-    std::vector<tb_rx_tb_job> tbj(ntb);
-    std::vector<tb_rx_seg_job> sj, sj_legacy;
-    struct ShapedJob { ldpc_dec_job dj; int kind, threads, lds; double cost; int num_llr; int zc; };
-    std::vector<ShapedJob> single; /* segments that get a workgroup of their own */
+  /* a launch of fused segments keeps the int8 decoder input in LDS when that costs the CU no workgroup (tb_chain.h lrow_off):
+   * no row through memory, no wait for the soft-buffer stores in front of the decoder.  NRLDPC_HIP_TB_LROW=0: off */
+  for (TbPlan::DecLaunch &dl : dec)
+    if (tb_lrow_enabled() && dl.kind == 0 && dl.fused && dl.all_fused) {
+      const int base = (int)align_up((size_t)dl.lds, 16), with_row = base + (int)align_up((size_t)dl.max_llr, 16);
+      if (with_row <= 160 * 1024 && per_cu_of(0, dl.threads, with_row) == per_cu_of(0, dl.threads, dl.lds)) {
+        dl.lrow = (uint32_t)base;
+        dl.lds = with_row;
+      }
+    }
+}
+
+/* what the kernels of a call get: the caller's arrays, or this device's copies of the ranges the blocks touch (biased like the
+ * caller's: job offsets stay the caller's); harq_mirror: the page-locked mirror of a pageable soft-buffer array (harq_bounce) */
+struct RxViews { const int16_t *llr; int16_t *harq; uint8_t *payload, *ack; int32_t *iter_max; bool harq_bounce = false; uint8_t *harq_mirror = nullptr; };
+
+/* one tb_rx_enqueue call: its arguments, the stream it works on, the class of its soft-buffer memory, and its steps in the
+ * order they run.  harq_staged: the soft buffers are neither the library's nor usable in place */
+struct TbRxCall {
+  const nrLDPC_hip_tb_batch_t *b; const uint32_t tb0, ntb; const bool staged; /* as tb_rx_enqueue takes them */
+  const RxHostStage *st; const nrLDPC_hip_tb_scr_t *scr; const bool sym;
+  hipStream_t s; TbCtx &c; /* what tb_begin gave the call */
+  nrLDPC_hip_tb_t *tbs = b->tb + tb0;
+  const bool harq_lib = (b->mem & NRLDPC_HIP_MEM_HARQ_LIBRARY) != 0, to_host = staged && !(b->mem & NRLDPC_HIP_MEM_DEVICE);
+  bool harq_staged = false; /* (classify_harq) */
+  const size_t stride2 = (size_t)b->harq_stride * sizeof(int16_t);
+
+  int classify_harq()
+  {
+    /* soft buffers usable in place: the caller's device memory on THIS GPU */
+    bool harq_here = false;
+    if (!harq_lib && (!staged || (b->mem & (NRLDPC_HIP_MEM_HARQ_DEVICE | NRLDPC_HIP_MEM_DEVICE)))) {
+      hipPointerAttribute_t at;
+      bool harq_is_dev = false;
+      /* (hipMalloc memory, or hipMallocManaged memory -- the kernels and the peer copies reach both: ADVICE r05) */
+      if (hipPointerGetAttributes(&at, b->harq) == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged)) {
+        harq_is_dev = true;
+        harq_here = at.device == G().id;
+      } else {
+        (void)hipGetLastError();
+      }
+      if (!staged && !harq_here)
+        return set_error("soft buffers must be memory of the GPU that holds the LLRs");
+      /* whatever the number of GPUs the call is cut over: a host pointer under this flag would be handed to peer copies */
+      if ((b->mem & NRLDPC_HIP_MEM_HARQ_DEVICE) && !harq_is_dev)
+        return set_error("NRLDPC_HIP_MEM_HARQ_DEVICE: harq is not device memory");
+      /* test hook: logical devices that alias one GPU (the GPU box has one) treat the owner's soft buffers as a peer's */
+      static const bool stage_env = [] { const char *e = getenv("NRLDPC_HIP_TEST_STAGE_HARQ"); return e && atoi(e) != 0; }();
+      if (staged && stage_env)
+        harq_here = false;
+      if ((b->mem & NRLDPC_HIP_MEM_HARQ_DEVICE) && !(b->mem & NRLDPC_HIP_MEM_DEVICE) && !harq_here && g.n_shard == 1)
+        return set_error("NRLDPC_HIP_MEM_HARQ_DEVICE: harq is not device memory of the library's GPU");
+    }
+    harq_staged = !harq_lib && !harq_here;
+    return 0;
+  }
+
+  /* plan, part 1: the per-TB and per-segment jobs, and what the plan keeps of them */
+  int plan_jobs(TbPlan &pl, RxJobLists &jl, int fused_mode)
+  {
+    jl.tbj.resize(ntb);
     Arena ar;
     TbExtent ex;
     std::vector<TbPlan::HarqRun> runs;
     uint32_t rx_lds_elems = 8;
-    /* decoder workgroup shape (ldpc_graph.h): a batch that does not even give every CU one segment wants the latency shape */
-    uint32_t n_seg_total = 0;
-    for (uint32_t i = 0; i < ntb; i++) {
-      nr_hip_seg_t sg;
-      if (tbs[i].A && (tbs[i].BG == 1 || tbs[i].BG == 2) &&
-          nr_hip_segmentation((uint32_t)nr_hip_len_with_crc(1, (int)tbs[i].A), tbs[i].BG, &sg) == 0)
-        n_seg_total += sg.C;
-    }
-    const bool lat_shape = n_seg_total <= (uint32_t)G().n_cus;
-    const int multi_mode = tb_multi_mode();
-    const bool multi_ok = multi_mode != 0 && n_seg_total >= 2u * (uint32_t)G().n_cus;
-    const bool classes = tb_classes_enabled() && !lat_shape;
-    auto add_single = [&](const CodeEntry *ce, const ldpc_dec_job &dj, uint32_t fused_lds) {
-      const ldpc_code_desc_t &hc = ce->host, &shape = lat_shape ? ce->host_lat : ce->host;
-      const double cost = (double)hc.num_llr * dj.num_max_iter;
-      if (hc.f_ok)
-        single.push_back(ShapedJob{dj, 0, shape.f_n_threads, std::max(shape.f_lds_total, (int)fused_lds), cost, hc.num_llr,
-                                   (shape.f_mb == 1 && shape.f_rstride == shape.Z + 4 && shape.f_astride == 2 * shape.Z) ? shape.Z : 0});
-      else
-        single.push_back(ShapedJob{dj, 1, hc.n_threads, hc.lds_total, cost, hc.num_llr, 0});
-    };
-    struct MultiCand { const CodeEntry *ce; ldpc_dec_job dj; };
-    std::vector<MultiCand> cands;
-    std::vector<ldpc_dec_job> mjobs[2];
-    std::vector<ldpc_dec_mgroup> mgrp[2];
-    int m_threads[2] = {64, 64}, m_lds[2] = {0, 0};
     size_t n_legacy_tb = 0;
     bool any_fused = false;
     for (uint32_t i = 0; i < ntb; i++) {
@@ -923,9 +1069,9 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       }
       /* every segment of the block through the fused segment kernel?  (the fast decoder serves the code, and the block's
        * segments are not candidates for shared workgroups) */
-      bool fused_tb = fused_mode != 0 && full->host.f_ok && !(multi_ok && full->dev_multi);
+      bool fused_tb = fused_mode != 0 && full->host.f_ok && !(jl.multi_ok && full->dev_multi);
       const uint32_t cstride = (uint32_t)align_up(out_bytes_of(full->host, 0), 16);
-      tb_rx_tb_job &tj = tbj[i];
+      tb_rx_tb_job &tj = jl.tbj[i];
       memset(&tj, 0, sizeof(tj));
       tj.payload_off = t.payload_off;
       if (!fused_tb) {
@@ -933,7 +1079,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         tj.c_off0 = ar.take((size_t)cstride * sg.C);
       }
       tj.c_stride = cstride;
-      tj.seg0 = (uint32_t)sj.size();
+      tj.seg0 = (uint32_t)jl.sj.size();
       tj.C = sg.C;
       tj.A = t.A;
       tj.B = B;
@@ -1001,7 +1147,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         const uint32_t lds_elems = tb_rx_lds_elems(E, rm.Fin, rm.Ncb);
         if (!fused_tb)
           rx_lds_elems = std::max(rx_lds_elems, lds_elems);
-        j.tb = i; j.r = r; j.iter_idx = (uint32_t)sj.size();
+        j.tb = i; j.r = r; j.iter_idx = (uint32_t)jl.sj.size();
         if (harq_staged) { /* rows of the caller's array that travel: what the kernels look at of this segment's row (tb_rx_geometry) */
           const uint32_t width = std::min<uint32_t>(std::max(rm.Ncb, np_mode), b->harq_stride);
           const size_t first = (size_t)t.harq_off + (size_t)r * b->harq_stride;
@@ -1012,7 +1158,7 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
             runs.push_back(TbPlan::HarqRun{first, 1u, width, t.round != 0});
         }
         ldpc_dec_job dj;
-        dj.code = (hc.f_ok && lat_shape) ? ce->dev_lat : ce->dev;
+        dj.code = (hc.f_ok && jl.lat_shape) ? ce->dev_lat : ce->dev;
         dj.llr_off = j.l_off;
         dj.out_off = tj.c_off0 + (uint64_t)r * cstride;
         dj.num_max_iter = t.numMaxIter;
@@ -1025,191 +1171,27 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
          * look costs two dependent loads per extension item (+1.7 % on that slot). */
         if (t.round != 0 && tb_trunc_enabled())
           dj.crc_type |= LDPC_JOB_MUTE_CHECK;
-        dj.iter_idx = (int32_t)sj.size();
+        dj.iter_idx = (int32_t)jl.sj.size();
         dj.abort_idx = tb_abort_enabled() ? (int32_t)i : -1;
-        dj.seg_idx = fused_tb ? (int32_t)sj.size() : -1;
+        dj.seg_idx = fused_tb ? (int32_t)jl.sj.size() : -1;
         if (dj.E > hc.kb_full * hc.Z || (dj.E & 7))
           return set_error("CRC length outside the code block");
         if (fused_tb && !hc.f_ok)
           return set_error("internal: fused block with a segment outside the fast decoder");
-        if (!fused_tb && multi_ok && ce->dev_multi) /* candidates for a shared workgroup; sorted into groups below */
-          cands.push_back(MultiCand{ce, dj});
+        if (!fused_tb && jl.multi_ok && ce->dev_multi) /* candidates for a shared workgroup; sorted into groups below */
+          jl.cands.push_back(RxJobLists::MultiCand{ce, dj});
         else
-          add_single(ce, dj, fused_tb ? lds_elems * (uint32_t)sizeof(int16_t) + (scr ? TB_RX_SCR_LDS : 0u) : 0u);
-        sj.push_back(j);
+          jl.add_single(ce, dj, fused_tb ? lds_elems * (uint32_t)sizeof(int16_t) + (scr ? TB_RX_SCR_LDS : 0u) : 0u);
+        jl.sj.push_back(j);
         if (!fused_tb)
-          sj_legacy.push_back(j);
+          jl.sj_legacy.push_back(j);
         r_offset += E;
       }
       t.llrLen = llrLen;
     }
-    /* the candidates, grouped by (code, iteration cap, CRC length and type): a group of at least four shares workgroups of
-     * f_mb * f_sub segments each; smaller groups go back to one workgroup per segment */
-    if (multi_mode != 2 && cands.size() < (size_t)TB_MULTI_MIN_PER_CU * (size_t)G().n_cus) { /* they all fit side by side as they are */
-      for (const MultiCand &q : cands)
-        add_single(q.ce, q.dj, 0u);
-      cands.clear();
-    }
-    std::stable_sort(cands.begin(), cands.end(), [](const MultiCand &x, const MultiCand &y) {
-      if (x.ce != y.ce) return x.ce < y.ce;
-      if (x.dj.num_max_iter != y.dj.num_max_iter) return x.dj.num_max_iter < y.dj.num_max_iter;
-      if (x.dj.E != y.dj.E) return x.dj.E < y.dj.E;
-      return (x.dj.crc_type & 3) < (y.dj.crc_type & 3);
-    });
-    for (size_t i0 = 0; i0 < cands.size();) {
-      size_t i1 = i0;
-      while (i1 < cands.size() && cands[i1].ce == cands[i0].ce && cands[i1].dj.num_max_iter == cands[i0].dj.num_max_iter &&
-             cands[i1].dj.E == cands[i0].dj.E && (cands[i1].dj.crc_type & 3) == (cands[i0].dj.crc_type & 3))
-        i1++;
-      const CodeEntry *ce = cands[i0].ce;
-      const ldpc_code_desc_t &hm = ce->host_multi;
-      if (i1 - i0 >= 4) {
-        const int cls = hm.f_sub == 4 ? 1 : 0;
-        const size_t per_wg = (size_t)hm.f_mb * (size_t)hm.f_sub;
-        for (size_t k = i0; k < i1; k += per_wg) {
-          ldpc_dec_mgroup gq;
-          memset(&gq, 0, sizeof(gq));
-          gq.code = ce->dev_multi;
-          gq.first_job = (uint32_t)mjobs[cls].size();
-          gq.n_valid = (uint32_t)std::min(per_wg, i1 - k);
-          gq.num_max_iter = cands[i0].dj.num_max_iter; gq.E = cands[i0].dj.E; gq.crc_type = cands[i0].dj.crc_type & 3;
-          for (size_t q = k; q < k + gq.n_valid; q++)
-            mjobs[cls].push_back(cands[q].dj);
-          mgrp[cls].push_back(gq);
-        }
-        m_threads[cls] = std::max(m_threads[cls], hm.f_n_threads);
-        m_lds[cls] = std::max(m_lds[cls], hm.f_lds_total);
-      } else {
-        for (size_t q = i0; q < i1; q++)
-          add_single(ce, cands[q].dj, 0u);
-      }
-      i0 = i1;
-    }
-    /* Decoder launches.  A job-array launch has ONE workgroup shape (threads, LDS = the maxima over its jobs), so the jobs
-     * are sorted by kernel and by how many workgroups of their shape a CU holds (1, 2, 4, 8, 16+; the heaviest first inside
-     * a class) and cut into launches class by class -- and a launch whose last workgroup round would be partly empty takes
-     * jobs of the following, smaller classes along until that round is full: they run in slots that would otherwise idle
-     * (a smaller job fits any larger shape), and the smaller classes' own launches get shorter.  Round 3 gave every class
-     * its own launch: 9 workgroup rounds for the 93 small TBS x 64 where 4.3 rounds of work exist.
-     * NRLDPC_HIP_TB_FILL=0: no filling. */
-    const int fill_env = tb_fill_mode();
-    auto per_cu_of = [&](int kind, int threads, int lds) {
-      const int waves = kind == 0 ? 16 : 32; /* the fast kernel's 128 VGPRs allow 16 waves per CU */
-      return std::max(1, std::min(waves * 64 / std::max(threads, 64), (160 * 1024) / std::max(lds, 1024)));
-    };
-    auto wg_class = [&](const ShapedJob &j) {
-      if (!classes)
-        return 0;
-      const int per_cu = per_cu_of(j.kind, j.threads, j.lds);
-      return per_cu >= 16 ? 4 : per_cu >= 8 ? 3 : per_cu >= 4 ? 2 : per_cu >= 2 ? 1 : 0;
-    };
-    std::stable_sort(single.begin(), single.end(), [&](const ShapedJob &x, const ShapedJob &y) {
-      const int cx = x.kind * 8 + wg_class(x), cy = y.kind * 8 + wg_class(y);
-      return cx != cy ? cx < cy : (classes && x.cost > y.cost);
-    });
-    std::vector<ldpc_dec_job> single_jobs(single.size());
-    for (size_t q = 0; q < single.size(); q++)
-      single_jobs[q] = single[q].dj;
-    std::vector<TbPlan::DecLaunch> dec;
-    for (size_t q = 0; q < single.size();) {
-      const int kind = single[q].kind, cls = wg_class(single[q]);
-      size_t e = q;
-      int threads = 64, lds = 0;
-      while (e < single.size() && single[e].kind == kind && wg_class(single[e]) == cls) {
-        threads = std::max(threads, single[e].threads);
-        lds = std::max(lds, single[e].lds);
-        e++;
-      }
-      if (classes && fill_env) {
-        const size_t slots = (size_t)G().n_cus * (size_t)per_cu_of(kind, threads, lds);
-        const size_t rem = (e - q) % slots;
-        size_t room = rem ? slots - rem : 0;
-        /* (jobs of the classes behind: they fit when neither their threads nor their LDS exceed the launch's) */
-        while (room && e < single.size() && single[e].kind == kind && single[e].threads <= threads && single[e].lds <= lds) {
-          e++;
-          room--;
-        }
-      }
-      TbPlan::DecLaunch dl{kind, q * sizeof(ldpc_dec_job), 0, (uint32_t)(e - q), threads, lds, false};
-      dl.all_fused = true;
-      dl.zc = single[q].zc;
-      for (size_t i = q; i < e; i++) {
-        if (single[i].zc != dl.zc)
-          dl.zc = 0;
-        dl.fused |= single[i].dj.seg_idx >= 0;
-        dl.all_fused &= single[i].dj.seg_idx >= 0;
-        dl.mute |= (single[i].dj.crc_type & LDPC_JOB_MUTE_CHECK) != 0;
-        dl.max_llr = std::max(dl.max_llr, single[i].num_llr);
-      }
-      dec.push_back(dl);
-      q = e;
-    }
-    const size_t n_seg = sj.size();
-    const size_t o_tb = 0, o_seg = align_up(tbj.size() * sizeof(tb_rx_tb_job), 16),
-                 o_leg = o_seg + align_up(n_seg * sizeof(tb_rx_seg_job), 16),
-                 o_single = o_leg + align_up(sj_legacy.size() * sizeof(tb_rx_seg_job), 16),
-                 o_mj0 = o_single + align_up(single_jobs.size() * sizeof(ldpc_dec_job), 16),
-                 o_mg0 = o_mj0 + align_up(mjobs[0].size() * sizeof(ldpc_dec_job), 16),
-                 o_mj1 = o_mg0 + align_up(mgrp[0].size() * sizeof(ldpc_dec_mgroup), 16),
-                 o_mg1 = o_mj1 + align_up(mjobs[1].size() * sizeof(ldpc_dec_job), 16),
-                 o_acc = o_mg1 + align_up(mgrp[1].size() * sizeof(ldpc_dec_mgroup), 16), /* per TB: CRC accumulators, abort
-                                                                                            flags, finished-segment counters:
-                                                                                            uploaded as zeros, left zero */
-                 o_slots = o_acc + align_up((size_t)ntb * 4 * sizeof(uint32_t), 16), /* (+ per TB: generation) */
-                 jobs_bytes = o_slots + align_up(n_seg * sizeof(uint64_t), 16), /* per segment: the fused kernel's slots */
-                 o_iter = jobs_bytes; /* n_iter lives behind the uploaded part in the same device buffer */
-    if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_bytes) != 0 ||
-        pl.jobs_d.ensure(o_iter + n_seg * sizeof(int32_t)) != 0)
-      return -1;
-    memset(c.jobs_h.p + o_acc, 0, jobs_bytes - o_acc);
-    memcpy(c.jobs_h.p + o_tb, tbj.data(), tbj.size() * sizeof(tb_rx_tb_job));
-    memcpy(c.jobs_h.p + o_seg, sj.data(), n_seg * sizeof(tb_rx_seg_job));
-    memcpy(c.jobs_h.p + o_leg, sj_legacy.data(), sj_legacy.size() * sizeof(tb_rx_seg_job));
-    memcpy(c.jobs_h.p + o_single, single_jobs.data(), single_jobs.size() * sizeof(ldpc_dec_job));
-    memcpy(c.jobs_h.p + o_mj0, mjobs[0].data(), mjobs[0].size() * sizeof(ldpc_dec_job));
-    memcpy(c.jobs_h.p + o_mg0, mgrp[0].data(), mgrp[0].size() * sizeof(ldpc_dec_mgroup));
-    memcpy(c.jobs_h.p + o_mj1, mjobs[1].data(), mjobs[1].size() * sizeof(ldpc_dec_job));
-    memcpy(c.jobs_h.p + o_mg1, mgrp[1].data(), mgrp[1].size() * sizeof(ldpc_dec_mgroup));
-    if (tb_upload_jobs(c, pl.jobs_d.p, jobs_bytes, s) != 0)
-      return -1;
-    /* a launch too short to be worth its own tail (one segment's latency at the end of every launch) joins the launch of
-     * the next larger shape before it: the jobs are consecutive */
-    for (size_t k = 1; k < dec.size();) {
-      if (dec[k].kind == dec[k - 1].kind && dec[k].n < (uint32_t)G().n_cus / 2) {
-        dec[k - 1].n += dec[k].n;
-        dec[k - 1].threads = std::max(dec[k - 1].threads, dec[k].threads);
-        dec[k - 1].lds = std::max(dec[k - 1].lds, dec[k].lds);
-        dec[k - 1].fused |= dec[k].fused;
-        dec[k - 1].all_fused &= dec[k].all_fused;
-        dec[k - 1].mute |= dec[k].mute;
-        if (dec[k - 1].zc != dec[k].zc)
-          dec[k - 1].zc = 0;
-        dec[k - 1].max_llr = std::max(dec[k - 1].max_llr, dec[k].max_llr);
-        dec.erase(dec.begin() + (long)k);
-      } else {
-        k++;
-      }
-    }
-    for (TbPlan::DecLaunch &dl : dec)
-      dl.jobs_off += o_single;
-    /* a launch of fused segments keeps the int8 decoder input in LDS when that costs the CU no workgroup (tb_chain.h lrow_off):
-     * no row through memory, no wait for the soft-buffer stores in front of the decoder.  NRLDPC_HIP_TB_LROW=0: off */
-    for (TbPlan::DecLaunch &dl : dec)
-      if (tb_lrow_enabled() && dl.kind == 0 && dl.fused && dl.all_fused) {
-        const int base = (int)align_up((size_t)dl.lds, 16), with_row = base + (int)align_up((size_t)dl.max_llr, 16);
-        if (with_row <= 160 * 1024 && per_cu_of(0, dl.threads, with_row) == per_cu_of(0, dl.threads, dl.lds)) {
-          dl.lrow = (uint32_t)base;
-          dl.lds = with_row;
-        }
-      }
-    if (!mgrp[0].empty())
-      dec.push_back(TbPlan::DecLaunch{2, o_mj0, o_mg0, (uint32_t)mgrp[0].size(), m_threads[0], m_lds[0], false});
-    if (!mgrp[1].empty())
-      dec.push_back(TbPlan::DecLaunch{3, o_mj1, o_mg1, (uint32_t)mgrp[1].size(), m_threads[1], m_lds[1], false});
-    pl.dec.swap(dec);
-    pl.n_seg = n_seg; pl.scratch_top = ar.top;
-    pl.ext[0] = ex.pay_lo; pl.ext[1] = ex.pay_hi; pl.ext[2] = ex.cod_lo; pl.ext[3] = ex.cod_hi;
-    pl.ext[4] = harq_lib ? 0 : ex.harq_lo; pl.ext[5] = harq_lib ? 0 : ex.harq_hi;
+    pl.n_seg = jl.sj.size(); pl.scratch_top = ar.top;
+    pl.pay_lo = ex.pay_lo; pl.pay_hi = ex.pay_hi; pl.cod_lo = ex.cod_lo; pl.cod_hi = ex.cod_hi;
+    pl.harq_lo = harq_lib ? 0 : ex.harq_lo; pl.harq_hi = harq_lib ? 0 : ex.harq_hi;
     pl.out_dense = ex.pay_sum == ex.pay_hi - ex.pay_lo;
     {
       std::vector<uint64_t> off(ntb);
@@ -1221,270 +1203,343 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       pl.build_out_runs(off.data(), len.data(), ntb);
     }
     pl.harq_runs.swap(runs);
-    pl.off[0] = o_tb; pl.off[1] = o_seg; pl.off[4] = o_iter; pl.off[5] = o_acc; pl.off[6] = o_slots;
-    pl.legacy_off = o_leg; pl.n_legacy_seg = sj_legacy.size(); pl.n_legacy_tb = n_legacy_tb; pl.any_fused = any_fused;
+    pl.n_legacy_seg = jl.sj_legacy.size(); pl.n_legacy_tb = n_legacy_tb; pl.any_fused = any_fused;
     pl.rx_lds_elems = rx_lds_elems;
     pl.llr_len.resize(ntb);
     for (uint32_t i = 0; i < ntb; i++)
       pl.llr_len[i] = tbs[i].llrLen;
+    return 0;
+  }
+
+  /* plan, part 2: the job buffer's layout, its upload, and the launches' places in it */
+  int upload_jobs(TbPlan &pl, const RxJobLists &jl, std::vector<TbPlan::DecLaunch> &dec)
+  {
+    std::vector<ldpc_dec_job> single_jobs(jl.single.size());
+    for (size_t q = 0; q < jl.single.size(); q++)
+      single_jobs[q] = jl.single[q].dj;
+    const size_t n_seg = jl.sj.size();
+    const size_t o_tb = 0, o_seg = align_up(jl.tbj.size() * sizeof(tb_rx_tb_job), 16),
+                 o_leg = o_seg + align_up(n_seg * sizeof(tb_rx_seg_job), 16),
+                 o_single = o_leg + align_up(jl.sj_legacy.size() * sizeof(tb_rx_seg_job), 16),
+                 o_mj0 = o_single + align_up(single_jobs.size() * sizeof(ldpc_dec_job), 16),
+                 o_mg0 = o_mj0 + align_up(jl.mjobs[0].size() * sizeof(ldpc_dec_job), 16),
+                 o_mj1 = o_mg0 + align_up(jl.mgrp[0].size() * sizeof(ldpc_dec_mgroup), 16),
+                 o_mg1 = o_mj1 + align_up(jl.mjobs[1].size() * sizeof(ldpc_dec_job), 16),
+                 o_acc = o_mg1 + align_up(jl.mgrp[1].size() * sizeof(ldpc_dec_mgroup), 16), /* per TB: CRC accumulators, abort
+                                                                                            flags, finished-segment counters:
+                                                                                            uploaded as zeros, left zero */
+                 o_slots = o_acc + align_up((size_t)ntb * 4 * sizeof(uint32_t), 16), /* (+ per TB: generation) */
+                 jobs_bytes = o_slots + align_up(n_seg * sizeof(uint64_t), 16), /* per segment: the fused kernel's slots */
+                 o_iter = jobs_bytes; /* n_iter lives behind the uploaded part in the same device buffer */
+    if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_bytes) != 0 ||
+        pl.jobs_d.ensure(o_iter + n_seg * sizeof(int32_t)) != 0)
+      return -1;
+    memset(c.jobs_h.p + o_acc, 0, jobs_bytes - o_acc);
+    memcpy(c.jobs_h.p + o_tb, jl.tbj.data(), jl.tbj.size() * sizeof(tb_rx_tb_job));
+    memcpy(c.jobs_h.p + o_seg, jl.sj.data(), n_seg * sizeof(tb_rx_seg_job));
+    memcpy(c.jobs_h.p + o_leg, jl.sj_legacy.data(), jl.sj_legacy.size() * sizeof(tb_rx_seg_job));
+    memcpy(c.jobs_h.p + o_single, single_jobs.data(), single_jobs.size() * sizeof(ldpc_dec_job));
+    memcpy(c.jobs_h.p + o_mj0, jl.mjobs[0].data(), jl.mjobs[0].size() * sizeof(ldpc_dec_job));
+    memcpy(c.jobs_h.p + o_mg0, jl.mgrp[0].data(), jl.mgrp[0].size() * sizeof(ldpc_dec_mgroup));
+    memcpy(c.jobs_h.p + o_mj1, jl.mjobs[1].data(), jl.mjobs[1].size() * sizeof(ldpc_dec_job));
+    memcpy(c.jobs_h.p + o_mg1, jl.mgrp[1].data(), jl.mgrp[1].size() * sizeof(ldpc_dec_mgroup));
+    if (tb_upload_jobs(c, pl.jobs_d.p, jobs_bytes, s) != 0)
+      return -1;
+    for (TbPlan::DecLaunch &dl : dec)
+      dl.jobs_off += o_single;
+    if (!jl.mgrp[0].empty())
+      dec.push_back(TbPlan::DecLaunch{2, o_mj0, o_mg0, (uint32_t)jl.mgrp[0].size(), jl.m_threads[0], jl.m_lds[0], false});
+    if (!jl.mgrp[1].empty())
+      dec.push_back(TbPlan::DecLaunch{3, o_mj1, o_mg1, (uint32_t)jl.mgrp[1].size(), jl.m_threads[1], jl.m_lds[1], false});
+    pl.dec.swap(dec);
+    pl.o_tb = o_tb; pl.o_seg = o_seg; pl.o_iter = o_iter; pl.o_acc = o_acc; pl.o_slots = o_slots; pl.legacy_off = o_leg;
+    return 0;
+  }
+
+  /* a plan for the call's descriptors in `pl` (a cache slot given up for it: invalid until the last line) */
+  int build_plan(TbPlan &pl, uint64_t salt[3], int fused_mode, size_t scr_n)
+  {
+    std::vector<uint8_t> key_tb((const uint8_t *)tbs, (const uint8_t *)tbs + (size_t)ntb * sizeof(nrLDPC_hip_tb_t));
+    RxJobLists jl;
+    /* decoder workgroup shape (ldpc_graph.h): a batch that does not even give every CU one segment wants the latency shape */
+    uint32_t n_seg_total = 0;
+    for (uint32_t i = 0; i < ntb; i++) {
+      nr_hip_seg_t sg;
+      if (tbs[i].A && (tbs[i].BG == 1 || tbs[i].BG == 2) &&
+          nr_hip_segmentation((uint32_t)nr_hip_len_with_crc(1, (int)tbs[i].A), tbs[i].BG, &sg) == 0)
+        n_seg_total += sg.C;
+    }
+    jl.lat_shape = n_seg_total <= (uint32_t)G().n_cus;
+    const int multi_mode = tb_multi_mode();
+    jl.multi_ok = multi_mode != 0 && n_seg_total >= 2u * (uint32_t)G().n_cus;
+    const bool classes = tb_classes_enabled() && !jl.lat_shape;
+    if (plan_jobs(pl, jl, fused_mode) != 0)
+      return -1;
+    jl.group_multi(multi_mode);
+    std::vector<TbPlan::DecLaunch> dec = tb_cut_dec_launches(jl.single, classes, tb_fill_mode(), G().n_cus);
+    tb_rx_shape_launches(dec);
+    if (upload_jobs(pl, jl, dec) != 0)
+      return -1;
     /* the key is the descriptor array as it ARRIVED (llrLen is updated by the loop above); the library's soft buffers as
      * they are now, after this build's allocations */
     salt[2] = harq_lib ? harq_tbl.gen.load() : 0;
     pl.remember(key_tb.data(), ntb, salt, scr, scr_n);
+    return 0;
   }
-  if (c.scratch.ensure(pl.scratch_top) != 0)
-    return -1;
-  const size_t n_seg = pl.n_seg;
-  const size_t o_tb = pl.off[0], o_seg = pl.off[1], o_iter = pl.off[4], o_acc = pl.off[5];
-  int32_t *d_iter = reinterpret_cast<int32_t *>(pl.jobs_d.p + o_iter);
-  uint8_t *payload = b->payload;
-  const int16_t *llr = static_cast<const int16_t *>(b->coded);
-  int16_t *harq = harq_lib ? nullptr : b->harq;
-  uint8_t *ack = b->ack + tb0;
-  int32_t *iter_max = b->iter_max + tb0;
-  const size_t stride2 = (size_t)b->harq_stride * sizeof(int16_t);
-  const bool to_host = staged && !(b->mem & NRLDPC_HIP_MEM_DEVICE);
-  const bool payload_direct = false;
-  bool harq_bounce = false;
-  uint8_t *harq_mirror = nullptr;
-  if (staged) {
-    const size_t pay_lo = pl.ext[0], pay_n = pl.ext[1] - pl.ext[0], cod_lo = pl.ext[2], cod_n = pl.ext[3] - pl.ext[2];
-    /* LLRs in page-locked host memory are read in place (the device address of the caller's array); anything else is copied */
-    const int16_t *pulled = nullptr;
-    if (st && st->llr_dev) {
-      llr = st->llr_dev;
-    } else {
-      if (to_host && host_range_is_partly_pinned(static_cast<const int16_t *>(b->coded) + cod_lo, cod_n * sizeof(int16_t)))
-        return set_error("coded: the array is page-locked in part only (register the whole range the call reads, or none of it)");
-      if (to_host && !(st && st->no_pull) && tb_pull_mode() != 0 &&
-          host_ptr_is_pinned(static_cast<const int16_t *>(b->coded) + cod_lo, cod_n * sizeof(int16_t))) {
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, b->coded, 0) == hipSuccess)
-          pulled = static_cast<const int16_t *>(dp);
-        else
-          (void)hipGetLastError();
-      }
-      if (pulled) {
-        llr = pulled;
+
+  /* stage in: v arrives as the caller's arrays; whatever of them is not this device's memory and not read in place is copied */
+  int stage_in(const TbPlan &pl, RxViews &v)
+  {
+    auto &[llr, harq, payload, ack, iter_max, harq_bounce, harq_mirror] = v;
+    if (staged) {
+      const size_t pay_lo = pl.pay_lo, pay_n = pl.pay_hi - pl.pay_lo, cod_lo = pl.cod_lo, cod_n = pl.cod_hi - pl.cod_lo;
+      /* LLRs in page-locked host memory are read in place (the device address of the caller's array); anything else is copied */
+      const int16_t *pulled = nullptr;
+      if (st && st->llr_dev) {
+        llr = st->llr_dev;
       } else {
-        if (c.io_coded.ensure(cod_n * 2) != 0)
-          return -1;
-        const void *cod_src = static_cast<const int16_t *>(b->coded) + cod_lo;
-        if (to_host && needs_bounce(cod_src, cod_n * 2)) { /* pageable: bounced (TbCtx::fin_copies) */
-          if (c.coded_h.ensure(cod_n * 2) != 0)
+        if (to_host && host_range_is_partly_pinned(static_cast<const int16_t *>(b->coded) + cod_lo, cod_n * sizeof(int16_t)))
+          return set_error("coded: the array is page-locked in part only (register the whole range the call reads, or none of it)");
+        if (to_host && !(st && st->no_pull) && tb_pull_mode() != 0 &&
+            host_ptr_is_pinned(static_cast<const int16_t *>(b->coded) + cod_lo, cod_n * sizeof(int16_t))) {
+          void *dp = nullptr;
+          if (hipHostGetDevicePointer(&dp, b->coded, 0) == hipSuccess)
+            pulled = static_cast<const int16_t *>(dp);
+          else
+            (void)hipGetLastError();
+        }
+        if (pulled) {
+          llr = pulled;
+        } else {
+          if (c.io_coded.ensure(cod_n * 2) != 0)
             return -1;
-          bounce_copy(c.coded_h.p, cod_n * 2, cod_src, cod_n * 2, cod_n * 2, 1);
-          cod_src = c.coded_h.p;
-        }
-        HIP_TRY(hipMemcpyAsync(c.io_coded.p, cod_src, cod_n * 2, hipMemcpyDefault, s));
-        llr = reinterpret_cast<const int16_t *>(c.io_coded.p) - cod_lo;
-      }
-    }
-    if (harq_staged) {
-      const size_t harq_lo = pl.ext[4], harq_n = pl.ext[5] - pl.ext[4];
-      if (c.io_harq.ensure(harq_n * 2) != 0)
-        return -1;
-      /* a pageable array of the caller's is mirrored in page-locked memory: rows that travel up are copied into the mirror
-       * by the CPU first, rows that come back are handed over by tb_rx_finish (TbCtx::fin_copies) */
-      /* ... and only a HOST array is: device soft buffers of another GPU (a call cut over several GPUs, this part not the
-       * owner's) take the strided copies directly -- peer copies --, the CPU must never touch them */
-      const bool harq_is_host = !(b->mem & (NRLDPC_HIP_MEM_HARQ_DEVICE | NRLDPC_HIP_MEM_DEVICE));
-      harq_bounce = to_host && harq_is_host && needs_bounce(b->harq + harq_lo, harq_n * 2);
-      if (harq_bounce) { /* this piece's share of the mirror (growing it parks the old area: earlier pieces keep theirs) */
-        const size_t at = align_up(c.harq_h_used, 64);
-        if (c.harq_h.ensure(at + harq_n * 2) != 0)
-          return -1;
-        harq_mirror = c.harq_h.p + at;
-        c.harq_h_used = at + harq_n * 2;
-      }
-      const int16_t *harq_src = harq_bounce ? reinterpret_cast<const int16_t *>(harq_mirror) - harq_lo : b->harq;
-      for (const TbPlan::HarqRun &r : pl.harq_runs)
-        if (r.upload) {
-          /* a bounced run goes up in pieces of ~8 MB: the CPU fills the mirror for piece k + 1 while the link takes piece k */
-          const uint32_t step = harq_bounce ? std::max<uint32_t>(1, (uint32_t)(((size_t)8 << 20) / ((size_t)r.width * 2))) : r.rows;
-          for (uint32_t q0 = 0; q0 < r.rows; q0 += step) {
-            const uint32_t nq = std::min(step, r.rows - q0);
-            const size_t first = r.first + (size_t)q0 * b->harq_stride;
-            if (harq_bounce)
-              bounce_copy(harq_mirror + (first - harq_lo) * 2, stride2, b->harq + first, stride2, (size_t)r.width * 2, nq);
-            HIP_TRY(hipMemcpy2DAsync(c.io_harq.p + (first - harq_lo) * 2, stride2, harq_src + first, stride2, (size_t)r.width * 2, nq,
-                                     hipMemcpyDefault, s));
+          const void *cod_src = static_cast<const int16_t *>(b->coded) + cod_lo;
+          if (to_host && needs_bounce(cod_src, cod_n * 2)) { /* pageable: bounced (TbCtx::fin_copies) */
+            if (c.coded_h.ensure(cod_n * 2) != 0)
+              return -1;
+            bounce_copy(c.coded_h.p, cod_n * 2, cod_src, cod_n * 2, cod_n * 2, 1);
+            cod_src = c.coded_h.p;
           }
+          HIP_TRY(hipMemcpyAsync(c.io_coded.p, cod_src, cod_n * 2, hipMemcpyDefault, s));
+          llr = reinterpret_cast<const int16_t *>(c.io_coded.p) - cod_lo;
         }
-      harq = reinterpret_cast<int16_t *>(c.io_harq.p) - harq_lo;
-    }
-    if (to_host) {
-      /* verdicts: straight into this thread's page-locked result area (device-mapped; tb_rx_finish hands them over) -- no
-       * copy engine for a few bytes; payload: into the caller's array when that is page-locked too, else via a device copy */
-      const uint32_t call_tb0 = st ? st->call_tb0 : tb0, call_ntb = st ? st->call_ntb : ntb;
-      if (c.small_h.ensure((size_t)call_ntb * 8 + 64) != 0)
-        return -1;
-      void *dp = nullptr;
-      HIP_TRY(hipHostGetDevicePointer(&dp, c.small_h.p, 0));
-      iter_max = static_cast<int32_t *>(dp) + (tb0 - call_tb0);
-      ack = static_cast<uint8_t *>(dp) + (size_t)call_ntb * 4 + (tb0 - call_tb0);
-      /* payload: into device memory, then one copy per piece into PAGE-LOCKED host memory -- the caller's array when it is
-       * page-locked, else this thread's staging area, handed over by tb_rx_finish.  (A device -> host copy into pageable
-       * memory makes the host wait for the piece before it can enqueue the next one; and letting the kernels store the
-       * payload bytes over the link themselves was measured at 48 ms per slot: 4-byte writes, each one waited for.) */
-      const size_t lo = st ? st->pay_lo : pay_lo, n = st ? st->pay_hi - st->pay_lo : pay_n;
-      if (!needs_bounce(b->payload + lo, n)) {
-        c.fin_pay_n = 0;
-      } else {
-        (void)hipGetLastError();
-        if (c.payload_h.ensure(n) != 0)
-          return -1;
-        c.fin_pay_lo = lo;
-        c.fin_pay_n = n;
       }
-    } else {
-      if (c.io_small.ensure((size_t)ntb * 8 + 64) != 0)
-        return -1;
-      iter_max = reinterpret_cast<int32_t *>(c.io_small.p);
-      ack = c.io_small.p + (size_t)ntb * 4;
-    }
-    if (!payload_direct) {
+      if (harq_staged) {
+        const size_t harq_lo = pl.harq_lo, harq_n = pl.harq_hi - pl.harq_lo;
+        if (c.io_harq.ensure(harq_n * 2) != 0)
+          return -1;
+        /* a pageable array of the caller's is mirrored in page-locked memory: rows that travel up are copied into the mirror
+         * by the CPU first, rows that come back are handed over by tb_rx_finish (TbCtx::fin_copies) */
+        /* ... and only a HOST array is: device soft buffers of another GPU (a call cut over several GPUs, this part not the
+         * owner's) take the strided copies directly -- peer copies --, the CPU must never touch them */
+        const bool harq_is_host = !(b->mem & (NRLDPC_HIP_MEM_HARQ_DEVICE | NRLDPC_HIP_MEM_DEVICE));
+        harq_bounce = to_host && harq_is_host && needs_bounce(b->harq + harq_lo, harq_n * 2);
+        if (harq_bounce) { /* this piece's share of the mirror (growing it parks the old area: earlier pieces keep theirs) */
+          const size_t at = align_up(c.harq_h_used, 64);
+          if (c.harq_h.ensure(at + harq_n * 2) != 0)
+            return -1;
+          harq_mirror = c.harq_h.p + at;
+          c.harq_h_used = at + harq_n * 2;
+        }
+        const int16_t *harq_src = harq_bounce ? reinterpret_cast<const int16_t *>(harq_mirror) - harq_lo : b->harq;
+        for (const TbPlan::HarqRun &r : pl.harq_runs)
+          if (r.upload) {
+            /* a bounced run goes up in pieces of ~8 MB: the CPU fills the mirror for piece k + 1 while the link takes piece k */
+            if (tb_harq_run_pieces(r, b->harq_stride, v.harq_bounce, [&](size_t first, uint32_t nq) -> int {
+                  if (v.harq_bounce)
+                    bounce_copy(v.harq_mirror + (first - harq_lo) * 2, stride2, b->harq + first, stride2, (size_t)r.width * 2, nq);
+                  HIP_TRY(hipMemcpy2DAsync(c.io_harq.p + (first - harq_lo) * 2, stride2, harq_src + first, stride2, (size_t)r.width * 2, nq,
+                                           hipMemcpyDefault, s));
+                  return 0;
+                }) != 0)
+              return -1;
+          }
+        harq = reinterpret_cast<int16_t *>(c.io_harq.p) - harq_lo;
+      }
+      if (to_host) {
+        /* verdicts: straight into this thread's page-locked result area (device-mapped; tb_rx_finish hands them over) -- no
+         * copy engine for a few bytes; payload: into the caller's array when that is page-locked too, else via a device copy */
+        const uint32_t call_tb0 = st ? st->call_tb0 : tb0, call_ntb = st ? st->call_ntb : ntb;
+        if (c.small_h.ensure((size_t)call_ntb * 8 + 64) != 0)
+          return -1;
+        void *dp = nullptr;
+        HIP_TRY(hipHostGetDevicePointer(&dp, c.small_h.p, 0));
+        iter_max = static_cast<int32_t *>(dp) + (tb0 - call_tb0);
+        ack = static_cast<uint8_t *>(dp) + (size_t)call_ntb * 4 + (tb0 - call_tb0);
+        /* payload: into device memory, then one copy per piece into PAGE-LOCKED host memory -- the caller's array when it is
+         * page-locked, else this thread's staging area, handed over by tb_rx_finish.  (A device -> host copy into pageable
+         * memory makes the host wait for the piece before it can enqueue the next one; and letting the kernels store the
+         * payload bytes over the link themselves was measured at 48 ms per slot: 4-byte writes, each one waited for.) */
+        const size_t lo = st ? st->pay_lo : pay_lo, n = st ? st->pay_hi - st->pay_lo : pay_n;
+        if (!needs_bounce(b->payload + lo, n)) {
+          c.fin_pay_n = 0;
+        } else {
+          (void)hipGetLastError();
+          if (c.payload_h.ensure(n) != 0)
+            return -1;
+          c.fin_pay_lo = lo;
+          c.fin_pay_n = n;
+        }
+      } else {
+        if (c.io_small.ensure((size_t)ntb * 8 + 64) != 0)
+          return -1;
+        iter_max = reinterpret_cast<int32_t *>(c.io_small.p);
+        ack = c.io_small.p + (size_t)ntb * 4;
+      }
       if (c.io_payload.ensure(pay_n) != 0)
         return -1;
       payload = c.io_payload.p - pay_lo;
     }
+    return 0;
   }
-  const tb_rx_seg_job *d_seg = reinterpret_cast<const tb_rx_seg_job *>(pl.jobs_d.p + o_seg);
-  const tb_rx_seg_job *d_leg = reinterpret_cast<const tb_rx_seg_job *>(pl.jobs_d.p + pl.legacy_off);
-  const tb_rx_tb_job *d_tb = reinterpret_cast<const tb_rx_tb_job *>(pl.jobs_d.p + o_tb);
-  if (c.timing) {
-    for (hipEvent_t &e : c.tev)
-      if (!e)
-        HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c.tev[0], s));
-  }
-  TB_DEBUG_STAGE("entry + copies in (job upload, LLRs, soft buffers)");
-  HIP_TRY((sym ? tb_launch_rx_dematch_sym : scr ? tb_launch_rx_dematch_scr : tb_launch_rx_dematch)(d_leg, (uint32_t)pl.n_legacy_seg, pl.rx_lds_elems, llr, harq,
-                                                                   reinterpret_cast<int8_t *>(c.scratch.p), s,
-                               n_seg <= (size_t)G().n_cus));
-  TB_DEBUG_STAGE("de-matching launch (segments outside the fused kernel)");
-  if (c.timing)
-    HIP_TRY(hipEventRecord(c.tev[1], s));
-  ldpc_dec_args da;
-  memset(&da, 0, sizeof(da));
-  da.llr = reinterpret_cast<const int8_t *>(c.scratch.p);
-  da.out = reinterpret_cast<int8_t *>(c.scratch.p);
-  da.n_iter = d_iter;
-  da.out_mode = 0;
-  da.use_crc = 1;
-  for (int k = 0; k < 4; k++)
-    da.crc_pow_tbl[k] = G().crc_pow[k];
-  da.crc_pow_tbl[NR_HIP_CRC24_A] = G().crc_pow_24a_long;
-  uint32_t *d_acc = reinterpret_cast<uint32_t *>(pl.jobs_d.p + o_acc);
-  int *d_abort = reinterpret_cast<int *>(d_acc) + ntb; /* zero on entry, left zero by the verdict */
-  da.tb_abort = d_abort;
-  tb_rx_fused_args fx;
-  fx.segs = d_seg; fx.tbs = d_tb; fx.llr = llr; fx.harq = harq; fx.payload = payload; fx.ack = ack; fx.iter_max = iter_max;
-  fx.done = d_abort + ntb; fx.gen = reinterpret_cast<uint32_t *>(d_abort + 2 * ntb);
-  fx.slots = reinterpret_cast<unsigned long long *>(pl.jobs_d.p + pl.off[6]); fx.pow24a = G().crc_pow_24a_long;
-  fx.stagger_ticks = fx.stagger_cus = fx.stagger_slots = 0;
-  fx.lrow_off = 0;
-  fx.mute = 0;
-  fx.zc = 0;
-  fx.prio_pro = 0;
-  fx.trace = nullptr;
-  fx.scr = scr ? 1u : 0u;
-  fx.sym = sym ? 1u : 0u;
-  /* A call that mixes code sizes has several decoder launches (TbPlan::DecLaunch); nothing orders them among themselves --
-   * disjoint jobs, scratch rows, per-block state.  NRLDPC_HIP_TB_OVERLAP=1 sends them out on side streams, forked from and
-   * joined to the call's stream, so that the CUs one launch leaves free could take the next one's workgroups.  Default 0:
-   * with several hardware queues active every kernel of the call runs 2 - 4 x longer on this stack (the 96 large workgroups
-   * of the 93-small-TBS mix: 38 -> 162 us; the whole call 0.35 -> 0.53 ms; profiles/r04/small_tbs_overlap.txt) -- round 3
-   * had seen the same with the unfused kernels.  What replaces it is in the plan: launches that fill their last workgroup
-   * round with jobs of the smaller classes. */
-  static const int overlap_env = [] { const char *e = getenv("NRLDPC_HIP_TB_OVERLAP"); return e ? atoi(e) : 0; }();
-  const size_t n_side = (overlap_env && pl.dec.size() >= 2 && !c.timing) ? std::min<size_t>(pl.dec.size() - 1, TB_SIDE_STREAMS) : 0;
-  if (n_side) {
-    for (size_t j = 0; j < TB_SIDE_STREAMS + 1; j++)
-      if (!c.side_ev[j])
-        HIP_TRY(hipEventCreateWithFlags(&c.side_ev[j], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c.side_ev[TB_SIDE_STREAMS], s)); /* fork: behind the uploads, the copies in and the de-matching launch */
-    for (size_t j = 0; j < n_side; j++) {
-      if (!c.side[j])
-        HIP_TRY(hipStreamCreateWithFlags(&c.side[j], hipStreamNonBlocking));
-      HIP_TRY(hipStreamWaitEvent(c.side[j], c.side_ev[TB_SIDE_STREAMS], 0));
+
+  /* launch: de-matching, the decoder launches (on side streams where asked for), reassembly and verdicts; the timing events */
+  int launch(const TbPlan &pl, const RxViews &v)
+  {
+    auto [llr, harq, payload, ack, iter_max, harq_bounce, harq_mirror] = v;
+    int32_t *d_iter = reinterpret_cast<int32_t *>(pl.jobs_d.p + pl.o_iter);
+    const tb_rx_seg_job *d_seg = reinterpret_cast<const tb_rx_seg_job *>(pl.jobs_d.p + pl.o_seg);
+    const tb_rx_seg_job *d_leg = reinterpret_cast<const tb_rx_seg_job *>(pl.jobs_d.p + pl.legacy_off);
+    const tb_rx_tb_job *d_tb = reinterpret_cast<const tb_rx_tb_job *>(pl.jobs_d.p + pl.o_tb);
+    if (c.timing) {
+      for (hipEvent_t &e : c.tev)
+        if (!e)
+          HIP_TRY(hipEventCreate(&e));
+      HIP_TRY(hipEventRecord(c.tev[0], s));
     }
-  }
-  hipStream_t s_call = s;
-  for (size_t k = 0; k < pl.dec.size(); k++) {
-    const TbPlan::DecLaunch &dl = pl.dec[k];
-    const size_t lane = n_side ? k % (n_side + 1) : 0;
-    hipStream_t s = lane ? c.side[lane - 1] : s_call; /* (shadows the call's stream inside the loop) */
-    da.jobs = reinterpret_cast<const ldpc_dec_job *>(pl.jobs_d.p + dl.jobs_off);
-    da.mgroups = reinterpret_cast<const ldpc_dec_mgroup *>(pl.jobs_d.p + dl.grp_off);
-    if (dl.kind == 0 && dl.fused) {
-      /* more than one workgroup per CU in the first round: staggered start (tb_chain.h).  NRLDPC_HIP_TB_STAGGER_US = the
-       * offset between the two workgroups of a CU (k workgroups: 2 / k of it each).  Default 0 = off: measured level to
-       * slower at every offset (profiles/r04/fused_stagger_sweep.txt) -- a CU's workgroups only share their prologue in the
-       * first round, drift apart by themselves afterwards, and a workgroup that decodes alone is no faster than one that
-       * shares its CU (profiles/r04/wg_trace_*.txt) */
-      static const int stagger_us = [] { const char *e = getenv("NRLDPC_HIP_TB_STAGGER_US"); return e ? atoi(e) : 0; }();
-      const int per_cu = std::min(16 / std::max(dl.threads / 64, 1), (160 * 1024) / std::max(dl.lds, 1024));
-      fx.stagger_ticks = 0;
-      /* workgroups that share a CU take turns at the issue priority, pass by pass (ldpc_dec_fast_block.h fair_turns;
-       * NRLDPC_HIP_TB_FAIR=0: off) */
-      static const int fair_env = [] { const char *e = getenv("NRLDPC_HIP_TB_FAIR"); return e ? atoi(e) : 1; }();
-      da.fair = (fair_env && per_cu >= 2 && dl.n > (uint32_t)G().n_cus && dl.threads >= 256) ? dl.threads / 256 : 0;
-      if (stagger_us > 0 && per_cu >= 2 && dl.n > (uint32_t)G().n_cus) {
-        fx.stagger_ticks = (uint32_t)(stagger_us * 100 * 2 / per_cu);
-        fx.stagger_cus = (uint32_t)G().n_cus;
-        fx.stagger_slots = (uint32_t)per_cu;
+    TB_DEBUG_STAGE("entry + copies in (job upload, LLRs, soft buffers)");
+    HIP_TRY((sym ? tb_launch_rx_dematch_sym : scr ? tb_launch_rx_dematch_scr : tb_launch_rx_dematch)(d_leg, (uint32_t)pl.n_legacy_seg, pl.rx_lds_elems, llr, harq,
+                                                                     reinterpret_cast<int8_t *>(c.scratch.p), s,
+                                 pl.n_seg <= (size_t)G().n_cus));
+    TB_DEBUG_STAGE("de-matching launch (segments outside the fused kernel)");
+    if (c.timing)
+      HIP_TRY(hipEventRecord(c.tev[1], s));
+    ldpc_dec_args da;
+    memset(&da, 0, sizeof(da));
+    da.llr = reinterpret_cast<const int8_t *>(c.scratch.p);
+    da.out = reinterpret_cast<int8_t *>(c.scratch.p);
+    da.n_iter = d_iter;
+    da.out_mode = 0;
+    da.use_crc = 1;
+    for (int k = 0; k < 4; k++)
+      da.crc_pow_tbl[k] = G().crc_pow[k];
+    da.crc_pow_tbl[NR_HIP_CRC24_A] = G().crc_pow_24a_long;
+    uint32_t *d_acc = reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.o_acc);
+    int *d_abort = reinterpret_cast<int *>(d_acc) + ntb; /* zero on entry, left zero by the verdict */
+    da.tb_abort = d_abort;
+    tb_rx_fused_args fx;
+    fx.segs = d_seg; fx.tbs = d_tb; fx.llr = llr; fx.harq = harq; fx.payload = payload; fx.ack = ack; fx.iter_max = iter_max;
+    fx.done = d_abort + ntb; fx.gen = reinterpret_cast<uint32_t *>(d_abort + 2 * ntb);
+    fx.slots = reinterpret_cast<unsigned long long *>(pl.jobs_d.p + pl.o_slots); fx.pow24a = G().crc_pow_24a_long;
+    fx.stagger_ticks = fx.stagger_cus = fx.stagger_slots = 0;
+    fx.lrow_off = 0;
+    fx.mute = 0;
+    fx.zc = 0;
+    fx.prio_pro = 0;
+    fx.trace = nullptr;
+    fx.scr = scr ? 1u : 0u;
+    fx.sym = sym ? 1u : 0u;
+    /* A call that mixes code sizes has several decoder launches (TbPlan::DecLaunch); nothing orders them among themselves --
+     * disjoint jobs, scratch rows, per-block state.  NRLDPC_HIP_TB_OVERLAP=1 sends them out on side streams, forked from and
+     * joined to the call's stream, so that the CUs one launch leaves free could take the next one's workgroups.  Default 0:
+     * with several hardware queues active every kernel of the call runs 2 - 4 x longer on this stack (the 96 large workgroups
+     * of the 93-small-TBS mix: 38 -> 162 us; the whole call 0.35 -> 0.53 ms; profiles/r04/small_tbs_overlap.txt) -- round 3
+     * had seen the same with the unfused kernels.  What replaces it is in the plan: launches that fill their last workgroup
+     * round with jobs of the smaller classes. */
+    static const int overlap_env = [] { const char *e = getenv("NRLDPC_HIP_TB_OVERLAP"); return e ? atoi(e) : 0; }();
+    const size_t n_side = (overlap_env && pl.dec.size() >= 2 && !c.timing) ? std::min<size_t>(pl.dec.size() - 1, TB_SIDE_STREAMS) : 0;
+    if (n_side) {
+      for (size_t j = 0; j < TB_SIDE_STREAMS + 1; j++)
+        if (!c.side_ev[j])
+          HIP_TRY(hipEventCreateWithFlags(&c.side_ev[j], hipEventDisableTiming));
+      HIP_TRY(hipEventRecord(c.side_ev[TB_SIDE_STREAMS], s)); /* fork: behind the uploads, the copies in and the de-matching launch */
+      for (size_t j = 0; j < n_side; j++) {
+        if (!c.side[j])
+          HIP_TRY(hipStreamCreateWithFlags(&c.side[j], hipStreamNonBlocking));
+        HIP_TRY(hipStreamWaitEvent(c.side[j], c.side_ev[TB_SIDE_STREAMS], 0));
       }
-      static const char *trace_file = getenv("NRLDPC_HIP_TB_TRACE"); /* diagnostics: per-workgroup clocks of this launch */
-      if (trace_file && c.trace_d.ensure((size_t)dl.n * 128) == 0) {
-        HIP_TRY(hipMemsetAsync(c.trace_d.p, 0, (size_t)dl.n * 128, s));
-        fx.trace = reinterpret_cast<unsigned long long *>(c.trace_d.p);
-      }
-      fx.lrow_off = dl.lrow;
-      fx.mute = dl.mute ? 1u : 0u;
-      fx.zc = (uint32_t)dl.zc;
-      {
-        static const int prio_env = [] { const char *e = getenv("NRLDPC_HIP_TB_PRIO"); return e ? atoi(e) : 1; }();
-        fx.prio_pro = per_cu >= 2 ? (uint32_t)prio_env : 0u;
-      }
-      HIP_TRY(tb_launch_rx_fused(da, fx, dl.threads, dl.lds, dl.n, s));
-      TB_DEBUG_STAGE("fused segment kernel");
-      if (fx.trace) {
-        std::vector<unsigned long long> h((size_t)dl.n * 16);
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(h.data(), c.trace_d.p, h.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(trace_file, "wb")) {
-          fwrite(h.data(), 8, h.size(), f);
-          fclose(f);
+    }
+    hipStream_t s_call = s;
+    for (size_t k = 0; k < pl.dec.size(); k++) {
+      const TbPlan::DecLaunch &dl = pl.dec[k];
+      const size_t lane = n_side ? k % (n_side + 1) : 0;
+      hipStream_t s = lane ? c.side[lane - 1] : s_call; /* (shadows the call's stream inside the loop) */
+      da.jobs = reinterpret_cast<const ldpc_dec_job *>(pl.jobs_d.p + dl.jobs_off);
+      da.mgroups = reinterpret_cast<const ldpc_dec_mgroup *>(pl.jobs_d.p + dl.grp_off);
+      if (dl.kind == 0 && dl.fused) {
+        /* more than one workgroup per CU in the first round: staggered start (tb_chain.h).  NRLDPC_HIP_TB_STAGGER_US = the
+         * offset between the two workgroups of a CU (k workgroups: 2 / k of it each).  Default 0 = off: measured level to
+         * slower at every offset (profiles/r04/fused_stagger_sweep.txt) -- a CU's workgroups only share their prologue in the
+         * first round, drift apart by themselves afterwards, and a workgroup that decodes alone is no faster than one that
+         * shares its CU (profiles/r04/wg_trace_*.txt) */
+        static const int stagger_us = [] { const char *e = getenv("NRLDPC_HIP_TB_STAGGER_US"); return e ? atoi(e) : 0; }();
+        const int per_cu = std::min(16 / std::max(dl.threads / 64, 1), (160 * 1024) / std::max(dl.lds, 1024));
+        fx.stagger_ticks = 0;
+        /* workgroups that share a CU take turns at the issue priority, pass by pass (ldpc_dec_fast_block.h fair_turns;
+         * NRLDPC_HIP_TB_FAIR=0: off) */
+        static const int fair_env = [] { const char *e = getenv("NRLDPC_HIP_TB_FAIR"); return e ? atoi(e) : 1; }();
+        /* (set in this branch only: the other launches go out with what the last fused one left -- known) */
+        da.fair = (fair_env && per_cu >= 2 && dl.n > (uint32_t)G().n_cus && dl.threads >= 256) ? dl.threads / 256 : 0;
+        if (stagger_us > 0 && per_cu >= 2 && dl.n > (uint32_t)G().n_cus) {
+          fx.stagger_ticks = (uint32_t)(stagger_us * 100 * 2 / per_cu);
+          fx.stagger_cus = (uint32_t)G().n_cus;
+          fx.stagger_slots = (uint32_t)per_cu;
         }
-        fx.trace = nullptr;
+        static const char *trace_file = getenv("NRLDPC_HIP_TB_TRACE"); /* diagnostics: per-workgroup clocks of this launch */
+        if (trace_file && c.trace_d.ensure((size_t)dl.n * 128) == 0) {
+          HIP_TRY(hipMemsetAsync(c.trace_d.p, 0, (size_t)dl.n * 128, s));
+          fx.trace = reinterpret_cast<unsigned long long *>(c.trace_d.p);
+        }
+        fx.lrow_off = dl.lrow;
+        fx.mute = dl.mute ? 1u : 0u;
+        fx.zc = (uint32_t)dl.zc;
+        {
+          static const int prio_env = [] { const char *e = getenv("NRLDPC_HIP_TB_PRIO"); return e ? atoi(e) : 1; }();
+          fx.prio_pro = per_cu >= 2 ? (uint32_t)prio_env : 0u;
+        }
+        HIP_TRY(tb_launch_rx_fused(da, fx, dl.threads, dl.lds, dl.n, s));
+        TB_DEBUG_STAGE("fused segment kernel");
+        if (fx.trace) {
+          std::vector<unsigned long long> h((size_t)dl.n * 16);
+          HIP_TRY(hipStreamSynchronize(s));
+          HIP_TRY(hipMemcpy(h.data(), c.trace_d.p, h.size() * 8, hipMemcpyDeviceToHost));
+          if (FILE *f = fopen(trace_file, "wb")) {
+            fwrite(h.data(), 8, h.size(), f);
+            fclose(f);
+          }
+          fx.trace = nullptr;
+        }
       }
+      else if (dl.kind == 0)
+      {
+        HIP_TRY(ldpc_launch_dec_fast_jobs(da, dl.threads, dl.lds, dl.n, s, dl.zc));
+        TB_DEBUG_STAGE("decoder launch (fast kernel, job array)");
+      }
+      else if (dl.kind == 1)
+        HIP_TRY(ldpc_launch_dec_generic_jobs(da, dl.threads, dl.lds, dl.n, s));
+      else
+        HIP_TRY(ldpc_launch_dec_fast_multi_jobs(da, dl.kind == 3 ? 4 : 1, dl.threads, dl.lds, dl.n, s));
     }
-    else if (dl.kind == 0)
-    {
-      HIP_TRY(ldpc_launch_dec_fast_jobs(da, dl.threads, dl.lds, dl.n, s, dl.zc));
-      TB_DEBUG_STAGE("decoder launch (fast kernel, job array)");
+    for (size_t j = 0; j < n_side; j++) { /* join */
+      HIP_TRY(hipEventRecord(c.side_ev[j], c.side[j]));
+      HIP_TRY(hipStreamWaitEvent(s, c.side_ev[j], 0));
     }
-    else if (dl.kind == 1)
-      HIP_TRY(ldpc_launch_dec_generic_jobs(da, dl.threads, dl.lds, dl.n, s));
-    else
-      HIP_TRY(ldpc_launch_dec_fast_multi_jobs(da, dl.kind == 3 ? 4 : 1, dl.threads, dl.lds, dl.n, s));
+    if (c.timing)
+      HIP_TRY(hipEventRecord(c.tev[2], s));
+    if (pl.n_legacy_tb)
+      HIP_TRY(tb_launch_rx_assemble(d_tb, ntb, d_leg, (uint32_t)pl.n_legacy_seg, d_iter, c.scratch.p, payload, ack, iter_max, d_acc, d_abort,
+                                    G().crc_pow_24a_long, G().crc_pow[NR_HIP_CRC16], s));
+    if (c.timing) {
+      HIP_TRY(hipEventRecord(c.tev[3], s));
+      c.timed = true;
+    }
+    TB_DEBUG_STAGE("remaining decoder launches + reassembly / verdict");
+    return 0;
   }
-  for (size_t j = 0; j < n_side; j++) { /* join */
-    HIP_TRY(hipEventRecord(c.side_ev[j], c.side[j]));
-    HIP_TRY(hipStreamWaitEvent(s, c.side_ev[j], 0));
-  }
-  if (c.timing)
-    HIP_TRY(hipEventRecord(c.tev[2], s));
-  if (pl.n_legacy_tb)
-    HIP_TRY(tb_launch_rx_assemble(d_tb, ntb, d_leg, (uint32_t)pl.n_legacy_seg, d_iter, c.scratch.p, payload, ack, iter_max, d_acc, d_abort,
-                                  G().crc_pow_24a_long, G().crc_pow[NR_HIP_CRC16], s));
-  if (c.timing) {
-    HIP_TRY(hipEventRecord(c.tev[3], s));
-    c.timed = true;
-  }
-  TB_DEBUG_STAGE("remaining decoder launches + reassembly / verdict");
-  if (staged) {
+
+  /* stage out: payload back, soft-buffer rows down, a peer's verdicts to the owner */
+  int stage_out(const TbPlan &pl, const RxViews &v)
+  {
     /* payload back: to the caller's array, or (host call, pageable array) to this thread's page-locked staging area */
     uint8_t *pay_dst = (to_host && c.fin_pay_n) ? c.payload_h.p - c.fin_pay_lo : b->payload;
     /* one copy of the whole range when the piece's blocks fill it, or when the destination is the staging area of a call that
@@ -1493,36 +1548,75 @@ int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
      * blocks an earlier piece has already delivered, so there only the blocks themselves are copied, run by run */
     const bool several_pieces = st && st->call_ntb != ntb;
     if (pl.out_dense || (pay_dst != b->payload && !several_pieces)) {
-      HIP_TRY(hipMemcpyAsync(pay_dst + pl.ext[0], c.io_payload.p, pl.ext[1] - pl.ext[0], hipMemcpyDefault, s));
+      HIP_TRY(hipMemcpyAsync(pay_dst + pl.pay_lo, c.io_payload.p, pl.pay_hi - pl.pay_lo, hipMemcpyDefault, s));
     } else {
       for (const TbPlan::OutRun &r : pl.out_runs)
-        HIP_TRY(hipMemcpy2DAsync(pay_dst + r.first, r.pitch, c.io_payload.p + (r.first - pl.ext[0]), r.pitch, r.width, r.rows,
+        HIP_TRY(hipMemcpy2DAsync(pay_dst + r.first, r.pitch, c.io_payload.p + (r.first - pl.pay_lo), r.pitch, r.width, r.rows,
                                  hipMemcpyDefault, s));
     }
     if (harq_staged)
       for (const TbPlan::HarqRun &r : pl.harq_runs) {
         /* a bounced run comes down in pieces of ~8 MB with an event behind each: tb_rx_finish hands piece k over to the
          * caller's array while piece k + 1 is on the link (TbCtx::finish_copies) */
-        const uint32_t step = harq_bounce ? std::max<uint32_t>(1, (uint32_t)(((size_t)8 << 20) / ((size_t)r.width * 2))) : r.rows;
-        for (uint32_t q0 = 0; q0 < r.rows; q0 += step) {
-          const uint32_t nq = std::min(step, r.rows - q0);
-          const size_t first = r.first + (size_t)q0 * b->harq_stride;
-          uint8_t *dst = harq_bounce ? harq_mirror + (first - pl.ext[4]) * 2 : reinterpret_cast<uint8_t *>(b->harq + first);
-          HIP_TRY(hipMemcpy2DAsync(dst, stride2, c.io_harq.p + (first - pl.ext[4]) * 2, stride2, (size_t)r.width * 2, nq, hipMemcpyDefault, s));
-          if (harq_bounce) {
-            hipEvent_t ev = c.next_fin_event();
-            if (ev)
-              HIP_TRY(hipEventRecord(ev, s));
-            c.fin_copies.push_back(TbCtx::FinCopy{reinterpret_cast<uint8_t *>(b->harq + first), dst, (size_t)r.width * 2, nq, stride2, stride2, ev});
-          }
-        }
+        if (tb_harq_run_pieces(r, b->harq_stride, v.harq_bounce, [&](size_t first, uint32_t nq) -> int {
+              uint8_t *dst = v.harq_bounce ? v.harq_mirror + (first - pl.harq_lo) * 2 : reinterpret_cast<uint8_t *>(b->harq + first);
+              HIP_TRY(hipMemcpy2DAsync(dst, stride2, c.io_harq.p + (first - pl.harq_lo) * 2, stride2, (size_t)r.width * 2, nq, hipMemcpyDefault, s));
+              if (v.harq_bounce) {
+                hipEvent_t ev = c.next_fin_event();
+                if (ev)
+                  HIP_TRY(hipEventRecord(ev, s));
+                c.fin_copies.push_back(TbCtx::FinCopy{reinterpret_cast<uint8_t *>(b->harq + first), dst, (size_t)r.width * 2, nq, stride2, stride2, ev});
+              }
+              return 0;
+            }) != 0)
+          return -1;
       }
     if (!to_host) { /* a peer GPU's share of a device-resident batch: the verdicts go to the owner's arrays */
       HIP_TRY(hipMemcpyAsync(b->iter_max + tb0, c.io_small.p, (size_t)ntb * 4, hipMemcpyDefault, s));
       HIP_TRY(hipMemcpyAsync(b->ack + tb0, c.io_small.p + (size_t)ntb * 4, ntb, hipMemcpyDefault, s));
     }
+    return 0;
   }
-  return 0;
+};
+
+/* scr != nullptr (nrLDPC_hip_ulsch_decode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the kernels' instantiations that
+ * unscramble the LLRs on their way into LDS (tb_rx_core.h) -- the caller's LLR array is only read.
+ * sym (with scr; nrLDPC_hip_ulsch_decode_symbols): b->coded holds each block's symbol record instead of its LLRs, in the same
+ * G int16 at coded_off -- staging and sharding move it as they move LLRs; the kernels' instantiations that demap it */
+int tb_rx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
+                  const RxHostStage *st = nullptr, const nrLDPC_hip_tb_scr_t *scr = nullptr, bool sym = false)
+{
+  hipStream_t s;
+  if (tb_begin(s, s_direct, staged) != 0)
+    return -1;
+  if (ntb == 0)
+    return 0;
+  nrLDPC_hip_tb_t *tbs = b->tb + tb0;
+  TbCtx &c = tls_tb;
+  TbRxCall call{b, tb0, ntb, staged, st, scr, sym, s, c};
+  if (call.classify_harq() != 0)
+    return -1;
+  const int fused_mode = tb_fused_mode();
+  uint64_t salt[3] = {(uint64_t)b->harq_stride | ((uint64_t)(call.harq_lib ? 2 : (call.harq_staged ? 1 : 0)) << 32),
+                            (uint64_t)(fused_mode & 0xff) | ((uint64_t)(tb_multi_mode() & 0xff) << 8) | ((uint64_t)tb_classes_enabled() << 16) |
+                                ((uint64_t)(tb_fill_mode() & 0xff) << 24) | ((uint64_t)tb_trunc_enabled() << 32) | ((uint64_t)tb_lrow_enabled() << 33),
+                            call.harq_lib ? harq_tbl.gen.load() : 0};
+  salt[1] |= scr ? (uint64_t)1 << 34 : 0; /* scrambled (and the scr bytes in the key): never an unscrambled call's plan */
+  salt[1] |= sym ? (uint64_t)1 << 35 : 0; /* symbol records: never an LLR call's plan, nor the reverse */
+  const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
+  TbPlan *hit = c.rx.find(tbs, ntb, salt, scr, scr_n);
+  if (hit)
+    for (uint32_t i = 0; i < ntb; i++) /* nr_get_R_ldpc_decoder's state leaves the call as it did the first time */
+      tbs[i].llrLen = hit->llr_len[i];
+  TbPlan &pl = hit ? *hit : c.rx.victim();
+  if (!hit && call.build_plan(pl, salt, fused_mode, scr_n) != 0)
+    return -1;
+  if (c.scratch.ensure(pl.scratch_top) != 0)
+    return -1;
+  RxViews v{static_cast<const int16_t *>(b->coded), call.harq_lib ? nullptr : b->harq, b->payload, b->ack + tb0, b->iter_max + tb0};
+  if (call.stage_in(pl, v) != 0 || call.launch(pl, v) != 0)
+    return -1;
+  return staged ? call.stage_out(pl, v) : 0;
 }
 
 int tb_rx_finish(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb)
@@ -1735,24 +1829,16 @@ template <typename Enq, typename Fin> int tb_run_sharded(const nrLDPC_hip_tb_bat
   return rc;
 }
 
-} // namespace
-
-extern "C" {
-
-int32_t nrLDPC_hip_dlsch_encode(const nrLDPC_hip_tb_batch_t *b)
+/* what every nrLDPC_hip_dlsch_encode* / nrLDPC_hip_ulsch_decode* call checks first: null arguments, mem flags, buffers */
+int tb_check_encode_batch(const nrLDPC_hip_tb_batch_t *b)
 {
   if (!b || !b->tb || !b->payload || !b->coded)
     return set_error("null argument");
   if (b->mem & ~NRLDPC_HIP_MEM_DEVICE)
     return set_error("encode: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
-  if (b->n_tb == 0)
-    return ensure_ready();
-  return tb_run_sharded(
-      b, [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) { return tb_tx_enqueue(b, tb0, n, staged, s); },
-      [&](uint32_t, uint32_t n) { return tb_tx_finish(b, n); });
+  return 0;
 }
-
-int32_t nrLDPC_hip_ulsch_decode(const nrLDPC_hip_tb_batch_t *b)
+int tb_check_decode_batch(const nrLDPC_hip_tb_batch_t *b)
 {
   if (!b || !b->tb || !b->payload || !b->coded)
     return set_error("null argument");
@@ -1762,14 +1848,42 @@ int32_t nrLDPC_hip_ulsch_decode(const nrLDPC_hip_tb_batch_t *b)
     return set_error("decode: invalid mem flags");
   if ((!b->harq && !harq_lib) || !b->ack || !b->iter_max || b->harq_stride < 66 * 384)
     return set_error("decode needs harq (stride >= 66*384), ack and iter_max buffers");
+  return 0;
+}
+
+/* a checked batch over the library's GPUs; scr (its array checked by the caller) and sym as tb_tx_enqueue / tb_rx_enqueue take them */
+int tb_encode_sharded(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr, bool sym)
+{
   if (b->n_tb == 0)
     return ensure_ready();
   return tb_run_sharded(
-      b,
-      [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) {
-        return (staged && !(b->mem & NRLDPC_HIP_MEM_DEVICE)) ? tb_rx_enqueue_host(b, tb0, n) : tb_rx_enqueue(b, tb0, n, staged, s);
+      b, [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) { return tb_tx_enqueue(b, tb0, n, staged, s, scr ? scr + tb0 : nullptr, sym); },
+      [&](uint32_t, uint32_t n) { return tb_tx_finish(b, n); });
+}
+int tb_decode_sharded(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr, bool sym)
+{
+  if (b->n_tb == 0)
+    return ensure_ready();
+  return tb_run_sharded(
+      b, [&](uint32_t tb0, uint32_t n, bool staged, hipStream_t s) {
+        const nrLDPC_hip_tb_scr_t *scr0 = scr ? scr + tb0 : nullptr;
+        return (staged && !(b->mem & NRLDPC_HIP_MEM_DEVICE)) ? tb_rx_enqueue_host(b, tb0, n, scr0, sym) : tb_rx_enqueue(b, tb0, n, staged, s, nullptr, scr0, sym);
       },
       [&](uint32_t tb0, uint32_t n) { return tb_rx_finish(b, tb0, n); });
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t nrLDPC_hip_dlsch_encode(const nrLDPC_hip_tb_batch_t *b)
+{
+  return tb_check_encode_batch(b) != 0 ? -1 : tb_encode_sharded(b, nullptr, false);
+}
+
+int32_t nrLDPC_hip_ulsch_decode(const nrLDPC_hip_tb_batch_t *b)
+{
+  return tb_check_decode_batch(b) != 0 ? -1 : tb_decode_sharded(b, nullptr, false);
 }
 
 int32_t nrLDPC_hip_harq_release(uint64_t id)
