@@ -369,6 +369,57 @@ int32_t nrLDPC_hip_ulsch_decode_symbols(const nrLDPC_hip_tb_batch_t *b, const nr
 int32_t nrLDPC_hip_dlsch_encode_symbols(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr);
 int32_t nrLDPC_hip_layer_mapping(const int16_t *in, uint32_t n_symbs, uint8_t Nl, int16_t *out, uint32_t layer_stride, int32_t mem,
                                  void *stream);
+/* The UL receive front for one layer: the reference's channel level with its shift log2_maxh (nr_rx_pusch_tp, openair1/PHY/
+ * NR_TRANSPORT/nr_ulsch_demodulation.c:1612-1647 with nr_ulsch_scale_channel :382-415 and nr_ulsch_channel_level :434-466) and
+ * nr_ulsch_channel_compensation (:468-577: matched filter and maximum ratio combining over the receive antennas) on the GPU, from
+ * the extracted REs and channel estimates (rxFext[aarx], chFext[aarx] of inner_rx, :1281-1324) to the symbol records
+ * nrLDPC_hip_ulsch_decode_symbols reads.  nrOfLayers == 1 and rho == NULL only; two layers, transform precoding, PTRS and the
+ * extraction from the OFDM grid are not here.  rxFext / chFext are c16 arrays (int16 re, im), antenna a's values ant_stride c16
+ * behind antenna 0's; n_rx = 1..8.  A descriptor (host memory) names one OFDM symbol's data REs of one transport block:
+ *   channel_compensation: for each of the n_seg segments and each RE r < nb_re, over the antennas in order (csrc/nr_rx_front.h
+ *     has the arithmetic, with int16 sums that wrap and packs that saturate exactly where the reference's do), with
+ *     s = shift[tb] taken as 0..31 (a value outside is clamped: it may come from device memory): plane k (k < Qm/2: y, mag_a,
+ *     mag_b, mag_c) of the block's record receives its value at c16 index sym_off + r, the record being int16 at
+ *     records + rec_off and a plane `plane` c16 values long (S = G/Qm for a record decode_symbols reads; sym_off = the
+ *     reference's llr_offset[symbol]/Qm).  Exactly nb_re c16 entries of each of the Qm/2 planes are written per segment and
+ *     nothing else -- not the gaps between segments, not the planes a Qm does not use -- and they are overwritten, not
+ *     accumulated into: no memset as in :1307-1311 is needed.  shift has an entry for every tb the descriptors name.
+ *   channel_level: descriptor i (n_tb of them, every tb < n_tb once) names block tb's measurement symbol (ch_off, nb_re > 0;
+ *     the other fields are not looked at): log2_maxh[tb] = max(0, (log2_approx(avgs) >> 1) + 1 + log2_approx(n_rx >> 2)),
+ *     avgs = max(0, the antennas' averages over the symbol rounded up to 16 REs, the padding counting as zeros).
+ * mem = NRLDPC_HIP_MEM_HOST (synchronous; every array host memory) or NRLDPC_HIP_MEM_DEVICE (enqueued on `stream`: rxFext,
+ * chFext, shift / log2_maxh and records in device memory of one GPU, 4-byte aligned; the descriptors stay host memory and are
+ * uploaded through the calling thread's page-locked area, like the chain's jobs).  So level -> compensation -> decode_symbols
+ * on one stream take a slot from extracted REs to payloads with the records as the only array in between.  A stream that is
+ * being captured is refused: graph capture of these two calls is not supported yet.
+ * 0, or negative -- before anything is enqueued or written -- for a NULL array, n_rx outside 1..8, a bad Qm, rec_off odd,
+ * sym_off + nb_re > plane, two segments of a call whose output ranges overlap, nb_re*Qm > 2^21, (level) nb_re = 0 or a tb that
+ * is out of range or named twice, another mem value, (DEVICE) a buffer that is not device memory of that GPU or not 4-byte
+ * aligned, a capturing stream; nrLDPC_hip_last_error() names the reason.
+ * compensate_host / level_host: the same arithmetic on the CPU, no GPU involved, for checking the kernels: one segment (out =
+ * Qm/2 planes of nb_re c16 one after another; shift clamped as above) / one block (avg, when not NULL, receives the n_rx
+ * averages).  0 / -1. */
+typedef struct nrLDPC_hip_rx_seg {
+  uint32_t tb;      /* index into shift / log2_maxh */
+  uint8_t Qm;       /* 2, 4, 6, 8 */
+  uint8_t pad[3];
+  uint32_t nb_re;   /* data REs of this OFDM symbol */
+  uint32_t plane;   /* c16 values per plane of the block's record */
+  uint32_t sym_off; /* first codeword symbol of this OFDM symbol */
+  uint32_t pad2;
+  uint64_t rx_off;  /* c16 offset of antenna 0's first RE in rxFext */
+  uint64_t ch_off;  /* the same in chFext */
+  uint64_t rec_off; /* int16 offset of the block's record in records, even */
+} nrLDPC_hip_rx_seg_t;
+int32_t nrLDPC_hip_ulsch_channel_level(const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, const nrLDPC_hip_rx_seg_t *first_sym,
+                                       uint32_t n_tb, int32_t *log2_maxh, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_channel_compensation(const int16_t *rxFext, const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride,
+                                              const nrLDPC_hip_rx_seg_t *seg, uint32_t n_seg, const int32_t *shift, int16_t *records,
+                                              int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_compensate_host(const int16_t *rxFext, const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re,
+                                         uint8_t Qm, int32_t shift, int16_t *out);
+int32_t nrLDPC_hip_ulsch_level_host(const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re, int32_t *avg,
+                                    int32_t *log2_maxh);
 /* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one

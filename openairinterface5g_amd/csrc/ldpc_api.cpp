@@ -28,6 +28,8 @@
 #include "nr_gold.h"
 #include "tb_chain.h"
 #include "tb_tx_scr.h"
+#include "nr_rx_front.h"
+#include "tb_rx_front.h"
 #include "ldpc_enc_packed_core.h"
 
 namespace {
@@ -1499,3 +1501,4 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "tb_offload.inc.cpp"
 #include "scrambling_api.inc.cpp"
 #include "qam_api.inc.cpp"
+#include "rx_front_api.inc.cpp"

@@ -1086,3 +1086,128 @@ def layer_mapping(x, Nl, out=None, layer_stride=None, n_symbs=None, stream=None)
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     _check(L.nrLDPC_hip_layer_mapping(x.data_ptr(), n, Nl, out.data_ptr(), stride, MEM_DEVICE, s), "nrLDPC_hip_layer_mapping")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# UL receive front (include/nrLDPC_hip.h: nrLDPC_hip_ulsch_channel_level / _channel_compensation and their _host mirrors)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_ulsch_channel_level", "nrLDPC_hip_ulsch_channel_compensation", "nrLDPC_hip_ulsch_compensate_host",
+            "nrLDPC_hip_ulsch_level_host"]
+
+
+class nrLDPC_hip_rx_seg_t(C.Structure):
+    _fields_ = [("tb", C.c_uint32), ("Qm", C.c_uint8), ("pad", C.c_uint8 * 3), ("nb_re", C.c_uint32), ("plane", C.c_uint32),
+                ("sym_off", C.c_uint32), ("pad2", C.c_uint32), ("rx_off", C.c_uint64), ("ch_off", C.c_uint64), ("rec_off", C.c_uint64)]
+
+
+def _rxf_lib():
+    L = load_library()
+    L.nrLDPC_hip_ulsch_channel_level.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(nrLDPC_hip_rx_seg_t), C.c_uint32, C.c_void_p,
+                                                 C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_channel_level.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_channel_compensation.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(nrLDPC_hip_rx_seg_t),
+                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_channel_compensation.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_compensate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint8, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_compensate_host.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_level_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.nrLDPC_hip_ulsch_level_host.restype = C.c_int32
+    return L
+
+
+def _rx_seg_array(segs):
+    """dicts (tb, Qm, nb_re, plane, sym_off, rx_off, ch_off, rec_off) -> nrLDPC_hip_rx_seg_t[n]; the library checks the values"""
+    arr = (nrLDPC_hip_rx_seg_t * max(len(segs), 1))()
+    for i, s in enumerate(segs):
+        arr[i] = nrLDPC_hip_rx_seg_t(tb=s["tb"], Qm=s["Qm"] & 0xff, nb_re=s["nb_re"], plane=s.get("plane", 0), sym_off=s.get("sym_off", 0),
+                                     rx_off=s.get("rx_off", 0), ch_off=s.get("ch_off", 0), rec_off=s.get("rec_off", 0))
+    return arr
+
+
+def rx_front_segments(tbs, nb_re_per_symbol, rec_off=None):
+    """The descriptors of the receive front for transport blocks tbs (dicts with G, Qm): nb_re_per_symbol[i] = the data REs
+    of TB i's OFDM symbols in time order (they add up to G/Qm).  TB i's record lies at int16 offset rec_off[i] (tb_layout co[i]
+    by default: where ulsch_decode_symbols_device reads it, laid out as pack_symbol_records does); the extracted REs and channel
+    estimates of one antenna are taken back to back, TB after TB and symbol after symbol.  Returns (segs, first_sym, rec_off,
+    n_in): every segment, each TB's first symbol with REs (the measurement symbol), the record offsets, and the c16 values per
+    antenna (ant_stride >= n_in)."""
+    if rec_off is None:
+        rec_off = tb_layout(tbs)[1][:len(tbs)]
+    segs, first, at = [], [], 0
+    for i, (t, syms) in enumerate(zip(tbs, nb_re_per_symbol)):
+        S = t["G"] // t["Qm"]
+        if sum(syms) != S:
+            raise ValueError(f"TB {i}: the symbols hold {sum(syms)} REs, G/Qm = {S}")
+        off = 0
+        for nb in syms:
+            segs.append(dict(tb=i, Qm=t["Qm"], nb_re=int(nb), plane=S, sym_off=off, rx_off=at, ch_off=at, rec_off=int(rec_off[i])))
+            off += nb
+            at += nb
+        first.append(next(s for s in segs[len(segs) - len(syms):] if s["nb_re"] > 0))
+    return segs, first, [int(o) for o in rec_off], at
+
+
+def ulsch_compensate_host(rx, ch, n_rx, ant_stride, nb_re, Qm, shift):
+    """nr_ulsch_channel_compensation for one layer and one segment on the CPU (csrc/nr_rx_front.h, no GPU): rx / ch = numpy int16
+    c16 arrays, antenna a's RE r at c16 index a * ant_stride + r.  Returns int16[Qm/2, nb_re, 2]: y, mag_a, mag_b, mag_c."""
+    rx, ch = np.ascontiguousarray(rx, np.int16).reshape(-1), np.ascontiguousarray(ch, np.int16).reshape(-1)
+    if 1 <= n_rx <= 8:
+        assert min(rx.size, ch.size) >= 2 * ((n_rx - 1) * ant_stride + nb_re)
+    out = np.zeros((max(Qm // 2, 1) if Qm in (2, 4, 6, 8) else 1, max(nb_re, 1), 2), np.int16)
+    _check(_rxf_lib().nrLDPC_hip_ulsch_compensate_host(rx.ctypes.data, ch.ctypes.data, n_rx, ant_stride, nb_re, Qm, shift, out.ctypes.data),
+           "nrLDPC_hip_ulsch_compensate_host")
+    return out.reshape(-1)[:Qm // 2 * nb_re * 2].reshape(Qm // 2, nb_re, 2)
+
+
+def ulsch_level_host(ch, n_rx, ant_stride, nb_re):
+    """The channel level of one block's measurement symbol on the CPU (no GPU): (log2_maxh, int32[n_rx] averages)."""
+    ch = np.ascontiguousarray(ch, np.int16).reshape(-1)
+    if 1 <= n_rx <= 8:
+        assert ch.size >= 2 * ((n_rx - 1) * ant_stride + nb_re)
+    avg, out = np.zeros(8, np.int32), np.zeros(1, np.int32)
+    _check(_rxf_lib().nrLDPC_hip_ulsch_level_host(ch.ctypes.data, n_rx, ant_stride, nb_re, avg.ctypes.data, out.ctypes.data),
+           "nrLDPC_hip_ulsch_level_host")
+    return int(out[0]), avg[:n_rx]
+
+
+def ulsch_channel_level(ch, n_rx, ant_stride, first_sym, out=None, stream=None):
+    """nrLDPC_hip_ulsch_channel_level: first_sym = one descriptor per block (rx_front_segments).  numpy int16 `ch` -> host call,
+    returns int32[n_tb]; torch int16 CUDA tensor -> device call enqueued on `stream` into `out`, a torch int32 CUDA tensor of at
+    least n_tb elements on the same GPU; returns `out`."""
+    L = _rxf_lib()
+    n, arr = len(first_sym), _rx_seg_array(first_sym)
+    if isinstance(ch, np.ndarray):
+        assert ch.dtype == np.int16 and ch.flags.c_contiguous
+        res = np.zeros(max(n, 1), np.int32)
+        _check(L.nrLDPC_hip_ulsch_channel_level(ch.ctypes.data, n_rx, ant_stride, arr, n, res.ctypes.data, MEM_HOST, None),
+               "nrLDPC_hip_ulsch_channel_level")
+        return res[:n]
+    import torch
+    assert ch.is_cuda and ch.dtype == torch.int16 and ch.is_contiguous()
+    assert out is not None and out.is_cuda and out.device == ch.device and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_ulsch_channel_level(ch.data_ptr(), n_rx, ant_stride, arr, n, out.data_ptr(), MEM_DEVICE, s),
+           "nrLDPC_hip_ulsch_channel_level")
+    return out
+
+
+def ulsch_channel_compensation(rx, ch, n_rx, ant_stride, segs, shift, records, stream=None):
+    """nrLDPC_hip_ulsch_channel_compensation: segs = the descriptors (rx_front_segments), shift = int32 per block (the output of
+    ulsch_channel_level), records = the int16 array the blocks' symbol records lie in, written in place -- only the segments'
+    entries.  numpy arrays -> host call; torch CUDA tensors (one GPU, contiguous) -> device call enqueued on `stream`.  Returns
+    `records`."""
+    L = _rxf_lib()
+    arr = _rx_seg_array(segs)
+    if isinstance(rx, np.ndarray):
+        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (rx, ch, records))
+        sh = np.ascontiguousarray(shift, np.int32)
+        _check(L.nrLDPC_hip_ulsch_channel_compensation(rx.ctypes.data, ch.ctypes.data, n_rx, ant_stride, arr, len(segs), sh.ctypes.data,
+                                                       records.ctypes.data, MEM_HOST, None), "nrLDPC_hip_ulsch_channel_compensation")
+        return records
+    import torch
+    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == rx.device for a in (rx, ch, records))
+    assert shift.is_cuda and shift.dtype == torch.int32 and shift.is_contiguous() and shift.device == rx.device
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_ulsch_channel_compensation(rx.data_ptr(), ch.data_ptr(), n_rx, ant_stride, arr, len(segs), shift.data_ptr(),
+                                                   records.data_ptr(), MEM_DEVICE, s), "nrLDPC_hip_ulsch_channel_compensation")
+    return records
