@@ -373,8 +373,8 @@ int32_t nrLDPC_hip_layer_mapping(const int16_t *in, uint32_t n_symbs, uint8_t Nl
  * NR_TRANSPORT/nr_ulsch_demodulation.c:1612-1647 with nr_ulsch_scale_channel :382-415 and nr_ulsch_channel_level :434-466) and
  * nr_ulsch_channel_compensation (:468-577: matched filter and maximum ratio combining over the receive antennas) on the GPU, from
  * the extracted REs and channel estimates (rxFext[aarx], chFext[aarx] of inner_rx, :1281-1324) to the symbol records
- * nrLDPC_hip_ulsch_decode_symbols reads.  nrOfLayers == 1 and rho == NULL only; two layers, transform precoding, PTRS and the
- * extraction from the OFDM grid are not here.  rxFext / chFext are c16 arrays (int16 re, im), antenna a's values ant_stride c16
+ * nrLDPC_hip_ulsch_decode_symbols reads.  nrOfLayers == 1 and rho == NULL only; two layers, transform precoding and PTRS are
+ * not here; the _grid calls below read the OFDM grid itself.  rxFext / chFext are c16 arrays (int16 re, im), antenna a's values ant_stride c16
  * behind antenna 0's; n_rx = 1..8.  A descriptor (host memory) names one OFDM symbol's data REs of one transport block:
  *   channel_compensation: for each of the n_seg segments and each RE r < nb_re, over the antennas in order (csrc/nr_rx_front.h
  *     has the arithmetic, with int16 sums that wrap and packs that saturate exactly where the reference's do), with
@@ -420,6 +420,77 @@ int32_t nrLDPC_hip_ulsch_compensate_host(const int16_t *rxFext, const int16_t *c
                                          uint8_t Qm, int32_t shift, int16_t *out);
 int32_t nrLDPC_hip_ulsch_level_host(const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re, int32_t *avg,
                                     int32_t *log2_maxh);
+/* The same front read straight from what a gNB has in memory -- the FFT output grid rxdataF[aarx] and the full-width channel
+ * estimates ul_ch_estimates[aarx] of a DMRS symbol -- with nr_ulsch_extract_rbs (nr_ulsch_demodulation.c:279-380) fused into
+ * the kernels' loads: no rxFext / chFext arrays exist.  csrc/nr_rx_grid.h defines the extraction once for host and device.  A
+ * symbol has a pattern: NRLDPC_HIP_RXG_FULL (no DMRS: all 12 subcarriers of an RB, p(j) = j), _DMRS1 (type 1: the odd ones,
+ * p(j) = 2j + 1) or _DMRS2 (type 2: those with p % 6 >= 2, p(j) = 6 (j/4) + 2 + j%4).  Data RE j < nb_re of a segment is read
+ * from the grid at c16 index rx_off + a rx_ant_stride + (start_re + p(j)) mod fft_size and its estimate at ch_off +
+ * a ch_ant_stride + p(j) (the grid wraps at fft_size, the estimates do not), for antenna a; the two arrays have an antenna
+ * stride each.  Everything else -- arithmetic, records, write set, mem modes, the refusals -- is that of
+ * nrLDPC_hip_ulsch_channel_compensation / _channel_level run on arrays extracted that way, bit for bit.  HOST mode stages the
+ * c16 ranges the descriptors reach and nothing else.  Further refusals: a pattern that is none of the three, fft_size = 0,
+ * start_re >= fft_size, nb_re above the pattern's count within fft_size subcarriers, which is p(nb_re - 1) >= fft_size.  The
+ * calls do not know the arrays' extents; the Python wrappers, which do, refuse a descriptor that reaches outside.
+ * One deviation: the reference's one-piece type-2 branch reads rxF[idx] (:352) where every other branch reads
+ * rxF[start_re + idx]; start_re is added here.
+ * extract_host: the extraction of one OFDM symbol of one antenna on the CPU, no GPU involved, for checking: rxdataF points at
+ * the symbol's subcarrier 0, ul_ch at the estimate of PUSCH subcarrier 0, rxFext / chFext receive nb_re c16 each.  0 / -1.
+ * pusch_grid_segments (host only, no GPU): the descriptors of n_alloc PUSCH allocations as nr_rx_pusch_tp derives them
+ * (:1584-1665): one segment per OFDM symbol with nb_re = get_nb_re_pusch > 0, allocation after allocation in symbol order,
+ * sym_off the running sum (llr_offset / Qm), start_re = (first_carrier_offset + (rb_start + bwp_start) 12) % fft_size, rx_off =
+ * rx_slot_off + symbol fft_size, ch_off = the allocation's ch_off + dmrs_symbol fft_size; first_sym_out[i] = allocation i's
+ * measurement symbol, its first with REs.  At most `cap` segments are written, *n_seg_out receives their number.  Refused:
+ * start_symbol + nr_of_symbols > 14, nr_of_symbols = 0, a DMRS symbol of the allocation followed by another (the reference
+ * asserts, :421), rb_size = 0, 12 rb_size > fft_size, first_carrier_offset >= fft_size, a dmrs_config_type other than 0 (type 1)
+ * or 1 (type 2), num_dmrs_cdm_grps_no_data other than 1 or 2, the sum of nb_re above plane, no symbol with REs, more than cap
+ * segments, and type 2 with two CDM groups without data: the reference's extraction then writes 8 REs per RB where nb_re
+ * counts 4, and its level, which runs over the symbol rounded up to 16 REs, sums extracted entries beyond nb_re that are not
+ * zeros -- a value this interface, which reads nb_re entries, cannot reproduce. */
+#define NRLDPC_HIP_RXG_FULL 0
+#define NRLDPC_HIP_RXG_DMRS1 1
+#define NRLDPC_HIP_RXG_DMRS2 2
+typedef struct nrLDPC_hip_rx_grid_seg {
+  uint32_t tb;       /* index into shift / log2_maxh */
+  uint8_t Qm;        /* 2, 4, 6, 8 */
+  uint8_t pattern;   /* NRLDPC_HIP_RXG_* */
+  uint8_t pad[2];
+  uint32_t nb_re;    /* data REs of this OFDM symbol */
+  uint32_t plane;    /* c16 values per plane of the block's record */
+  uint32_t sym_off;  /* first codeword symbol of this OFDM symbol */
+  uint32_t fft_size; /* N, the OFDM symbol size */
+  uint32_t start_re; /* grid subcarrier of PUSCH subcarrier 0, < N */
+  uint32_t pad2;
+  uint64_t rx_off;   /* c16 offset of antenna 0's subcarrier 0 of this OFDM symbol in rxdataF */
+  uint64_t ch_off;   /* c16 offset of antenna 0's estimate of PUSCH subcarrier 0, of the symbol whose estimates are used */
+  uint64_t rec_off;  /* int16 offset of the block's record in records, even */
+} nrLDPC_hip_rx_grid_seg_t;
+typedef struct nrLDPC_hip_pusch_alloc {
+  uint32_t tb;                        /* index into shift / log2_maxh */
+  uint8_t Qm;
+  uint8_t dmrs_config_type;           /* 0: type 1, 1: type 2 */
+  uint8_t num_dmrs_cdm_grps_no_data;  /* 1 or 2 */
+  uint8_t dmrs_symbol;                /* the symbol whose estimates are used; the caller decides (chest_time changes it) */
+  uint32_t fft_size;                  /* N */
+  uint32_t first_carrier_offset;
+  uint32_t bwp_start, rb_start, rb_size;
+  uint32_t start_symbol, nr_of_symbols;
+  uint32_t ul_dmrs_symb_pos;          /* bit s: symbol s carries DMRS */
+  uint32_t plane;                     /* c16 values per plane of the block's record (G / Qm) */
+  uint32_t pad;
+  uint64_t rx_slot_off;               /* c16 offset of antenna 0's symbol 0, subcarrier 0 of the slot in rxdataF */
+  uint64_t ch_off;                    /* c16 offset of antenna 0's estimates of symbol 0 in ul_ch */
+  uint64_t rec_off;                   /* int16 offset of the block's record in records, even */
+} nrLDPC_hip_pusch_alloc_t;
+int32_t nrLDPC_hip_ulsch_channel_level_grid(const int16_t *ul_ch, uint32_t n_rx, uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *first_sym,
+                                            uint32_t n_tb, int32_t *log2_maxh, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_channel_compensation_grid(const int16_t *rxdataF, const int16_t *ul_ch, uint32_t n_rx, uint64_t rx_ant_stride,
+                                                   uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, const int32_t *shift,
+                                                   int16_t *records, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_extract_host(const int16_t *rxdataF, const int16_t *ul_ch, uint32_t pattern, uint32_t fft_size, uint32_t start_re,
+                                      uint32_t nb_re, int16_t *rxFext, int16_t *chFext);
+int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_rx_grid_seg_t *seg_out, uint32_t cap,
+                                       nrLDPC_hip_rx_grid_seg_t *first_sym_out, uint32_t *n_seg_out);
 /* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one

@@ -29,6 +29,7 @@
 #include "tb_chain.h"
 #include "tb_tx_scr.h"
 #include "nr_rx_front.h"
+#include "nr_rx_grid.h"
 #include "tb_rx_front.h"
 #include "ldpc_enc_packed_core.h"
 
@@ -1502,3 +1503,4 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "scrambling_api.inc.cpp"
 #include "qam_api.inc.cpp"
 #include "rx_front_api.inc.cpp"
+#include "rx_grid_api.inc.cpp"

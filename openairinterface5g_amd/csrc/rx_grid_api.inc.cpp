@@ -1,0 +1,356 @@
+/*
+ * rx_grid_api.inc.cpp -- the UL receive front read from the OFDM grid: the _grid forms of the two calls of
+ * rx_front_api.inc.cpp (included behind it; they share its checks and its plan), the CPU extraction for checking, and the
+ * descriptors of a PUSCH allocation.  Where the REs lie: nr_rx_grid.h; the kernels: tb_rx_front.hip.  Everything the kernels
+ * index with is checked here, before anything is enqueued.
+ */
+
+namespace {
+
+int rxg_check_seg(const char *who, uint32_t pattern, uint32_t fft_size, uint32_t start_re, uint32_t nb_re)
+{
+  if (pattern >= NR_RXG_PATTERNS)
+    return set_error((std::string(who) + ": pattern must be FULL, DMRS1 or DMRS2").c_str());
+  if (fft_size > NR_SCR_MAX_BITS)
+    return set_error((std::string(who) + ": fft_size above 2^21").c_str());
+  if (fft_size == 0 || start_re >= fft_size)
+    return set_error((std::string(who) + ": start_re must be below fft_size").c_str());
+  /* the same as p(nb_re - 1) >= fft_size */
+  if (nb_re > nr_rxg_count(pattern, fft_size))
+    return set_error((std::string(who) + ": nb_re above the pattern's count within fft_size subcarriers (p(nb_re - 1) >= fft_size)").c_str());
+  return 0;
+}
+
+/* the c16 range [lo, hi) of one antenna's grid that a segment reaches: one piece, or the whole OFDM symbol when it wraps */
+void rxg_rx_range(const nrLDPC_hip_rx_grid_seg_t &g, uint64_t &lo, uint64_t &hi)
+{
+  const uint32_t first = g.start_re + nr_rxg_p(g.pattern, 0), last = g.start_re + nr_rxg_p(g.pattern, g.nb_re - 1u);
+  if (last < g.fft_size) {
+    lo = g.rx_off + first;
+    hi = g.rx_off + last + 1u;
+  } else if (first >= g.fft_size) {
+    lo = g.rx_off + first - g.fft_size;
+    hi = g.rx_off + last - g.fft_size + 1u;
+  } else {
+    lo = g.rx_off;
+    hi = g.rx_off + g.fft_size;
+  }
+}
+
+/* the grid checks, then the plan of the extracted form (its checks, output ranges and jobs) with the input ranges of the grid */
+int rxg_plan_compensation(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
+                          std::vector<rx_front_grid_job> &gj)
+{
+  std::vector<nrLDPC_hip_rx_seg_t> plain(n_seg);
+  for (uint32_t i = 0; i < n_seg; i++) {
+    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
+    if (rxg_check_seg("channel_compensation_grid", g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
+      return -1;
+    nrLDPC_hip_rx_seg_t &q = plain[i];
+    memset(&q, 0, sizeof q);
+    q.tb = g.tb;
+    q.Qm = g.Qm;
+    q.nb_re = g.nb_re;
+    q.plane = g.plane;
+    q.sym_off = g.sym_off;
+    q.rx_off = g.rx_off;
+    q.ch_off = g.ch_off;
+    q.rec_off = g.rec_off;
+  }
+  if (rxf_plan_compensation(plain.data(), n_seg, 1, 0, p) != 0)
+    return -1;
+  p.rx_lo = p.ch_lo = UINT64_MAX;
+  p.rx_hi = p.ch_hi = 0;
+  gj.reserve(p.jobs.size());
+  for (uint32_t i = 0; i < n_seg; i++) {
+    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
+    if (g.nb_re == 0)
+      continue;
+    uint64_t lo, hi;
+    rxg_rx_range(g, lo, hi);
+    p.rx_lo = std::min(p.rx_lo, lo);
+    p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
+    p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
+    p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(n_rx - 1) * ch_stride);
+    rx_front_grid_job j{};
+    j.pattern = g.pattern;
+    j.fft_size = g.fft_size;
+    j.start_re = g.start_re;
+    gj.push_back(j);
+  }
+  return 0;
+}
+
+/* rxf_place, then the placed segments into the grid jobs (p.jobs and gj run in step: the segments with REs).  A staged copy
+ * starts at the first c16 that is reached, which lies behind subcarrier 0: rx_off / ch_off minus the bias may wrap below zero,
+ * and the kernels' 64-bit address sums bring it back. */
+void rxg_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias, uint64_t rec_word)
+{
+  rxf_place(p, rx_bias, ch_bias, out_bias, rec_word);
+  for (size_t i = 0; i < gj.size(); i++)
+    gj[i].s = p.jobs[i];
+}
+
+size_t rxg_jobs_bytes(const RxFrontPlan &p, const std::vector<rx_front_grid_job> &gj)
+{
+  return align_up(p.wgs.size() * sizeof(rx_front_wg), 16) + align_up(gj.size() * sizeof(rx_front_grid_job), 16);
+}
+void rxg_write_jobs(const RxFrontPlan &p, const std::vector<rx_front_grid_job> &gj, uint8_t *dst)
+{
+  memcpy(dst, p.wgs.data(), p.wgs.size() * sizeof(rx_front_wg));
+  memcpy(dst + align_up(p.wgs.size() * sizeof(rx_front_wg), 16), gj.data(), gj.size() * sizeof(rx_front_grid_job));
+}
+
+int rxg_plan_level(const nrLDPC_hip_rx_grid_seg_t *fs, uint32_t n_tb, uint32_t n_rx, uint64_t ch_stride, std::vector<rx_front_grid_lvl_job> &lvl,
+                   uint64_t &ch_lo, uint64_t &ch_hi)
+{
+  std::vector<uint8_t> seen(n_tb, 0);
+  lvl.resize(n_tb);
+  ch_lo = UINT64_MAX;
+  ch_hi = 0;
+  for (uint32_t i = 0; i < n_tb; i++) {
+    if (fs[i].tb >= n_tb || seen[fs[i].tb])
+      return set_error("channel_level_grid: every tb below n_tb must be named once");
+    seen[fs[i].tb] = 1;
+    if (fs[i].nb_re == 0)
+      return set_error("channel_level_grid: the measurement symbol has no REs");
+    if ((uint64_t)fs[i].nb_re * 2u > NR_SCR_MAX_BITS)
+      return set_error("channel_level_grid: nb_re above 2^20");
+    /* the level reads the estimates alone, but the descriptor is the segment's: its grid fields are held to the same rules */
+    if (rxg_check_seg("channel_level_grid", fs[i].pattern, fs[i].fft_size, fs[i].start_re, fs[i].nb_re) != 0)
+      return -1;
+    lvl[i] = rx_front_grid_lvl_job{fs[i].ch_off, fs[i].nb_re, fs[i].tb, fs[i].pattern, 0};
+    ch_lo = std::min(ch_lo, fs[i].ch_off + nr_rxg_p(fs[i].pattern, 0));
+    ch_hi = std::max(ch_hi, fs[i].ch_off + nr_rxg_p(fs[i].pattern, fs[i].nb_re - 1u) + 1u + (uint64_t)(n_rx - 1) * ch_stride);
+  }
+  return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t nrLDPC_hip_ulsch_extract_host(const int16_t *rxdataF, const int16_t *ul_ch, uint32_t pattern, uint32_t fft_size, uint32_t start_re,
+                                      uint32_t nb_re, int16_t *rxFext, int16_t *chFext)
+{
+  if (rxg_check_seg("extract_host", pattern, fft_size, start_re, nb_re) != 0)
+    return -1;
+  if (nb_re && (!rxdataF || !ul_ch || !rxFext || !chFext))
+    return set_error("null argument");
+  for (uint32_t j = 0; j < nb_re; j++) {
+    const uint32_t p = nr_rxg_p(pattern, j), sc = nr_rxg_grid_sc(start_re, p, fft_size);
+    rxFext[2 * (size_t)j] = rxdataF[2 * (size_t)sc];
+    rxFext[2 * (size_t)j + 1] = rxdataF[2 * (size_t)sc + 1];
+    chFext[2 * (size_t)j] = ul_ch[2 * (size_t)p];
+    chFext[2 * (size_t)j + 1] = ul_ch[2 * (size_t)p + 1];
+  }
+  return 0;
+}
+
+int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_rx_grid_seg_t *seg_out, uint32_t cap,
+                                       nrLDPC_hip_rx_grid_seg_t *first_sym_out, uint32_t *n_seg_out)
+{
+  if (!n_seg_out || (n_alloc && (!alloc || !first_sym_out)) || (cap && !seg_out))
+    return set_error("null argument");
+  /* everything is checked and derived first: nothing is written when an allocation is refused */
+  std::vector<nrLDPC_hip_rx_grid_seg_t> segs, first;
+  for (uint32_t i = 0; i < n_alloc; i++) {
+    const nrLDPC_hip_pusch_alloc_t &a = alloc[i];
+    const uint32_t N = a.fft_size, type = a.dmrs_config_type, cdm = a.num_dmrs_cdm_grps_no_data;
+    if (qam_check_qm(a.Qm) != 0)
+      return set_error("pusch_grid_segments: Qm must be 2, 4, 6 or 8");
+    if (a.nr_of_symbols == 0 || a.start_symbol >= NR_RXG_SYMBOLS || a.nr_of_symbols > NR_RXG_SYMBOLS - a.start_symbol)
+      return set_error("pusch_grid_segments: the symbols must lie within the slot's 14");
+    if (a.rb_size == 0)
+      return set_error("pusch_grid_segments: rb_size is 0");
+    if (N == 0 || (uint64_t)a.rb_size * 12u > N)
+      return set_error("pusch_grid_segments: the allocation is wider than fft_size");
+    if (a.first_carrier_offset >= N)
+      return set_error("pusch_grid_segments: first_carrier_offset must be below fft_size");
+    if (type > 1)
+      return set_error("pusch_grid_segments: dmrs_config_type must be 0 (type 1) or 1 (type 2)");
+    if (cdm < 1 || cdm > 2)
+      return set_error("pusch_grid_segments: num_dmrs_cdm_grps_no_data must be 1 or 2");
+    if (type == 1 && cdm == 2)
+      return set_error("pusch_grid_segments: type 2 with two CDM groups without data is not supported (the level runs over extracted entries beyond nb_re)");
+    const uint32_t start_re = nr_rxg_start_re(a.first_carrier_offset, a.bwp_start, a.rb_start, N);
+    uint32_t off = 0;
+    bool have_first = false;
+    for (uint32_t sym = a.start_symbol; sym < a.start_symbol + a.nr_of_symbols; sym++) {
+      if (nr_rxg_double_dmrs(a.ul_dmrs_symb_pos, sym))
+        return set_error("pusch_grid_segments: two adjacent DMRS symbols are not supported");
+      const uint32_t nb = nr_rxg_nb_re(a.ul_dmrs_symb_pos, sym, type, cdm, a.rb_size);
+      if (nb == 0)
+        continue;
+      nrLDPC_hip_rx_grid_seg_t g;
+      memset(&g, 0, sizeof g);
+      g.tb = a.tb;
+      g.Qm = a.Qm;
+      g.pattern = (uint8_t)nr_rxg_symbol_pattern(a.ul_dmrs_symb_pos, sym, type);
+      g.nb_re = nb;
+      g.plane = a.plane;
+      g.sym_off = off;
+      g.fft_size = N;
+      g.start_re = start_re;
+      g.rx_off = a.rx_slot_off + (uint64_t)sym * N;
+      g.ch_off = a.ch_off + (uint64_t)a.dmrs_symbol * N;
+      g.rec_off = a.rec_off;
+      off += nb;
+      if (off > a.plane)
+        return set_error("pusch_grid_segments: the symbols' REs add up to more than plane");
+      segs.push_back(g);
+      if (!have_first) {
+        first.push_back(g);
+        have_first = true;
+      }
+    }
+    if (!have_first)
+      return set_error("pusch_grid_segments: no symbol of the allocation has data REs");
+  }
+  if (segs.size() > cap)
+    return set_error("pusch_grid_segments: more segments than cap");
+  if (!segs.empty())
+    memcpy(seg_out, segs.data(), segs.size() * sizeof segs[0]);
+  if (!first.empty())
+    memcpy(first_sym_out, first.data(), first.size() * sizeof first[0]);
+  *n_seg_out = (uint32_t)segs.size();
+  return 0;
+}
+
+int32_t nrLDPC_hip_ulsch_channel_compensation_grid(const int16_t *rxdataF, const int16_t *ul_ch, uint32_t n_rx, uint64_t rx_ant_stride,
+                                                   uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, const int32_t *shift,
+                                                   int16_t *records, int32_t mem, void *stream)
+{
+  if (rxf_check_common("channel_compensation_grid", n_rx, mem) != 0)
+    return -1;
+  if (n_seg && (!rxdataF || !ul_ch || !seg || !shift || !records))
+    return set_error("null argument");
+  RxFrontPlan p;
+  std::vector<rx_front_grid_job> gj;
+  if (rxg_plan_compensation(seg, n_seg, n_rx, rx_ant_stride, ch_ant_stride, p, gj) != 0)
+    return -1;
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    if (n_seg == 0)
+      return 0;
+    const int ord = scr_device_ordinal(records);
+    if (ord < 0 || !rxf_dev_ok(records, ord) || !rxf_dev_ok(rxdataF, ord) || !rxf_dev_ok(ul_ch, ord) || !rxf_dev_ok(shift, ord))
+      return set_error("channel_compensation_grid: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    if (rxf_check_stream("channel_compensation_grid", static_cast<hipStream_t>(stream)) != 0)
+      return -1;
+    if (gj.empty())
+      return 0;
+    rxg_place(p, gj, 0, 0, 0, reinterpret_cast<uintptr_t>(records) >> 2);
+    TbCtx &c = tls_tb;
+    hipStream_t s;
+    const size_t bytes = rxg_jobs_bytes(p, gj);
+    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 ||
+        c.jobs_d.ensure(bytes) != 0)
+      return -1;
+    rxg_write_jobs(p, gj, c.jobs_h.p);
+    if (tb_upload_jobs(c, c.jobs_d.p, bytes, s) != 0)
+      return -1;
+    HIP_TRY(nr_launch_rx_compensation_grid(reinterpret_cast<const rx_front_wg *>(c.jobs_d.p), (uint32_t)p.wgs.size(),
+                                           reinterpret_cast<const rx_front_grid_job *>(c.jobs_d.p + align_up(p.wgs.size() * sizeof(rx_front_wg), 16)),
+                                           reinterpret_cast<const uint32_t *>(rxdataF), reinterpret_cast<const uint32_t *>(ul_ch), n_rx, rx_ant_stride,
+                                           ch_ant_stride, shift, reinterpret_cast<uint32_t *>(records), s));
+    return 0;
+  }
+  if (gj.empty())
+    return 0;
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  /* the device works on copies of the c16 ranges the segments reach; the output keeps the caller's alignment phase */
+  const uint64_t out_pad = p.out_lo & 3u;
+  rxg_place(p, gj, p.rx_lo, p.ch_lo, p.out_lo - out_pad, 0);
+  const size_t jobs_b = rxg_jobs_bytes(p, gj), shift_b = align_up((size_t)p.n_shift * 4u, 16), rx_b = align_up((size_t)(p.rx_hi - p.rx_lo) * 4u, 16),
+               ch_b = align_up((size_t)(p.ch_hi - p.ch_lo) * 4u, 16), out_b = (size_t)(p.out_hi - p.out_lo + out_pad) * 4u;
+  if (c.ensure(jobs_b + shift_b + rx_b + ch_b, out_b) != 0)
+    return -1;
+  rxg_write_jobs(p, gj, c.h_in);
+  memcpy(c.h_in + jobs_b, shift, (size_t)p.n_shift * 4u);
+  memcpy(c.h_in + jobs_b + shift_b, rxdataF + 2 * p.rx_lo, (size_t)(p.rx_hi - p.rx_lo) * 4u);
+  memcpy(c.h_in + jobs_b + shift_b + rx_b, ul_ch + 2 * p.ch_lo, (size_t)(p.ch_hi - p.ch_lo) * 4u);
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + shift_b + rx_b + ch_b, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(nr_launch_rx_compensation_grid(reinterpret_cast<const rx_front_wg *>(c.d_in), (uint32_t)p.wgs.size(),
+                                         reinterpret_cast<const rx_front_grid_job *>(c.d_in + align_up(p.wgs.size() * sizeof(rx_front_wg), 16)),
+                                         reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + shift_b),
+                                         reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + shift_b + rx_b), n_rx, rx_ant_stride, ch_ant_stride,
+                                         reinterpret_cast<const int32_t *>(c.d_in + jobs_b), reinterpret_cast<uint32_t *>(c.d_out), c.stream));
+  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_b, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  /* only the segments' entries go to the caller's array */
+  for (const rx_front_seg_job &j : p.jobs)
+    for (uint32_t k = 0; k < j.Qm / 2u; k++) {
+      const uint64_t at = j.out_off + (uint64_t)k * j.plane;
+      memcpy(records + 2 * (at + p.out_lo - out_pad), c.h_out + 4u * at, (size_t)j.nb_re * 4u);
+    }
+  return 0;
+}
+
+int32_t nrLDPC_hip_ulsch_channel_level_grid(const int16_t *ul_ch, uint32_t n_rx, uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *first_sym,
+                                            uint32_t n_tb, int32_t *log2_maxh, int32_t mem, void *stream)
+{
+  if (rxf_check_common("channel_level_grid", n_rx, mem) != 0)
+    return -1;
+  if (n_tb && (!ul_ch || !first_sym || !log2_maxh))
+    return set_error("null argument");
+  if (n_tb == 0)
+    return 0;
+  std::vector<rx_front_grid_lvl_job> lvl;
+  uint64_t ch_lo, ch_hi;
+  if (rxg_plan_level(first_sym, n_tb, n_rx, ch_ant_stride, lvl, ch_lo, ch_hi) != 0)
+    return -1;
+  /* the blocks' jobs, then their zeroed state (maxima, counters) */
+  const size_t jobs_b = align_up((size_t)n_tb * sizeof(rx_front_grid_lvl_job), 16), state_b = align_up((size_t)n_tb * 8u, 16);
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    const int ord = scr_device_ordinal(log2_maxh);
+    if (ord < 0 || !rxf_dev_ok(log2_maxh, ord) || !rxf_dev_ok(ul_ch, ord))
+      return set_error("channel_level_grid: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    if (rxf_check_stream("channel_level_grid", static_cast<hipStream_t>(stream)) != 0)
+      return -1;
+    TbCtx &c = tls_tb;
+    hipStream_t s;
+    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_b + state_b) != 0 ||
+        c.jobs_d.ensure(jobs_b + state_b) != 0)
+      return -1;
+    memcpy(c.jobs_h.p, lvl.data(), (size_t)n_tb * sizeof(rx_front_grid_lvl_job));
+    memset(c.jobs_h.p + jobs_b, 0, state_b);
+    if (tb_upload_jobs(c, c.jobs_d.p, jobs_b + state_b, s) != 0)
+      return -1;
+    HIP_TRY(nr_launch_rx_level_grid(reinterpret_cast<const rx_front_grid_lvl_job *>(c.jobs_d.p), n_tb, reinterpret_cast<const uint32_t *>(ul_ch), n_rx,
+                                    ch_ant_stride, reinterpret_cast<int32_t *>(c.jobs_d.p + jobs_b), log2_maxh, s));
+    return 0;
+  }
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  for (rx_front_grid_lvl_job &j : lvl)
+    j.ch_off -= ch_lo;
+  const size_t ch_b = (size_t)(ch_hi - ch_lo) * 4u;
+  if (c.ensure(jobs_b + state_b + align_up(ch_b, 16), (size_t)n_tb * 4u) != 0)
+    return -1;
+  memcpy(c.h_in, lvl.data(), (size_t)n_tb * sizeof(rx_front_grid_lvl_job));
+  memset(c.h_in + jobs_b, 0, state_b);
+  memcpy(c.h_in + jobs_b + state_b, ul_ch + 2 * ch_lo, ch_b);
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + state_b + ch_b, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(nr_launch_rx_level_grid(reinterpret_cast<const rx_front_grid_lvl_job *>(c.d_in), n_tb,
+                                  reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + state_b), n_rx, ch_ant_stride,
+                                  reinterpret_cast<int32_t *>(c.d_in + jobs_b), reinterpret_cast<int32_t *>(c.d_out), c.stream));
+  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, (size_t)n_tb * 4u, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  memcpy(log2_maxh, c.h_out, (size_t)n_tb * 4u);
+  return 0;
+}
+
+} /* extern "C" */

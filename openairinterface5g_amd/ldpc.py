@@ -1211,3 +1211,148 @@ def ulsch_channel_compensation(rx, ch, n_rx, ant_stride, segs, shift, records, s
     _check(L.nrLDPC_hip_ulsch_channel_compensation(rx.data_ptr(), ch.data_ptr(), n_rx, ant_stride, arr, len(segs), shift.data_ptr(),
                                                    records.data_ptr(), MEM_DEVICE, s), "nrLDPC_hip_ulsch_channel_compensation")
     return records
+
+
+# ---------------------------------------------------------------------------------------------------------
+# UL receive front from the OFDM grid (include/nrLDPC_hip.h: the _grid calls, extract_host, pusch_grid_segments)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_ulsch_channel_level_grid", "nrLDPC_hip_ulsch_channel_compensation_grid", "nrLDPC_hip_ulsch_extract_host",
+            "nrLDPC_hip_pusch_grid_segments"]
+RXG_FULL, RXG_DMRS1, RXG_DMRS2 = 0, 1, 2
+
+
+class nrLDPC_hip_rx_grid_seg_t(C.Structure):
+    _fields_ = [("tb", C.c_uint32), ("Qm", C.c_uint8), ("pattern", C.c_uint8), ("pad", C.c_uint8 * 2), ("nb_re", C.c_uint32),
+                ("plane", C.c_uint32), ("sym_off", C.c_uint32), ("fft_size", C.c_uint32), ("start_re", C.c_uint32), ("pad2", C.c_uint32),
+                ("rx_off", C.c_uint64), ("ch_off", C.c_uint64), ("rec_off", C.c_uint64)]
+
+
+class nrLDPC_hip_pusch_alloc_t(C.Structure):
+    _fields_ = [("tb", C.c_uint32), ("Qm", C.c_uint8), ("dmrs_config_type", C.c_uint8), ("num_dmrs_cdm_grps_no_data", C.c_uint8),
+                ("dmrs_symbol", C.c_uint8), ("fft_size", C.c_uint32), ("first_carrier_offset", C.c_uint32), ("bwp_start", C.c_uint32),
+                ("rb_start", C.c_uint32), ("rb_size", C.c_uint32), ("start_symbol", C.c_uint32), ("nr_of_symbols", C.c_uint32),
+                ("ul_dmrs_symb_pos", C.c_uint32), ("plane", C.c_uint32), ("pad", C.c_uint32), ("rx_slot_off", C.c_uint64),
+                ("ch_off", C.c_uint64), ("rec_off", C.c_uint64)]
+
+
+_RXG_SEG_KEYS = ("tb", "Qm", "pattern", "nb_re", "plane", "sym_off", "fft_size", "start_re", "rx_off", "ch_off", "rec_off")
+_RXG_ALLOC_KEYS = ("tb", "Qm", "dmrs_config_type", "num_dmrs_cdm_grps_no_data", "dmrs_symbol", "fft_size", "first_carrier_offset", "bwp_start",
+                   "rb_start", "rb_size", "start_symbol", "nr_of_symbols", "ul_dmrs_symb_pos", "plane", "rx_slot_off", "ch_off", "rec_off")
+
+
+def _rxg_lib():
+    L = load_library()
+    P = C.POINTER(nrLDPC_hip_rx_grid_seg_t)
+    L.nrLDPC_hip_ulsch_channel_level_grid.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, P, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_channel_level_grid.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_channel_compensation_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, P, C.c_uint32, C.c_void_p,
+                                                             C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_channel_compensation_grid.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_extract_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.nrLDPC_hip_ulsch_extract_host.restype = C.c_int32
+    L.nrLDPC_hip_pusch_grid_segments.argtypes = [C.POINTER(nrLDPC_hip_pusch_alloc_t), C.c_uint32, P, C.c_uint32, P, C.POINTER(C.c_uint32)]
+    L.nrLDPC_hip_pusch_grid_segments.restype = C.c_int32
+    return L
+
+
+def _rx_grid_seg_array(segs):
+    """dicts with the fields of nrLDPC_hip_rx_grid_seg_t -> an array of them; the library checks the values"""
+    arr = (nrLDPC_hip_rx_grid_seg_t * max(len(segs), 1))()
+    for i, s in enumerate(segs):
+        arr[i] = nrLDPC_hip_rx_grid_seg_t(**{k: (s.get(k, 0) & 0xff if k in ("Qm", "pattern") else s.get(k, 0)) for k in _RXG_SEG_KEYS})
+    return arr
+
+
+def _rxg_p(pattern, j):
+    return 2 * j + 1 if pattern == RXG_DMRS1 else (6 * (j // 4) + 2 + j % 4 if pattern == RXG_DMRS2 else j)
+
+
+def _rxg_check_extent(segs, n_rx, rx_stride, ch_stride, rx_len, ch_len):
+    """The calls do not know the arrays' extents; the wrappers do.  rx_len / ch_len in c16, None where an array is not read."""
+    for s in segs:
+        if s["nb_re"] == 0 or s.get("pattern", 0) > 2 or not 0 <= s["start_re"] < s["fft_size"]:
+            continue                                                   # the library names what is wrong with those
+        last = _rxg_p(s["pattern"], s["nb_re"] - 1)
+        if last >= s["fft_size"]:
+            continue
+        if ch_len is not None and s["ch_off"] + (n_rx - 1) * ch_stride + last + 1 > ch_len:
+            raise ValueError("a segment's channel estimates leave the array")
+        if rx_len is not None:
+            top = s["start_re"] + last + 1 if s["start_re"] + last < s["fft_size"] else s["fft_size"]
+            if s["rx_off"] + (n_rx - 1) * rx_stride + top > rx_len:
+                raise ValueError("a segment's REs leave the grid array")
+
+
+def ulsch_extract_host(rx_sym, ch_sym, pattern, fft_size, start_re, nb_re):
+    """nr_ulsch_extract_rbs of one OFDM symbol of one antenna on the CPU (csrc/nr_rx_grid.h, no GPU): rx_sym = int16 [fft_size, 2],
+    the symbol of the grid; ch_sym = int16 [>= p(nb_re - 1) + 1, 2], the estimates from PUSCH subcarrier 0.  Returns (rxFext,
+    chFext), int16 [nb_re, 2] each."""
+    rx_sym, ch_sym = np.ascontiguousarray(rx_sym, np.int16).reshape(-1), np.ascontiguousarray(ch_sym, np.int16).reshape(-1)
+    if pattern in (0, 1, 2) and 0 <= start_re < fft_size and nb_re and _rxg_p(pattern, nb_re - 1) < fft_size:
+        assert rx_sym.size >= 2 * fft_size and ch_sym.size >= 2 * (_rxg_p(pattern, nb_re - 1) + 1)
+    a, b = np.zeros((max(nb_re, 1), 2), np.int16), np.zeros((max(nb_re, 1), 2), np.int16)
+    _check(_rxg_lib().nrLDPC_hip_ulsch_extract_host(rx_sym.ctypes.data, ch_sym.ctypes.data, pattern, fft_size, start_re, nb_re, a.ctypes.data,
+                                                    b.ctypes.data), "nrLDPC_hip_ulsch_extract_host")
+    return a[:nb_re], b[:nb_re]
+
+
+def pusch_grid_segments(allocs, cap=None):
+    """nrLDPC_hip_pusch_grid_segments: allocs = dicts with the fields of nrLDPC_hip_pusch_alloc_t.  Returns (segs, first_sym), lists
+    of dicts with the fields of nrLDPC_hip_rx_grid_seg_t."""
+    n = len(allocs)
+    arr = (nrLDPC_hip_pusch_alloc_t * max(n, 1))()
+    for i, a in enumerate(allocs):
+        arr[i] = nrLDPC_hip_pusch_alloc_t(**{k: a.get(k, 0) for k in _RXG_ALLOC_KEYS})
+    cap = 14 * n if cap is None else cap
+    out, first, n_out = (nrLDPC_hip_rx_grid_seg_t * max(cap, 1))(), (nrLDPC_hip_rx_grid_seg_t * max(n, 1))(), C.c_uint32(0)
+    _check(_rxg_lib().nrLDPC_hip_pusch_grid_segments(arr, n, out, cap, first, C.byref(n_out)), "nrLDPC_hip_pusch_grid_segments")
+    as_dict = lambda g: {k: int(getattr(g, k)) for k in _RXG_SEG_KEYS}
+    return [as_dict(out[i]) for i in range(n_out.value)], [as_dict(first[i]) for i in range(n)]
+
+
+def ulsch_channel_level_grid(ch, n_rx, ch_ant_stride, first_sym, out=None, stream=None):
+    """nrLDPC_hip_ulsch_channel_level_grid: ch = the full-width channel estimates, first_sym = one grid descriptor per block
+    (pusch_grid_segments).  numpy int16 -> host call, returns int32[n_tb]; torch int16 CUDA tensor -> device call enqueued on
+    `stream` into `out` (torch int32 CUDA, >= n_tb elements); returns `out`."""
+    L = _rxg_lib()
+    n, arr = len(first_sym), _rx_grid_seg_array(first_sym)
+    if isinstance(ch, np.ndarray):
+        assert ch.dtype == np.int16 and ch.flags.c_contiguous
+        _rxg_check_extent(first_sym, n_rx, 0, ch_ant_stride, None, ch.size // 2)
+        res = np.zeros(max(n, 1), np.int32)
+        _check(L.nrLDPC_hip_ulsch_channel_level_grid(ch.ctypes.data, n_rx, ch_ant_stride, arr, n, res.ctypes.data, MEM_HOST, None),
+               "nrLDPC_hip_ulsch_channel_level_grid")
+        return res[:n]
+    import torch
+    assert ch.is_cuda and ch.dtype == torch.int16 and ch.is_contiguous()
+    assert out is not None and out.is_cuda and out.device == ch.device and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
+    _rxg_check_extent(first_sym, n_rx, 0, ch_ant_stride, None, ch.numel() // 2)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_ulsch_channel_level_grid(ch.data_ptr(), n_rx, ch_ant_stride, arr, n, out.data_ptr(), MEM_DEVICE, s),
+           "nrLDPC_hip_ulsch_channel_level_grid")
+    return out
+
+
+def ulsch_channel_compensation_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, shift, records, stream=None):
+    """nrLDPC_hip_ulsch_channel_compensation_grid: rx = the OFDM grid, ch = the full-width channel estimates, segs = the grid
+    descriptors (pusch_grid_segments); shift and records as ulsch_channel_compensation.  numpy arrays -> host call; torch CUDA
+    tensors -> device call enqueued on `stream`.  Returns `records`."""
+    L = _rxg_lib()
+    arr = _rx_grid_seg_array(segs)
+    if isinstance(rx, np.ndarray):
+        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (rx, ch, records))
+        _rxg_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.size // 2, ch.size // 2)
+        sh = np.ascontiguousarray(shift, np.int32)
+        _check(L.nrLDPC_hip_ulsch_channel_compensation_grid(rx.ctypes.data, ch.ctypes.data, n_rx, rx_ant_stride, ch_ant_stride, arr, len(segs),
+                                                            sh.ctypes.data, records.ctypes.data, MEM_HOST, None),
+               "nrLDPC_hip_ulsch_channel_compensation_grid")
+        return records
+    import torch
+    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == rx.device for a in (rx, ch, records))
+    assert shift.is_cuda and shift.dtype == torch.int32 and shift.is_contiguous() and shift.device == rx.device
+    _rxg_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.numel() // 2, ch.numel() // 2)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_ulsch_channel_compensation_grid(rx.data_ptr(), ch.data_ptr(), n_rx, rx_ant_stride, ch_ant_stride, arr, len(segs),
+                                                        shift.data_ptr(), records.data_ptr(), MEM_DEVICE, s),
+           "nrLDPC_hip_ulsch_channel_compensation_grid")
+    return records

@@ -10,6 +10,11 @@ filler (four decode calls) that keeps the GPU busy while the host enqueues, and 
 descriptor upload and the kernel -- not the host's enqueueing.  The yardstick for the compensation kernel is nrLDPC_hip_ulsch_llr
 on the same number of REs (64 launches, one per block), timed the same way in the same run; both as a share of the HBM peak with
 bytes counted from the shapes (compensation: 8 n_rx in + 2 Qm out per RE; ulsch_llr: 2 Qm in + 2 Qm out).
+
+The grid leg: the same REs laid into OFDM grids (N = 4096, first_carrier_offset = N - 6 * 273, one type-1 DMRS symbol per block) and
+read by nrLDPC_hip_ulsch_channel_compensation_grid, against the launch above on the pre-extracted arrays and a plain device copy
+that moves the same number of bytes (half of them read, half written), the three alternating inside one loop so that they see the
+same machine; the records of the two launches are compared.
 """
 import json
 import sys
@@ -134,4 +139,76 @@ for key, t, b in (("compensation", res["compensation_ms"], comp_bytes), ("ulsch_
     res[key + "_share_of_hbm_peak"] = {k: b / (t[k2] * 1e-3) / HBM_PEAK for k, k2 in (("mean", "mean"), ("best", "min"), ("worst", "max"))}
     res[key + "_spread"] = (t["max"] - t["min"]) / t["mean"]
 res["front_over_slot"] = (res["level_ms"]["mean"] + res["compensation_ms"]["mean"]) / res["level_compensation_decode_ms"]["mean"]
+
+# ---- the grid leg ----
+N = 4096
+allocs = [dict(tb=i, Qm=Qm, dmrs_config_type=0, num_dmrs_cdm_grps_no_data=1, dmrs_symbol=2, fft_size=N, first_carrier_offset=N - 6 * rb, bwp_start=0,
+               rb_start=0, rb_size=rb, start_symbol=0, nr_of_symbols=13, ul_dmrs_symb_pos=1 << 2, plane=S, rx_slot_off=i * 14 * N, ch_off=i * 14 * N,
+               rec_off=int(rec_off[i])) for i in range(n)]
+gsegs, gfirst = m.pusch_grid_segments(allocs)
+assert [g["nb_re"] for g in gsegs] == [s_["nb_re"] for s_ in segs] and [g["sym_off"] for g in gsegs] == [s_["sym_off"] for s_ in segs]
+gstride = n * 14 * N
+LG = m._rxg_lib()
+gseg_arr, gfirst_arr = m._rx_grid_seg_array(gsegs), m._rx_grid_seg_array(gfirst)
+with torch.cuda.stream(side):
+    rx_g = torch.zeros(n_rx, gstride, 2, dtype=torch.int16, device="cuda")
+    ch_g = torch.zeros(n_rx, gstride, 2, dtype=torch.int16, device="cuda")
+    j12, j6 = torch.arange(12 * rb, device="cuda"), 2 * torch.arange(6 * rb, device="cuda") + 1
+    for g, e in zip(gsegs, segs):
+        p_idx = j6 if g["pattern"] == m.RXG_DMRS1 else j12
+        rx_g[:, g["rx_off"] + (g["start_re"] + p_idx) % N] = rx[:, e["rx_off"]:e["rx_off"] + e["nb_re"]]
+        ch_g[:, g["ch_off"] + p_idx] = ch[:, e["ch_off"]:e["ch_off"] + e["nb_re"]]      # flat per block: every symbol writes the same estimates
+    rec_g = torch.zeros_like(rec)
+    shift_g = torch.zeros_like(shift)
+    copy_src = torch.zeros(comp_bytes // 2, dtype=torch.uint8, device="cuda")
+    copy_dst = torch.zeros_like(copy_src)
+torch.cuda.synchronize()
+
+
+def level_grid():
+    assert LG.nrLDPC_hip_ulsch_channel_level_grid(ch_g.data_ptr(), n_rx, gstride, gfirst_arr, n, shift_g.data_ptr(), m.MEM_DEVICE, s_ptr) == 0, m.last_error()
+
+
+def compensation_grid():
+    assert LG.nrLDPC_hip_ulsch_channel_compensation_grid(rx_g.data_ptr(), ch_g.data_ptr(), n_rx, gstride, gstride, gseg_arr, len(gsegs), shift.data_ptr(),
+                                                         rec_g.data_ptr(), m.MEM_DEVICE, s_ptr) == 0, m.last_error()
+
+
+def device_copy():
+    copy_dst.copy_(copy_src)
+
+
+with torch.cuda.stream(side):
+    level()
+    compensation()
+    level_grid()
+    compensation_grid()
+torch.cuda.synchronize()
+res["grid_equals_extracted"] = bool(torch.equal(rec_g, rec)) and bool(torch.equal(shift_g, shift))
+legs = {"compensation_grid": compensation_grid, "compensation_extracted": compensation, "device_copy": device_copy}
+for fn in legs.values():
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            fn()
+torch.cuda.synchronize()
+ts = {k: [] for k in legs}
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+for _ in range(reps):
+    for k, fn in legs.items():
+        with torch.cuda.stream(side):
+            filler()
+            e0.record()
+            fn()
+            e1.record()
+        torch.cuda.synchronize()
+        ts[k].append(e0.elapsed_time(e1))
+res["grid_leg"] = {"fft_size": N, "rb": rb, "dmrs": "type 1, one symbol", "bytes_each": comp_bytes}
+for k, v in ts.items():
+    res["grid_leg"][k + "_ms"] = {"mean": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v)), "median": float(np.median(v))}
+    res["grid_leg"][k + "_share_of_hbm_peak"] = {"mean": comp_bytes / (float(np.mean(v)) * 1e-3) / HBM_PEAK, "best": comp_bytes / (float(np.min(v)) * 1e-3) / HBM_PEAK}
+    res["grid_leg"][k + "_spread"] = (float(np.max(v)) - float(np.min(v))) / float(np.mean(v))
+res["grid_leg"]["grid_over_extracted"] = {"mean": float(np.mean(ts["compensation_grid"]) / np.mean(ts["compensation_extracted"])),
+                                          "median": float(np.median(ts["compensation_grid"]) / np.median(ts["compensation_extracted"])),
+                                          "min": float(np.min(ts["compensation_grid"]) / np.min(ts["compensation_extracted"]))}
+res["level_grid_ms"] = timed(level_grid)
 print(json.dumps(res))
