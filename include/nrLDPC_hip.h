@@ -492,6 +492,63 @@ int32_t nrLDPC_hip_ulsch_extract_host(const int16_t *rxdataF, const int16_t *ul_
 int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_rx_grid_seg_t *seg_out, uint32_t cap,
                                        nrLDPC_hip_rx_grid_seg_t *first_sym_out, uint32_t *n_seg_out);
 /* ---------------------------------------------------------------------------------------------------
+ * PUSCH DMRS channel estimation from the OFDM grid: nr_pusch_channel_estimation (openair1/PHY/NR_ESTIMATION/
+ * nr_ul_channel_estimation.c:67-473) for one list of descriptors, one per (allocation, DMRS symbol), times n_rx antennas.  It
+ * writes the full-width estimates that the _grid calls above read, so that channel_estimation -> channel_level_grid ->
+ * channel_compensation_grid -> ulsch_decode_symbols on one stream takes a slot from rxdataF to payload bytes.  csrc/nr_chest.h
+ * defines the arithmetic once for host and device, bit for bit the reference's: the pilots of nr_pusch_dmrs_rx, and the four
+ * estimators NRLDPC_HIP_CHEST_TYPE1_INTERP / _TYPE2_INTERP (chest_freq = 0) and _TYPE1_AVG / _TYPE2_AVG (chest_freq = 1).
+ * For antenna a the symbol is read at c16 index rx_off + a rx_ant_stride + subcarrier (the grid wraps at fft_size; start_re is
+ * bwp_start_subcarrier) and exactly 12 rb_size c16 are written at ch_off + a ch_ant_stride, overwritten: the reference's memset
+ * of the whole symbol and its TYPE1_INTERP spill of four entries behind the allocation are not reproduced.  est_delay holds
+ * one int32 per (descriptor, antenna) at delay_off + a, the value nr_est_delay would have found (the search itself, a
+ * fixed-point IDFT, is not built); NULL means 0 everywhere.  max_ch and nvar are not produced.  Deviations from the
+ * reference: TYPE2_AVG reads every RE relative to the descriptor's symbol and PRB b uses pilots 4b .. 4b + 3.
+ * mem = HOST stages one contiguous span of the grid, from the lowest to the highest c16 any (descriptor, antenna) pair reads,
+ * works on a bounce of the span of estimates from the lowest to the highest c16 written, and copies only the write set back to
+ * ul_ch: the spans grow with the distance between descriptors and with the antenna strides.  mem = DEVICE enqueues on `stream`;
+ * the first call per (GPU, fft_size) also allocates that size's delay table (41 fft_size c16, kept until the process ends) and
+ * uploads it with a synchronous copy, so it blocks: run one call per fft_size at start-up where the first slot must not wait.
+ * Refused before anything is enqueued: NULL arrays, n_rx outside 1..8, an unknown mode, a port outside 0..7 (type 1) / 0..11
+ * (type 2), rb_size = 0, 12 rb_size > fft_size, start_re >= fft_size, an fft_size other than 128, 256, 512, 1024, 1536, 2048,
+ * 4096, 6144, 8192, c_init >= 2^31, dmrs_offset > 2^20, a descriptor whose nushift would move a read to index fft_size, output
+ * ranges of two (descriptor, antenna) pairs that overlap, a misaligned or foreign device pointer, a capturing stream.
+ * pusch_chest_host: one descriptor, antenna 0, on the CPU from the same header, no GPU (rx_off and ch_off apply).
+ * pusch_dmrs_host: n conjugated pilots from sequence symbol dmrs_offset on (type 0: type 1, 1: type 2).
+ * delay_table_host: row get_delay_idx(delay) of the delay table of fft_size (fft_size c16).
+ * pusch_chest_segments (host only): one descriptor per DMRS symbol of each allocation, in symbol order; ch_off = the
+ * allocation's ch_off + symbol fft_size, where nrLDPC_hip_pusch_grid_segments makes the grid calls read when dmrs_symbol names
+ * that symbol; delay_off = descriptor index times n_rx; c_init as nr_gold_pusch (nr_gold.c:107-108). */
+#define NRLDPC_HIP_CHEST_TYPE1_INTERP 0
+#define NRLDPC_HIP_CHEST_TYPE2_INTERP 1
+#define NRLDPC_HIP_CHEST_TYPE1_AVG 2
+#define NRLDPC_HIP_CHEST_TYPE2_AVG 3
+typedef struct nrLDPC_hip_chest_seg {
+  uint8_t mode;         /* NRLDPC_HIP_CHEST_* */
+  uint8_t port;         /* antenna port p - 1000 */
+  uint8_t pad[2];
+  uint32_t fft_size;    /* N, the OFDM symbol size */
+  uint32_t start_re;    /* grid subcarrier of PUSCH subcarrier 0, < N */
+  uint32_t rb_size;
+  uint32_t dmrs_offset; /* first sequence symbol: 12 (bwp_start + rb_start) / 2 (type 1) or / 3 (type 2) */
+  uint32_t c_init;      /* of the symbol's Gold sequence */
+  uint32_t delay_off;   /* index of antenna 0's entry in est_delay */
+  uint32_t pad2;
+  uint64_t rx_off;      /* c16 offset of antenna 0's subcarrier 0 of the DMRS symbol in rxdataF */
+  uint64_t ch_off;      /* c16 offset of antenna 0's estimate of PUSCH subcarrier 0 in ul_ch */
+} nrLDPC_hip_chest_seg_t;
+typedef struct nrLDPC_hip_pusch_chest_cfg {
+  uint32_t slot, scid, dmrs_scrambling_id, port;
+  uint32_t chest_freq;  /* 0: interpolation in frequency, 1: average per PRB */
+} nrLDPC_hip_pusch_chest_cfg_t;
+int32_t nrLDPC_hip_pusch_channel_estimation(const int16_t *rxdataF, uint64_t rx_ant_stride, int16_t *ul_ch, uint64_t ch_ant_stride, uint32_t n_rx,
+                                            const nrLDPC_hip_chest_seg_t *seg, uint32_t n_seg, const int32_t *est_delay, int32_t mem, void *stream);
+int32_t nrLDPC_hip_pusch_chest_host(const int16_t *rxdataF, const nrLDPC_hip_chest_seg_t *seg, int32_t est_delay, int16_t *ul_ch);
+int32_t nrLDPC_hip_pusch_dmrs_host(uint32_t c_init, uint32_t dmrs_offset, uint32_t n, uint32_t port, uint32_t type, int16_t *out);
+int32_t nrLDPC_hip_delay_table_host(uint32_t fft_size, int32_t delay, int16_t *out);
+int32_t nrLDPC_hip_pusch_chest_segments(const nrLDPC_hip_pusch_alloc_t *alloc, const nrLDPC_hip_pusch_chest_cfg_t *cfg, uint32_t n_alloc, uint32_t n_rx,
+                                        nrLDPC_hip_chest_seg_t *seg_out, uint32_t cap, uint32_t *n_seg_out);
+/* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one
  * segment per call, rate (de)matching + (de)interleaving + HARQ combining inside, soft buffers kept on the device per

@@ -7,6 +7,7 @@
  * library -- without a usable GPU LDPCinit() fails and every other entry point returns an error.
  */
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +31,8 @@
 #include "tb_tx_scr.h"
 #include "nr_rx_front.h"
 #include "nr_rx_grid.h"
+#include "nr_chest.h"
+#include "tb_rx_chest.h"
 #include "tb_rx_front.h"
 #include "ldpc_enc_packed_core.h"
 
@@ -1504,3 +1507,4 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "qam_api.inc.cpp"
 #include "rx_front_api.inc.cpp"
 #include "rx_grid_api.inc.cpp"
+#include "rx_chest_api.inc.cpp"

@@ -1356,3 +1356,128 @@ def ulsch_channel_compensation_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, 
                                                         shift.data_ptr(), records.data_ptr(), MEM_DEVICE, s),
            "nrLDPC_hip_ulsch_channel_compensation_grid")
     return records
+
+
+# ---------------------------------------------------------------------------------------------------------
+# PUSCH DMRS channel estimation (include/nrLDPC_hip.h: pusch_channel_estimation and its host forms; csrc/nr_chest.h)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_pusch_channel_estimation", "nrLDPC_hip_pusch_chest_host", "nrLDPC_hip_pusch_dmrs_host", "nrLDPC_hip_delay_table_host",
+            "nrLDPC_hip_pusch_chest_segments"]
+CHEST_TYPE1_INTERP, CHEST_TYPE2_INTERP, CHEST_TYPE1_AVG, CHEST_TYPE2_AVG = 0, 1, 2, 3
+
+
+class nrLDPC_hip_chest_seg_t(C.Structure):
+    _fields_ = [("mode", C.c_uint8), ("port", C.c_uint8), ("pad", C.c_uint8 * 2), ("fft_size", C.c_uint32), ("start_re", C.c_uint32),
+                ("rb_size", C.c_uint32), ("dmrs_offset", C.c_uint32), ("c_init", C.c_uint32), ("delay_off", C.c_uint32), ("pad2", C.c_uint32),
+                ("rx_off", C.c_uint64), ("ch_off", C.c_uint64)]
+
+
+class nrLDPC_hip_pusch_chest_cfg_t(C.Structure):
+    _fields_ = [("slot", C.c_uint32), ("scid", C.c_uint32), ("dmrs_scrambling_id", C.c_uint32), ("port", C.c_uint32), ("chest_freq", C.c_uint32)]
+
+
+_CHEST_SEG_KEYS = ("mode", "port", "fft_size", "start_re", "rb_size", "dmrs_offset", "c_init", "delay_off", "rx_off", "ch_off")
+_CHEST_CFG_KEYS = ("slot", "scid", "dmrs_scrambling_id", "port", "chest_freq")
+
+
+def _chest_lib():
+    L = load_library()
+    P = C.POINTER(nrLDPC_hip_chest_seg_t)
+    L.nrLDPC_hip_pusch_channel_estimation.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, P, C.c_uint32, C.c_void_p, C.c_int32,
+                                                      C.c_void_p]
+    L.nrLDPC_hip_pusch_channel_estimation.restype = C.c_int32
+    L.nrLDPC_hip_pusch_chest_host.argtypes = [C.c_void_p, P, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_pusch_chest_host.restype = C.c_int32
+    L.nrLDPC_hip_pusch_dmrs_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.nrLDPC_hip_pusch_dmrs_host.restype = C.c_int32
+    L.nrLDPC_hip_delay_table_host.argtypes = [C.c_uint32, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_delay_table_host.restype = C.c_int32
+    L.nrLDPC_hip_pusch_chest_segments.argtypes = [C.POINTER(nrLDPC_hip_pusch_alloc_t), C.POINTER(nrLDPC_hip_pusch_chest_cfg_t), C.c_uint32, C.c_uint32, P,
+                                                  C.c_uint32, C.POINTER(C.c_uint32)]
+    L.nrLDPC_hip_pusch_chest_segments.restype = C.c_int32
+    return L
+
+
+def _chest_seg_array(segs):
+    """dicts with the fields of nrLDPC_hip_chest_seg_t -> an array of them; the library checks the values"""
+    arr = (nrLDPC_hip_chest_seg_t * max(len(segs), 1))()
+    for i, s in enumerate(segs):
+        arr[i] = nrLDPC_hip_chest_seg_t(**{k: (s.get(k, 0) & 0xff if k in ("mode", "port") else s.get(k, 0)) for k in _CHEST_SEG_KEYS})
+    return arr
+
+
+def _chest_check_extent(segs, n_rx, rx_stride, ch_stride, rx_len, ch_len, delay_len):
+    """The call does not know the arrays' extents; the wrappers do.  Lengths in c16 (rx, ch) and int32 (delay, None = no array)."""
+    for s in segs:
+        if s["rb_size"] == 0 or 12 * s["rb_size"] > s["fft_size"]:
+            continue                                                   # the library names what is wrong with those
+        if s["rx_off"] + (n_rx - 1) * rx_stride + s["fft_size"] > rx_len:
+            raise ValueError("a descriptor's OFDM symbol leaves the grid array")
+        if s["ch_off"] + (n_rx - 1) * ch_stride + 12 * s["rb_size"] > ch_len:
+            raise ValueError("a descriptor's channel estimates leave the array")
+        if delay_len is not None and s.get("delay_off", 0) + n_rx > delay_len:
+            raise ValueError("a descriptor's delays leave the est_delay array")
+
+
+def delay_table_host(fft_size, delay):
+    """Row get_delay_idx(delay) of the delay table of fft_size: int16 [fft_size, 2]."""
+    out = np.zeros((max(fft_size, 1), 2), np.int16)
+    _check(_chest_lib().nrLDPC_hip_delay_table_host(fft_size, delay, out.ctypes.data), "nrLDPC_hip_delay_table_host")
+    return out
+
+
+def pusch_dmrs_host(c_init, dmrs_offset, n, port, dmrs_type):
+    """n conjugated PUSCH DMRS pilots from sequence symbol dmrs_offset on (dmrs_type 0: type 1, 1: type 2): int16 [n, 2]."""
+    out = np.zeros((max(n, 1), 2), np.int16)
+    _check(_chest_lib().nrLDPC_hip_pusch_dmrs_host(c_init, dmrs_offset, n, port, dmrs_type, out.ctypes.data), "nrLDPC_hip_pusch_dmrs_host")
+    return out[:n]
+
+
+def pusch_chest_host(rx, seg, est_delay, ch):
+    """nrLDPC_hip_pusch_chest_host: one descriptor, antenna 0, on the CPU (csrc/nr_chest.h, no GPU).  rx = int16 grid, ch = int16
+    estimates (written in place at seg's ch_off).  Returns ch."""
+    assert rx.dtype == np.int16 and ch.dtype == np.int16 and rx.flags.c_contiguous and ch.flags.c_contiguous
+    _chest_check_extent([seg], 1, 0, 0, rx.size // 2, ch.size // 2, None)
+    arr = _chest_seg_array([seg])
+    _check(_chest_lib().nrLDPC_hip_pusch_chest_host(rx.ctypes.data, arr, est_delay, ch.ctypes.data), "nrLDPC_hip_pusch_chest_host")
+    return ch
+
+
+def pusch_chest_segments(allocs, cfgs, n_rx, cap=None):
+    """nrLDPC_hip_pusch_chest_segments: allocs = dicts with the fields of nrLDPC_hip_pusch_alloc_t, cfgs = parallel dicts with slot,
+    scid, dmrs_scrambling_id, port, chest_freq.  Returns a list of dicts with the fields of nrLDPC_hip_chest_seg_t."""
+    n = len(allocs)
+    assert len(cfgs) == n
+    arr, carr = (nrLDPC_hip_pusch_alloc_t * max(n, 1))(), (nrLDPC_hip_pusch_chest_cfg_t * max(n, 1))()
+    for i, (a, c) in enumerate(zip(allocs, cfgs)):
+        arr[i] = nrLDPC_hip_pusch_alloc_t(**{k: a.get(k, 0) for k in _RXG_ALLOC_KEYS})
+        carr[i] = nrLDPC_hip_pusch_chest_cfg_t(**{k: c.get(k, 0) for k in _CHEST_CFG_KEYS})
+    cap = 14 * n if cap is None else cap
+    out, n_out = (nrLDPC_hip_chest_seg_t * max(cap, 1))(), C.c_uint32(0)
+    _check(_chest_lib().nrLDPC_hip_pusch_chest_segments(arr, carr, n, n_rx, out, cap, C.byref(n_out)), "nrLDPC_hip_pusch_chest_segments")
+    return [{k: int(getattr(out[i], k)) for k in _CHEST_SEG_KEYS} for i in range(n_out.value)]
+
+
+def pusch_channel_estimation(rx, rx_ant_stride, ch, ch_ant_stride, n_rx, segs, est_delay=None, stream=None):
+    """nrLDPC_hip_pusch_channel_estimation: rx = the OFDM grid, ch = the full-width channel estimates (written), segs = the
+    descriptors (pusch_chest_segments), est_delay = int32 per (descriptor, antenna) or None (0 everywhere).  numpy int16 arrays
+    -> host call; torch int16 CUDA tensors -> device call enqueued on `stream`.  Returns ch."""
+    L = _chest_lib()
+    arr = _chest_seg_array(segs)
+    if isinstance(rx, np.ndarray):
+        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (rx, ch))
+        dl = None if est_delay is None else np.ascontiguousarray(est_delay, np.int32)
+        _chest_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.size // 2, ch.size // 2, None if dl is None else dl.size)
+        _check(L.nrLDPC_hip_pusch_channel_estimation(rx.ctypes.data, rx_ant_stride, ch.ctypes.data, ch_ant_stride, n_rx, arr, len(segs),
+                                                     None if dl is None else dl.ctypes.data, MEM_HOST, None), "nrLDPC_hip_pusch_channel_estimation")
+        return ch
+    import torch
+    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == rx.device for a in (rx, ch))
+    if est_delay is not None:
+        assert est_delay.is_cuda and est_delay.dtype == torch.int32 and est_delay.is_contiguous() and est_delay.device == rx.device
+    _chest_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.numel() // 2, ch.numel() // 2, None if est_delay is None else est_delay.numel())
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_pusch_channel_estimation(rx.data_ptr(), rx_ant_stride, ch.data_ptr(), ch_ant_stride, n_rx, arr, len(segs),
+                                                 None if est_delay is None else est_delay.data_ptr(), MEM_DEVICE, s),
+           "nrLDPC_hip_pusch_channel_estimation")
+    return ch
