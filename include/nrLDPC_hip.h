@@ -549,6 +549,96 @@ int32_t nrLDPC_hip_delay_table_host(uint32_t fft_size, int32_t delay, int16_t *o
 int32_t nrLDPC_hip_pusch_chest_segments(const nrLDPC_hip_pusch_alloc_t *alloc, const nrLDPC_hip_pusch_chest_cfg_t *cfg, uint32_t n_alloc, uint32_t n_rx,
                                         nrLDPC_hip_chest_seg_t *seg_out, uint32_t cap, uint32_t *n_seg_out);
 /* ---------------------------------------------------------------------------------------------------
+ * PDSCH resource mapping with DMRS onto the transmit grid: the resource mapping loop of nr_generate_pdsch (openair1/PHY/
+ * NR_TRANSPORT/nr_dlsch.c:205-474) and its unit-precoding copy (:483-535) for one list of descriptors, one per (allocation, OFDM
+ * symbol), times n_tx antennas -- the mirror image of pusch_channel_estimation + channel_compensation_grid, so that
+ * dlsch_encode_symbols -> pdsch_resource_mapping on one stream takes a slot from payload bytes to txdataF.  csrc/nr_pdsch_map.h
+ * defines the mapping once for host and device.
+ * Read: for layer l < Nl the nb_re c16 at int16 offset lay_off + 2 (l plane + sym_off) of `layers` (the layer planes
+ * dlsch_encode_symbols wrote at lay_off), and the descriptors.  Written: for every descriptor and antenna a < n_tx exactly the
+ * 12 rb_size c16 at txdataF index tx_off + a tx_ant_stride + (start_re + i) mod fft_size, i = 0 .. 12 rb_size - 1, overwritten;
+ * nothing else.  Antenna a < Nl receives layer a, the antennas Nl <= a < n_tx zeros (unit precoding, pmi = 0).
+ * The value at allocation subcarrier i, by the symbol's pattern:
+ *   NRLDPC_HIP_PDM_FULL (no DMRS)  data everywhere: mulhrs(amp, x) per component, x the next entry of the layer plane.
+ *   _DMRS1 / _DMRS2 (DMRS type 1 / 2), the pilot test first as in the reference:
+ *     pilot of the layer's port  i = 4n + 2k' + delta (type 1), 6n + k' + delta (type 2); the j-th pilot of the allocation (k' =
+ *       j & 1) is the unconjugated QPSK point (nrLDPC_hip_mod_table(2)) of bits 2 (dmrs_offset + j) and the next of the Gold
+ *       sequence of c_init, times Wt[l_prime] Wf[k'] amp at shift 15, flooring; delta, Wf, Wt: nr_sch_dmrs.c:37-57
+ *     data                       i % 2 >= ncdm (type 1), i % 6 >= 2 ncdm (type 2): x amp >> 15, truncating (not mulhrs)
+ *     everything else            0
+ * Deviations from the reference: every data RE of a FULL symbol is mulhrs (the reference's scalar tail, the
+ * last len % 4 REs of each piece of a symbol, omits the final shift, :428-435, :460-467), and the pattern is decided by i, never
+ * by the grid subcarrier (allowed_xlsch_re_in_dmrs_symbol takes diff = fft_size at the first subcarrier, dmrs_nr.c:45-48).
+ * PTRS, precoding matrices other than unit, interleaved VRB mapping and CSI-RS / SSB collisions are not built.
+ * mem = HOST: synchronous; stages the span of the layer planes the descriptors reach, works on a bounce of the span of the grid
+ * from the lowest to the highest c16 written, and copies only the write set back.  mem = DEVICE enqueues on `stream` (one launch
+ * per pattern present); the descriptors go through the calling thread's page-locked job area.
+ * Refused before anything is enqueued or written: NULL arrays, n_tx outside 1..8 or below a descriptor's Nl, a pattern that is
+ * none of the three, Nl outside 1..4, (DMRS symbols) ncdm outside 1..2 (type 1) / 1..3 (type 2), l_prime > 1, a port outside
+ * 0..7 (type 1) / 0..11 (type 2), c_init >= 2^31, dmrs_offset > 2^20; amp <= 0, rb_size = 0, 12 rb_size > fft_size, start_re >=
+ * fft_size, an fft_size other than 128, 256, 512, 1024, 1536, 2048, 4096, 6144, 8192, nb_re that is not the pattern's number of
+ * data REs (rb_size times those of a PRB, the same for every layer's port), sym_off + nb_re > plane, lay_off odd, output
+ * ranges of two (descriptor, antenna) pairs that overlap, another mem value, (DEVICE) an array that is not device memory of
+ * one GPU or not 4-byte aligned, a capturing stream; nrLDPC_hip_last_error() names the reason.  The calls do not know the
+ * arrays' extents; the Python wrappers, which do, refuse a descriptor that reaches outside.
+ * pdsch_map_host: one descriptor and one antenna on the CPU from the same header, no GPU: layer 0 .. Nl - 1 maps that layer,
+ * a negative layer writes the zeros of an antenna behind the layers; tx_off and lay_off apply.  0 / -1.
+ * pdsch_dmrs_host: n unconjugated pilots (before Wt Wf amp) from sequence symbol dmrs_offset on.
+ * pdsch_map_segments (host only, no GPU): one descriptor per OFDM symbol of each allocation, in symbol order: start_re =
+ * (first_carrier_offset + (rb_start + bwp_start) 12) % fft_size (:208-210), dmrs_offset = (rb_start + bwp_start) 6 (type 1) or 4
+ * (type 2), without bwp_start when si_rnti (:260-263), l_prime by the reference's rule (:229-230, :264-269) starting from the
+ * lowest set bit of dl_dmrs_symb_pos, layer l's port the l-th set bit of dmrs_ports (get_dmrs_port, nr_common.c:494; an empty
+ * bitmap is port 0), c_init as nr_init_pdsch_dmrs (nr_gold.c:87-88), sym_off the running sum of nb_re, tx_off = tx_slot_off +
+ * symbol fft_size.  Refused: start_symbol + nr_of_symbols > 14, nr_of_symbols = 0, no port for a layer, the running sum
+ * different from plane at the end, scid > 1, dl_dmrs_scrambling_id > 65535, slot >= 160, amp outside 1..32767, more than cap
+ * descriptors, and anything the mapping call would refuse. */
+#define NRLDPC_HIP_PDM_FULL 0
+#define NRLDPC_HIP_PDM_DMRS1 1
+#define NRLDPC_HIP_PDM_DMRS2 2
+typedef struct nrLDPC_hip_pdsch_map_seg {
+  uint8_t pattern;      /* NRLDPC_HIP_PDM_* */
+  uint8_t Nl;           /* layers, 1..4 */
+  uint8_t ncdm;         /* numDmrsCdmGrpsNoData (DMRS symbols) */
+  uint8_t l_prime;      /* 0, or 1 for the second symbol of a double-symbol DMRS */
+  uint8_t port[4];      /* layer l's antenna port p - 1000 (DMRS symbols) */
+  int16_t amp;          /* > 0 */
+  uint16_t pad;
+  uint32_t fft_size;    /* N, the OFDM symbol size */
+  uint32_t start_re;    /* grid subcarrier of PDSCH subcarrier 0, < N */
+  uint32_t rb_size;
+  uint32_t nb_re;       /* data REs per layer in this OFDM symbol */
+  uint32_t sym_off;     /* first entry of each layer plane this symbol takes */
+  uint32_t plane;       /* c16 values per layer plane (G / (Qm Nl)) */
+  uint32_t dmrs_offset; /* first sequence symbol (DMRS symbols) */
+  uint32_t c_init;      /* of the symbol's Gold sequence (DMRS symbols) */
+  uint32_t pad2;
+  uint64_t tx_off;      /* c16 offset of antenna 0's subcarrier 0 of this OFDM symbol in txdataF */
+  uint64_t lay_off;     /* int16 offset of the block's dlsch_encode_symbols output in layers, even */
+} nrLDPC_hip_pdsch_map_seg_t;
+typedef struct nrLDPC_hip_pdsch_alloc {
+  uint32_t Nl;
+  uint32_t plane;                     /* c16 values per layer plane (G / (Qm Nl)) */
+  uint32_t dmrs_config_type;          /* 0: type 1, 1: type 2 */
+  uint32_t num_dmrs_cdm_grps_no_data;
+  uint32_t dmrs_ports;                /* bit p: port p carries a layer, lowest first */
+  uint32_t scid, dl_dmrs_scrambling_id, slot;
+  uint32_t si_rnti;                   /* != 0: the DMRS reference point leaves bwp_start out */
+  int32_t amp;
+  uint32_t fft_size;                  /* N */
+  uint32_t first_carrier_offset;
+  uint32_t bwp_start, rb_start, rb_size;
+  uint32_t start_symbol, nr_of_symbols;
+  uint32_t dl_dmrs_symb_pos;          /* bit s: symbol s carries DMRS */
+  uint64_t tx_slot_off;               /* c16 offset of antenna 0's symbol 0, subcarrier 0 of the slot in txdataF */
+  uint64_t lay_off;                   /* int16 offset of the block's dlsch_encode_symbols output in layers, even */
+} nrLDPC_hip_pdsch_alloc_t;
+int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdataF, uint64_t tx_ant_stride, uint32_t n_tx,
+                                          const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, int32_t mem, void *stream);
+int32_t nrLDPC_hip_pdsch_map_host(const int16_t *layers, const nrLDPC_hip_pdsch_map_seg_t *seg, int32_t layer, int16_t *txdataF);
+int32_t nrLDPC_hip_pdsch_dmrs_host(uint32_t c_init, uint32_t dmrs_offset, uint32_t n, int16_t *out);
+int32_t nrLDPC_hip_pdsch_map_segments(const nrLDPC_hip_pdsch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_pdsch_map_seg_t *seg_out, uint32_t cap,
+                                      uint32_t *n_seg_out);
+/* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one
  * segment per call, rate (de)matching + (de)interleaving + HARQ combining inside, soft buffers kept on the device per

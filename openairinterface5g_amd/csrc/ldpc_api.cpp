@@ -33,6 +33,8 @@
 #include "nr_rx_grid.h"
 #include "nr_chest.h"
 #include "tb_rx_chest.h"
+#include "nr_pdsch_map.h"
+#include "tb_tx_map.h"
 #include "tb_rx_front.h"
 #include "ldpc_enc_packed_core.h"
 
@@ -1508,3 +1510,4 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "rx_front_api.inc.cpp"
 #include "rx_grid_api.inc.cpp"
 #include "rx_chest_api.inc.cpp"
+#include "tx_map_api.inc.cpp"

@@ -1,0 +1,401 @@
+/*
+ * tx_map_api.inc.cpp -- PDSCH resource mapping with DMRS onto the transmit grid: the GPU call, its CPU check forms and the
+ * descriptors of a PDSCH allocation (included at the end of ldpc_api.cpp, behind rx_chest_api.inc.cpp whose checks and
+ * conventions it shares).  The arithmetic: nr_pdsch_map.h; the kernel: tb_tx_map.hip.  Everything the kernel indexes with is
+ * checked here, before anything is enqueued.
+ */
+
+namespace {
+
+int txm_check_seg(const char *who, const nrLDPC_hip_pdsch_map_seg_t &g)
+{
+  const std::string w(who);
+  if (g.pattern >= NR_PDM_PATTERNS)
+    return set_error((w + ": pattern must be FULL, DMRS1 or DMRS2").c_str());
+  if (g.Nl < 1 || g.Nl > NR_PDM_MAX_LAYERS)
+    return set_error((w + ": Nl must be 1..4").c_str());
+  if (g.amp <= 0)
+    return set_error((w + ": amp must be positive").c_str());
+  if (!che_fft_ok(g.fft_size))
+    return set_error((w + ": fft_size must be 128, 256, 512, 1024, 1536, 2048, 4096, 6144 or 8192").c_str());
+  if (g.rb_size == 0)
+    return set_error((w + ": rb_size is 0").c_str());
+  if ((uint64_t)g.rb_size * 12u > g.fft_size)
+    return set_error((w + ": the allocation is wider than fft_size").c_str());
+  if (g.start_re >= g.fft_size)
+    return set_error((w + ": start_re must be below fft_size").c_str());
+  if (g.lay_off & 1u)
+    return set_error((w + ": lay_off must be even").c_str());
+  if (g.pattern != NR_PDM_FULL) {
+    if (g.ncdm < 1 || g.ncdm > nr_pdm_max_ncdm(g.pattern))
+      return set_error((w + ": ncdm must be 1..2 for type 1 and 1..3 for type 2").c_str());
+    if (g.l_prime > 1)
+      return set_error((w + ": l_prime must be 0 or 1").c_str());
+    for (uint32_t l = 0; l < g.Nl; l++)
+      if (g.port[l] >= nr_pdm_ports(g.pattern))
+        return set_error((w + ": port must be 0..7 for type 1 and 0..11 for type 2").c_str());
+    if (g.c_init >> 31)
+      return set_error((w + ": c_init must be below 2^31").c_str());
+    if (g.dmrs_offset > (1u << 20))
+      return set_error((w + ": dmrs_offset above 2^20").c_str());
+  }
+  for (uint32_t l = 0; l < g.Nl; l++) {
+    uint32_t pm, dm;
+    nr_pdm_masks(g.pattern, g.ncdm, nr_pdm_delta(g.pattern, g.port[l]), &pm, &dm);
+    if (g.nb_re != g.rb_size * nr_pdm_popc(dm))
+      return set_error((w + ": nb_re is not the number of data REs of the pattern (for every layer's port)").c_str());
+  }
+  if ((uint64_t)g.sym_off + g.nb_re > g.plane)
+    return set_error((w + ": sym_off + nb_re is above plane").c_str());
+  return 0;
+}
+
+/* one descriptor, one antenna on the CPU: lay = the symbol's stretch of the layer's plane (NULL: zeros), sym = the symbol's
+ * subcarrier 0 */
+int txm_host_one(const nrLDPC_hip_pdsch_map_seg_t &g, const uint32_t *lay, uint32_t layer, uint32_t *sym)
+{
+  const uint32_t n_re = 12u * g.rb_size;
+  if (!lay) {
+    for (uint32_t i = 0; i < n_re; i++)
+      sym[nr_pdm_wrap(g.start_re, i, g.fft_size)] = 0u;
+    return 0;
+  }
+  const nr_pdm_sym s = nr_pdm_sym_make(g.pattern, g.ncdm, g.l_prime, g.port[layer], g.amp);
+  std::vector<uint32_t> gold;
+  const uint32_t w0 = (2u * g.dmrs_offset) >> 5;
+  if (g.pattern != NR_PDM_FULL) {
+    gold.resize(((2u * (g.dmrs_offset + nr_pdm_count(s.pmask, n_re))) >> 5) - w0 + 3u);
+    if (nr_hip_gold_words(g.c_init, w0, (uint32_t)gold.size(), gold.data()) != 0)
+      return set_error("pdsch_map_host: the Gold sequence could not be generated");
+  }
+  for (uint32_t i = 0; i < n_re; i++) {
+    uint64_t bits = 0;
+    const uint32_t jlo = nr_pdm_count(s.pmask, i);
+    if (g.pattern != NR_PDM_FULL)
+      bits = che_unit_bits(gold, w0, 2u * (g.dmrs_offset + jlo));
+    sym[nr_pdm_wrap(g.start_re, i, g.fft_size)] = nr_pdm_re(&s, lay, i, bits, jlo);
+  }
+  return 0;
+}
+
+struct TxMapPlan {
+  std::vector<tx_map_job> jobs;
+  std::vector<tx_map_wg> wgs; /* sorted by pattern */
+  uint32_t n_wg[NR_PDM_PATTERNS] = {0, 0, 0};
+  uint64_t lay_lo = UINT64_MAX, lay_hi = 0, out_lo = UINT64_MAX, out_hi = 0; /* c16 */
+};
+
+/* checks and ranges; the workgroup table needs the address the grid is written at (txm_plan_wgs) */
+int txm_plan(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, TxMapPlan &p)
+{
+  struct Range { uint64_t lo, hi; };
+  std::vector<Range> out;
+  p.jobs.resize(n_seg);
+  for (uint32_t i = 0; i < n_seg; i++) {
+    const nrLDPC_hip_pdsch_map_seg_t &g = seg[i];
+    if (txm_check_seg("pdsch_resource_mapping", g) != 0)
+      return -1;
+    if (n_tx < g.Nl)
+      return set_error("pdsch_resource_mapping: n_tx is below a descriptor's Nl");
+    const uint64_t lay0 = g.lay_off / 2u + g.sym_off;
+    p.lay_lo = std::min(p.lay_lo, lay0);
+    p.lay_hi = std::max(p.lay_hi, lay0 + (uint64_t)(g.Nl - 1u) * g.plane + g.nb_re);
+    const uint32_t n_re = 12u * g.rb_size, first = std::min(n_re, g.fft_size - g.start_re);
+    for (uint32_t a = 0; a < n_tx; a++) {
+      const uint64_t base = g.tx_off + (uint64_t)a * tx_stride;
+      out.push_back(Range{base + g.start_re, base + g.start_re + first});
+      if (first < n_re)
+        out.push_back(Range{base, base + (n_re - first)});
+    }
+    tx_map_job &j = p.jobs[i];
+    memset(&j, 0, sizeof j);
+    j.tx_off = g.tx_off;
+    j.lay_off = lay0;
+    j.plane = g.plane;
+    j.fft_size = g.fft_size;
+    j.start_re = g.start_re;
+    j.n_re = n_re;
+    j.dmrs_offset = g.dmrs_offset;
+    j.Nl = g.Nl;
+    j.ncdm = g.ncdm;
+    j.l_prime = g.l_prime;
+    j.amp = g.amp;
+    for (uint32_t l = 0; l < g.Nl; l++)
+      j.ports |= (uint32_t)g.port[l] << (8u * l);
+  }
+  for (const Range &r : out) {
+    p.out_lo = std::min(p.out_lo, r.lo);
+    p.out_hi = std::max(p.out_hi, r.hi);
+  }
+  std::sort(out.begin(), out.end(), [](const Range &a, const Range &b) { return a.lo < b.lo; });
+  for (size_t i = 1; i < out.size(); i++)
+    if (out[i].lo < out[i - 1].hi)
+      return set_error("pdsch_resource_mapping: the output ranges of two (descriptor, antenna) pairs overlap");
+  return 0;
+}
+
+/* the workgroup table, pattern by pattern; tx = the address the kernel is given, the jobs' tx_off as they will be launched */
+void txm_plan_wgs(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, const void *tx, TxMapPlan &p)
+{
+  const uint64_t word0 = (uint64_t)(reinterpret_cast<uintptr_t>(tx) >> 2);
+  for (uint32_t pattern = 0; pattern < NR_PDM_PATTERNS; pattern++)
+    for (uint32_t i = 0; i < n_seg; i++) {
+      const nrLDPC_hip_pdsch_map_seg_t &g = seg[i];
+      if (g.pattern != pattern)
+        continue;
+      const tx_map_job &j = p.jobs[i];
+      for (uint32_t a = 0; a < n_tx; a++) {
+        tx_map_wg w{};
+        w.job = i;
+        w.ant = a;
+        w.phase = (uint32_t)((word0 + j.tx_off + (uint64_t)a * tx_stride + j.start_re) & 3u);
+        uint32_t pm = 0, dm = 0;
+        if (a < g.Nl)
+          nr_pdm_masks(pattern, g.ncdm, nr_pdm_delta(pattern, g.port[a]), &pm, &dm);
+        for (uint32_t q = 0; (uint64_t)q * NR_TXM_THREADS * NR_TXM_GROUP < (uint64_t)j.n_re + w.phase; q++) {
+          w.piece = q;
+          if (pm) {
+            const uint32_t i_first = q ? q * NR_TXM_THREADS * NR_TXM_GROUP - w.phase : 0u;
+            w.w0 = (2u * (g.dmrs_offset + nr_pdm_count(pm, i_first))) >> 5;
+            nr_gold_jump(&che_gold_tables(), g.c_init, w.w0, &w.x1, &w.x2);
+          }
+          p.wgs.push_back(w);
+          p.n_wg[pattern]++;
+        }
+      }
+    }
+}
+
+size_t txm_jobs_bytes(const TxMapPlan &p) { return align_up(p.wgs.size() * sizeof(tx_map_wg), 16) + align_up(p.jobs.size() * sizeof(tx_map_job), 16); }
+void txm_write_jobs(const TxMapPlan &p, uint8_t *dst)
+{
+  memcpy(dst, p.wgs.data(), p.wgs.size() * sizeof(tx_map_wg));
+  memcpy(dst + align_up(p.wgs.size() * sizeof(tx_map_wg), 16), p.jobs.data(), p.jobs.size() * sizeof(tx_map_job));
+}
+
+/* the launches over the uploaded tables at `base` */
+int txm_launch(const TxMapPlan &p, const uint8_t *base, const uint32_t *lay, uint32_t *tx, uint64_t tx_stride, hipStream_t s)
+{
+  const tx_map_wg *wgs = reinterpret_cast<const tx_map_wg *>(base);
+  const tx_map_job *jobs = reinterpret_cast<const tx_map_job *>(base + align_up(p.wgs.size() * sizeof(tx_map_wg), 16));
+  uint32_t first = 0;
+  for (uint32_t pattern = 0; pattern < NR_PDM_PATTERNS; pattern++) {
+    HIP_TRY(nr_launch_tx_map(pattern, wgs + first, p.n_wg[pattern], jobs, lay, tx, tx_stride, s));
+    first += p.n_wg[pattern];
+  }
+  return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t nrLDPC_hip_pdsch_dmrs_host(uint32_t c_init, uint32_t dmrs_offset, uint32_t n, int16_t *out)
+{
+  if (n && !out)
+    return set_error("null argument");
+  if (c_init >> 31)
+    return set_error("pdsch_dmrs_host: c_init must be below 2^31");
+  if (dmrs_offset > (1u << 20) || n > (1u << 20))
+    return set_error("pdsch_dmrs_host: dmrs_offset or n above 2^20");
+  if (n == 0)
+    return 0;
+  const uint32_t w0 = (2u * dmrs_offset) >> 5;
+  std::vector<uint32_t> gold(((2u * (dmrs_offset + n) - 1u) >> 5) - w0 + 1u);
+  if (nr_hip_gold_words(c_init, w0, (uint32_t)gold.size(), gold.data()) != 0)
+    return set_error("pdsch_dmrs_host: the Gold sequence could not be generated");
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t bit = 2u * (dmrs_offset + k) - 32u * w0;
+    const uint32_t c = nr_qam_point(2u, (gold[bit >> 5] >> (bit & 31u)) & 3u);
+    out[2 * (size_t)k] = (int16_t)(c & 0xffffu);
+    out[2 * (size_t)k + 1] = (int16_t)(c >> 16);
+  }
+  return 0;
+}
+
+int32_t nrLDPC_hip_pdsch_map_host(const int16_t *layers, const nrLDPC_hip_pdsch_map_seg_t *seg, int32_t layer, int16_t *txdataF)
+{
+  if (!seg || !txdataF || (layer >= 0 && !layers))
+    return set_error("null argument");
+  if (txm_check_seg("pdsch_map_host", *seg) != 0)
+    return -1;
+  if (layer >= (int32_t)seg->Nl)
+    return set_error("pdsch_map_host: layer must be below Nl, or negative for an antenna behind the layers");
+  const uint32_t *lay = layer < 0 ? nullptr : reinterpret_cast<const uint32_t *>(layers) + seg->lay_off / 2u + (uint64_t)layer * seg->plane + seg->sym_off;
+  return txm_host_one(*seg, lay, layer < 0 ? 0u : (uint32_t)layer, reinterpret_cast<uint32_t *>(txdataF) + seg->tx_off);
+}
+
+int32_t nrLDPC_hip_pdsch_map_segments(const nrLDPC_hip_pdsch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_pdsch_map_seg_t *seg_out, uint32_t cap,
+                                      uint32_t *n_seg_out)
+{
+  if (!n_seg_out || (n_alloc && !alloc) || (cap && !seg_out))
+    return set_error("null argument");
+  std::vector<nrLDPC_hip_pdsch_map_seg_t> segs;
+  for (uint32_t i = 0; i < n_alloc; i++) {
+    const nrLDPC_hip_pdsch_alloc_t &a = alloc[i];
+    const uint32_t N = a.fft_size, type = a.dmrs_config_type;
+    if (a.nr_of_symbols == 0 || a.start_symbol >= NR_RXG_SYMBOLS || a.nr_of_symbols > NR_RXG_SYMBOLS - a.start_symbol)
+      return set_error("pdsch_map_segments: the symbols must lie within the slot's 14");
+    if (a.Nl < 1 || a.Nl > NR_PDM_MAX_LAYERS)
+      return set_error("pdsch_map_segments: Nl must be 1..4");
+    if (type > 1)
+      return set_error("pdsch_map_segments: dmrs_config_type must be 0 (type 1) or 1 (type 2)");
+    if (a.amp < 1 || a.amp > 32767)
+      return set_error("pdsch_map_segments: amp must be 1..32767");
+    if (a.rb_size == 0)
+      return set_error("pdsch_map_segments: rb_size is 0");
+    if (N == 0 || (uint64_t)a.rb_size * 12u > N)
+      return set_error("pdsch_map_segments: the allocation is wider than fft_size");
+    if (a.first_carrier_offset >= N)
+      return set_error("pdsch_map_segments: first_carrier_offset must be below fft_size");
+    if (a.scid > 1)
+      return set_error("pdsch_map_segments: scid must be 0 or 1");
+    if (a.dl_dmrs_scrambling_id > 0xffffu)
+      return set_error("pdsch_map_segments: dl_dmrs_scrambling_id above 65535");
+    if (a.slot >= 160)
+      return set_error("pdsch_map_segments: slot must be below 160");
+    if ((uint64_t)a.bwp_start + a.rb_start > (1u << 16))
+      return set_error("pdsch_map_segments: bwp_start + rb_start above 2^16");
+    /* get_dmrs_port (nr_common.c:494-511): layer l takes the l-th set bit; an empty bitmap (DCI 1_0) is port 0 */
+    uint8_t port[NR_PDM_MAX_LAYERS] = {0, 0, 0, 0};
+    for (uint32_t l = 0; l < a.Nl; l++) {
+      int32_t found = -1, p = a.dmrs_ports == 0 ? 0 : -1;
+      for (uint32_t b = 0; b < 12u && p < 0; b++)
+        if (((a.dmrs_ports >> b) & 1u) && ++found == (int32_t)l)
+          p = (int32_t)b;
+      if (p < 0)
+        return set_error("pdsch_map_segments: dmrs_ports has no port for a layer");
+      port[l] = (uint8_t)p;
+    }
+    uint32_t l_overline = 0; /* get_l0 (nr_sch_dmrs.c:89-98) */
+    while (l_overline < 14u && !((a.dl_dmrs_symb_pos >> l_overline) & 1u))
+      l_overline++;
+    uint32_t l_prime = 0, m = 0;
+    for (uint32_t sym = a.start_symbol; sym < a.start_symbol + a.nr_of_symbols; sym++) {
+      nrLDPC_hip_pdsch_map_seg_t g;
+      memset(&g, 0, sizeof g);
+      const bool dmrs = (a.dl_dmrs_symb_pos >> sym) & 1u;
+      g.pattern = (uint8_t)(dmrs ? (type == 0 ? NR_PDM_DMRS1 : NR_PDM_DMRS2) : NR_PDM_FULL);
+      g.Nl = (uint8_t)a.Nl;
+      g.amp = (int16_t)a.amp;
+      g.fft_size = N;
+      g.start_re = nr_rxg_start_re(a.first_carrier_offset, a.bwp_start, a.rb_start, N);
+      g.rb_size = a.rb_size;
+      g.plane = a.plane;
+      g.sym_off = m;
+      g.tx_off = a.tx_slot_off + (uint64_t)sym * N;
+      g.lay_off = a.lay_off;
+      if (dmrs) {
+        if (a.num_dmrs_cdm_grps_no_data > 255u)
+          return set_error("pdsch_map_segments: num_dmrs_cdm_grps_no_data must be 1..2 for type 1 and 1..3 for type 2");
+        g.ncdm = (uint8_t)a.num_dmrs_cdm_grps_no_data;
+        if (sym == l_overline + 1u) /* :264-269 */
+          l_prime = 1;
+        else if (sym > l_overline + 1u) {
+          l_overline = sym;
+          l_prime = 0;
+        }
+        g.l_prime = (uint8_t)l_prime;
+        memcpy(g.port, port, sizeof port);
+        g.dmrs_offset = (a.rb_start + (a.si_rnti ? 0u : a.bwp_start)) * (type == 0 ? 6u : 4u); /* :260-263 */
+        /* nr_gold.c:87-88 */
+        g.c_init = (uint32_t)(((1ull << 17) * (NR_RXG_SYMBOLS * a.slot + sym + 1u) * (2ull * a.dl_dmrs_scrambling_id + 1u) + 2ull * a.dl_dmrs_scrambling_id +
+                               a.scid) & 0x7fffffffull);
+      }
+      uint32_t pm, dm;
+      nr_pdm_masks(g.pattern, g.ncdm, nr_pdm_delta(g.pattern, port[0] < nr_pdm_ports(g.pattern) ? port[0] : 0u), &pm, &dm);
+      g.nb_re = a.rb_size * nr_pdm_popc(dm);
+      if ((uint64_t)m + g.nb_re > a.plane)
+        return set_error("pdsch_map_segments: the data REs of the symbols add up to more than plane");
+      if (txm_check_seg("pdsch_map_segments", g) != 0)
+        return -1;
+      m += g.nb_re;
+      segs.push_back(g);
+    }
+    if (m != a.plane)
+      return set_error("pdsch_map_segments: the data REs of the symbols do not add up to plane");
+  }
+  if (segs.size() > cap)
+    return set_error("pdsch_map_segments: more descriptors than cap");
+  if (!segs.empty())
+    memcpy(seg_out, segs.data(), segs.size() * sizeof segs[0]);
+  *n_seg_out = (uint32_t)segs.size();
+  return 0;
+}
+
+int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdataF, uint64_t tx_ant_stride, uint32_t n_tx,
+                                          const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, int32_t mem, void *stream)
+{
+  if (n_tx < 1 || n_tx > NR_PDM_MAX_TX)
+    return set_error("pdsch_resource_mapping: n_tx must be 1..8");
+  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
+    return set_error("pdsch_resource_mapping: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (n_seg && (!layers || !txdataF || !seg))
+    return set_error("null argument");
+  TxMapPlan p;
+  if (txm_plan(seg, n_seg, n_tx, tx_ant_stride, p) != 0)
+    return -1;
+  if (n_seg == 0)
+    return 0;
+  if (mem == NRLDPC_HIP_MEM_DEVICE) {
+    const int ord = scr_device_ordinal(txdataF);
+    if (ord < 0 || !rxf_dev_ok(txdataF, ord) || !rxf_dev_ok(layers, ord))
+      return set_error("pdsch_resource_mapping: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
+    Device *dv = device_for_ordinal(ord);
+    if (!dv)
+      return -1;
+    UseDevice use(*dv);
+    if (rxf_check_stream("pdsch_resource_mapping", static_cast<hipStream_t>(stream)) != 0)
+      return -1;
+    txm_plan_wgs(seg, n_seg, n_tx, tx_ant_stride, txdataF, p);
+    TbCtx &c = tls_tb;
+    hipStream_t s;
+    const size_t bytes = txm_jobs_bytes(p);
+    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 || c.jobs_d.ensure(bytes) != 0)
+      return -1;
+    txm_write_jobs(p, c.jobs_h.p);
+    if (tb_upload_jobs(c, c.jobs_d.p, bytes, s) != 0)
+      return -1;
+    return txm_launch(p, c.jobs_d.p, reinterpret_cast<const uint32_t *>(layers), reinterpret_cast<uint32_t *>(txdataF), tx_ant_stride, s);
+  }
+  if (ensure_ready() != 0)
+    return -1;
+  UseDevice use(g.dev[0]);
+  ThreadCtx &c = tls_ctx;
+  /* the device reads a copy of the span of the layer planes the descriptors reach and works on a bounce of the span of the grid
+   * from the lowest to the highest c16 written */
+  for (uint32_t i = 0; i < n_seg; i++) {
+    p.jobs[i].tx_off -= p.out_lo;
+    p.jobs[i].lay_off -= p.lay_lo;
+  }
+  const size_t lay_b = align_up((size_t)(p.lay_hi - p.lay_lo) * 4u, 16), out_b = (size_t)(p.out_hi - p.out_lo) * 4u;
+  /* the table's size does not depend on the phases: one piece more per (descriptor, antenna) at the most */
+  size_t max_wg = 0;
+  for (uint32_t i = 0; i < n_seg; i++)
+    max_wg += (size_t)n_tx * ((12u * (size_t)seg[i].rb_size + 3u) / (NR_TXM_THREADS * NR_TXM_GROUP) + 1u);
+  const size_t jobs_cap = align_up(max_wg * sizeof(tx_map_wg), 16) + align_up(p.jobs.size() * sizeof(tx_map_job), 16);
+  if (c.ensure(jobs_cap + lay_b, out_b) != 0)
+    return -1;
+  txm_plan_wgs(seg, n_seg, n_tx, tx_ant_stride, c.d_out, p);
+  const size_t jobs_b = txm_jobs_bytes(p);
+  txm_write_jobs(p, c.h_in);
+  memcpy(c.h_in + jobs_b, layers + 2 * p.lay_lo, (size_t)(p.lay_hi - p.lay_lo) * 4u);
+  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + lay_b, hipMemcpyHostToDevice, c.stream));
+  if (txm_launch(p, c.d_in, reinterpret_cast<const uint32_t *>(c.d_in + jobs_b), reinterpret_cast<uint32_t *>(c.d_out), tx_ant_stride, c.stream) != 0)
+    return -1;
+  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_b, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  /* only the write set goes to the caller's array */
+  for (uint32_t i = 0; i < n_seg; i++) {
+    const uint32_t n_re = 12u * seg[i].rb_size, first = std::min(n_re, seg[i].fft_size - seg[i].start_re);
+    for (uint32_t a = 0; a < n_tx; a++) {
+      const uint64_t base = seg[i].tx_off + (uint64_t)a * tx_ant_stride;
+      memcpy(txdataF + 2 * (base + seg[i].start_re), c.h_out + 4u * (base + seg[i].start_re - p.out_lo), (size_t)first * 4u);
+      if (first < n_re)
+        memcpy(txdataF + 2 * base, c.h_out + 4u * (base - p.out_lo), (size_t)(n_re - first) * 4u);
+    }
+  }
+  return 0;
+}
+
+} /* extern "C" */

@@ -1481,3 +1481,119 @@ def pusch_channel_estimation(rx, rx_ant_stride, ch, ch_ant_stride, n_rx, segs, e
                                                  None if est_delay is None else est_delay.data_ptr(), MEM_DEVICE, s),
            "nrLDPC_hip_pusch_channel_estimation")
     return ch
+
+
+# ---------------------------------------------------------------------------------------------------------
+# PDSCH resource mapping with DMRS (include/nrLDPC_hip.h: pdsch_resource_mapping and its host forms; csrc/nr_pdsch_map.h)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_pdsch_resource_mapping", "nrLDPC_hip_pdsch_map_host", "nrLDPC_hip_pdsch_dmrs_host", "nrLDPC_hip_pdsch_map_segments"]
+PDM_FULL, PDM_DMRS1, PDM_DMRS2 = 0, 1, 2
+
+
+class nrLDPC_hip_pdsch_map_seg_t(C.Structure):
+    _fields_ = [("pattern", C.c_uint8), ("Nl", C.c_uint8), ("ncdm", C.c_uint8), ("l_prime", C.c_uint8), ("port", C.c_uint8 * 4), ("amp", C.c_int16),
+                ("pad", C.c_uint16), ("fft_size", C.c_uint32), ("start_re", C.c_uint32), ("rb_size", C.c_uint32), ("nb_re", C.c_uint32),
+                ("sym_off", C.c_uint32), ("plane", C.c_uint32), ("dmrs_offset", C.c_uint32), ("c_init", C.c_uint32), ("pad2", C.c_uint32),
+                ("tx_off", C.c_uint64), ("lay_off", C.c_uint64)]
+
+
+class nrLDPC_hip_pdsch_alloc_t(C.Structure):
+    _fields_ = [("Nl", C.c_uint32), ("plane", C.c_uint32), ("dmrs_config_type", C.c_uint32), ("num_dmrs_cdm_grps_no_data", C.c_uint32),
+                ("dmrs_ports", C.c_uint32), ("scid", C.c_uint32), ("dl_dmrs_scrambling_id", C.c_uint32), ("slot", C.c_uint32), ("si_rnti", C.c_uint32),
+                ("amp", C.c_int32), ("fft_size", C.c_uint32), ("first_carrier_offset", C.c_uint32), ("bwp_start", C.c_uint32), ("rb_start", C.c_uint32),
+                ("rb_size", C.c_uint32), ("start_symbol", C.c_uint32), ("nr_of_symbols", C.c_uint32), ("dl_dmrs_symb_pos", C.c_uint32),
+                ("tx_slot_off", C.c_uint64), ("lay_off", C.c_uint64)]
+
+
+_PDM_SEG_KEYS = ("pattern", "Nl", "ncdm", "l_prime", "port", "amp", "fft_size", "start_re", "rb_size", "nb_re", "sym_off", "plane", "dmrs_offset",
+                 "c_init", "tx_off", "lay_off")
+_PDM_ALLOC_KEYS = tuple(f[0] for f in nrLDPC_hip_pdsch_alloc_t._fields_)
+
+
+def _pdm_lib():
+    L = load_library()
+    P = C.POINTER(nrLDPC_hip_pdsch_map_seg_t)
+    L.nrLDPC_hip_pdsch_resource_mapping.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, P, C.c_uint32, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_pdsch_resource_mapping.restype = C.c_int32
+    L.nrLDPC_hip_pdsch_map_host.argtypes = [C.c_void_p, P, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_pdsch_map_host.restype = C.c_int32
+    L.nrLDPC_hip_pdsch_dmrs_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.nrLDPC_hip_pdsch_dmrs_host.restype = C.c_int32
+    L.nrLDPC_hip_pdsch_map_segments.argtypes = [C.POINTER(nrLDPC_hip_pdsch_alloc_t), C.c_uint32, P, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.nrLDPC_hip_pdsch_map_segments.restype = C.c_int32
+    return L
+
+
+def _pdm_seg_array(segs):
+    """dicts with the fields of nrLDPC_hip_pdsch_map_seg_t (port = a sequence of up to 4) -> an array of them; the library checks the
+    values"""
+    arr = (nrLDPC_hip_pdsch_map_seg_t * max(len(segs), 1))()
+    for i, s in enumerate(segs):
+        kw = {k: s.get(k, 0) for k in _PDM_SEG_KEYS if k != "port"}
+        for k in ("pattern", "Nl", "ncdm", "l_prime"):
+            kw[k] &= 0xff
+        ports = list(s.get("port", ())) + [0] * 4
+        arr[i] = nrLDPC_hip_pdsch_map_seg_t(port=(C.c_uint8 * 4)(*[p & 0xff for p in ports[:4]]), **kw)
+    return arr
+
+
+def _pdm_check_extent(segs, n_tx, tx_stride, lay_len, tx_len):
+    """The calls do not know the arrays' extents; the wrappers do.  Lengths in c16."""
+    for s in segs:
+        if s["rb_size"] == 0 or 12 * s["rb_size"] > s["fft_size"] or not 1 <= s.get("Nl", 0) <= 4 or s["lay_off"] & 1:
+            continue                                                   # the library names what is wrong with those
+        if s["tx_off"] + (n_tx - 1) * tx_stride + min(s["start_re"] + 12 * s["rb_size"], s["fft_size"]) > tx_len:
+            raise ValueError("a descriptor's OFDM symbol leaves the grid array")
+        if lay_len is not None and s["lay_off"] // 2 + (s["Nl"] - 1) * s["plane"] + s["sym_off"] + s["nb_re"] > lay_len:
+            raise ValueError("a descriptor's layer entries leave the layers array")
+
+
+def pdsch_dmrs_host(c_init, dmrs_offset, n):
+    """n unconjugated PDSCH DMRS pilots (before Wt Wf amp) from sequence symbol dmrs_offset on: int16 [n, 2]."""
+    out = np.zeros((max(n, 1), 2), np.int16)
+    _check(_pdm_lib().nrLDPC_hip_pdsch_dmrs_host(c_init, dmrs_offset, n, out.ctypes.data), "nrLDPC_hip_pdsch_dmrs_host")
+    return out[:n]
+
+
+def pdsch_map_host(layers, seg, layer, tx):
+    """nrLDPC_hip_pdsch_map_host: one descriptor, one antenna, on the CPU (csrc/nr_pdsch_map.h, no GPU).  layers = int16 layer planes,
+    layer = 0 .. Nl - 1 or negative for the zeros of an antenna behind the layers, tx = int16 grid (written in place at seg's tx_off).
+    Returns tx."""
+    assert layers.dtype == np.int16 and tx.dtype == np.int16 and layers.flags.c_contiguous and tx.flags.c_contiguous
+    _pdm_check_extent([seg], 1, 0, layers.size // 2, tx.size // 2)
+    _check(_pdm_lib().nrLDPC_hip_pdsch_map_host(layers.ctypes.data, _pdm_seg_array([seg]), layer, tx.ctypes.data), "nrLDPC_hip_pdsch_map_host")
+    return tx
+
+
+def pdsch_map_segments(allocs, cap=None):
+    """nrLDPC_hip_pdsch_map_segments: allocs = dicts with the fields of nrLDPC_hip_pdsch_alloc_t.  Returns a list of dicts with the
+    fields of nrLDPC_hip_pdsch_map_seg_t."""
+    n = len(allocs)
+    arr = (nrLDPC_hip_pdsch_alloc_t * max(n, 1))()
+    for i, a in enumerate(allocs):
+        arr[i] = nrLDPC_hip_pdsch_alloc_t(**{k: a.get(k, 0) for k in _PDM_ALLOC_KEYS})
+    cap = 14 * n if cap is None else cap
+    out, n_out = (nrLDPC_hip_pdsch_map_seg_t * max(cap, 1))(), C.c_uint32(0)
+    _check(_pdm_lib().nrLDPC_hip_pdsch_map_segments(arr, n, out, cap, C.byref(n_out)), "nrLDPC_hip_pdsch_map_segments")
+    return [{k: (list(out[i].port) if k == "port" else int(getattr(out[i], k))) for k in _PDM_SEG_KEYS} for i in range(n_out.value)]
+
+
+def pdsch_resource_mapping(layers, tx, tx_ant_stride, n_tx, segs, stream=None):
+    """nrLDPC_hip_pdsch_resource_mapping: layers = the layer planes (dlsch_encode_symbols output), tx = the transmit grid (written),
+    segs = the descriptors (pdsch_map_segments).  numpy int16 arrays -> host call; torch int16 CUDA tensors -> device call enqueued
+    on `stream`.  Returns tx."""
+    L = _pdm_lib()
+    arr = _pdm_seg_array(segs)
+    if isinstance(tx, np.ndarray):
+        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (layers, tx))
+        _pdm_check_extent(segs, n_tx, tx_ant_stride, layers.size // 2, tx.size // 2)
+        _check(L.nrLDPC_hip_pdsch_resource_mapping(layers.ctypes.data, tx.ctypes.data, tx_ant_stride, n_tx, arr, len(segs), MEM_HOST, None),
+               "nrLDPC_hip_pdsch_resource_mapping")
+        return tx
+    import torch
+    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == tx.device for a in (layers, tx))
+    _pdm_check_extent(segs, n_tx, tx_ant_stride, layers.numel() // 2, tx.numel() // 2)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(L.nrLDPC_hip_pdsch_resource_mapping(layers.data_ptr(), tx.data_ptr(), tx_ant_stride, n_tx, arr, len(segs), MEM_DEVICE, s),
+           "nrLDPC_hip_pdsch_resource_mapping")
+    return tx
