@@ -18,6 +18,7 @@
 #include <dlfcn.h>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -1505,6 +1506,7 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "tb_api.inc.cpp"
 #include "dec_jobs.inc.cpp"
 #include "tb_offload.inc.cpp"
+#include "slot_call.inc.cpp"
 #include "scrambling_api.inc.cpp"
 #include "qam_api.inc.cpp"
 #include "rx_front_api.inc.cpp"

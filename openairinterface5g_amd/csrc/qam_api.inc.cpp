@@ -1,7 +1,7 @@
 /*
- * qam_api.inc.cpp -- modulation mapping, soft demapping and the UL-SCH chain call that takes symbols (included at the end of
- * ldpc_api.cpp, behind scrambling_api.inc.cpp whose checks it shares).  The constellations and the demapper: nr_qam.h; the
- * standalone kernels: tb_qam.hip; the demapper inside the chain: tb_rx_core.h (the symbol source of phase A).  And the DL-SCH
+ * qam_api.inc.cpp -- modulation mapping, soft demapping and the UL-SCH chain call that takes symbols (included into ldpc_api.cpp;
+ * uses the batch checks of scrambling_api.inc.cpp and the call scopes of slot_call.inc.cpp).  The constellations and the
+ * demapper: nr_qam.h; the standalone kernels: tb_qam.hip; the demapper inside the chain: tb_rx_core.h (the symbol source of phase A).  And the DL-SCH
  * chain call that ends in layer-mapped symbols (the fused segment kernel's symbol store: tb_tx_sym.h) with the standalone
  * layer mapping.
  */
@@ -70,36 +70,34 @@ int32_t nrLDPC_hip_modulation(const uint32_t *in, uint32_t length, uint8_t Qm, i
     return set_error("modulation: length must be a multiple of Qm");
   if (length > NR_SCR_MAX_BITS)
     return set_error("modulation: length above 2^21 bits");
-  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
-    return set_error("modulation: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (check_mem("modulation", mem) != 0)
+    return -1;
   if (length && (!in || !out))
     return set_error("null argument");
   if (length == 0)
     return 0;
   const size_t in_bytes = 4u * (size_t)((length + 31u) >> 5), out_bytes = (size_t)(length / Qm) * 4u;
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(in);
-    if (ord < 0 || scr_device_ordinal(out) != ord)
-      return set_error("modulation: DEVICE mem needs `in` and `out` in device memory of one GPU");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
+    DeviceCall dc;
+    if (dc.open("modulation", {{in, 1}, {out, 1}}, DEV_NEEDS_IN_OUT, stream) != 0)
       return -1;
-    UseDevice use(*dv);
-    HIP_TRY(nr_launch_modulation(in, length, Qm, out, static_cast<hipStream_t>(stream)));
+    HIP_TRY(nr_launch_modulation(in, length, Qm, out, dc.s));
     return 0;
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
-  if (c.ensure(align_up(in_bytes, 16), out_bytes) != 0)
+  const size_t in_o = st.take(in_bytes);
+  if (st.ensure(out_bytes) != 0)
     return -1;
-  memcpy(c.h_in, in, in_bytes);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, in_bytes, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_modulation(reinterpret_cast<const uint32_t *>(c.d_in), length, Qm, reinterpret_cast<int16_t *>(c.d_out), c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  memcpy(out, c.h_out, out_bytes);
+  memcpy(st.h(in_o), in, in_bytes);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_modulation(reinterpret_cast<const uint32_t *>(st.d(in_o)), length, Qm, reinterpret_cast<int16_t *>(st.d_out()), st.stream()));
+    return 0;
+  };
+  if (st.run(in_bytes, launch, out_bytes) != 0)
+    return -1;
+  memcpy(out, st.h_out(), out_bytes);
   return 0;
 }
 
@@ -110,8 +108,8 @@ int32_t nrLDPC_hip_ulsch_llr(const int32_t *rxdataF_comp, const int32_t *ul_ch_m
     return -1;
   if ((uint64_t)nb_re * Qm > NR_SCR_MAX_BITS)
     return set_error("ulsch_llr: nb_re * Qm above 2^21");
-  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
-    return set_error("ulsch_llr: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (check_mem("ulsch_llr", mem) != 0)
+    return -1;
   const int32_t *in[4] = {rxdataF_comp, ul_ch_mag, ul_ch_magb, ul_ch_magc};
   const uint32_t np = Qm / 2u;
   if (nb_re) {
@@ -125,39 +123,37 @@ int32_t nrLDPC_hip_ulsch_llr(const int32_t *rxdataF_comp, const int32_t *ul_ch_m
     return 0;
   const size_t plane_bytes = (size_t)nb_re * 4u, out_bytes = (size_t)nb_re * Qm * 2u;
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(llr);
-    bool ok = ord >= 0;
-    for (uint32_t k = 0; k < np; k++)
-      ok = ok && scr_device_ordinal(in[k]) == ord && (reinterpret_cast<uintptr_t>(in[k]) & 3u) == 0;
-    if (!ok)
-      return set_error("ulsch_llr: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
+    /* the planes beyond Qm / 2 are not read: NULL, as an array that was not given */
+    DeviceCall dc;
+    if (dc.open("ulsch_llr", {{llr, 1}, {in[0], 4}, {np > 1 ? in[1] : nullptr, 4}, {np > 2 ? in[2] : nullptr, 4}, {np > 3 ? in[3] : nullptr, 4}},
+                DEV_NEEDS_ALIGNED, stream) != 0)
       return -1;
-    UseDevice use(*dv);
     const uint32_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
     for (uint32_t k = 0; k < np; k++)
       pl[k] = reinterpret_cast<const uint32_t *>(in[k]);
-    HIP_TRY(nr_launch_ulsch_llr(pl, nb_re, Qm, llr, static_cast<hipStream_t>(stream)));
+    HIP_TRY(nr_launch_ulsch_llr(pl, nb_re, Qm, llr, dc.s));
     return 0;
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
-  const size_t stride = align_up(plane_bytes, 16);
-  if (c.ensure(stride * np, out_bytes) != 0)
+  size_t plane_o[4] = {0, 0, 0, 0};
+  for (uint32_t k = 0; k < np; k++)
+    plane_o[k] = st.take(plane_bytes);
+  if (st.ensure(out_bytes) != 0)
     return -1;
   const uint32_t *pl[4] = {nullptr, nullptr, nullptr, nullptr};
   for (uint32_t k = 0; k < np; k++) {
-    memcpy(c.h_in + k * stride, in[k], plane_bytes);
-    pl[k] = reinterpret_cast<const uint32_t *>(c.d_in + k * stride);
+    memcpy(st.h(plane_o[k]), in[k], plane_bytes);
+    pl[k] = reinterpret_cast<const uint32_t *>(st.d(plane_o[k]));
   }
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, stride * np, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_ulsch_llr(pl, nb_re, Qm, reinterpret_cast<int16_t *>(c.d_out), c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  memcpy(llr, c.h_out, out_bytes);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_ulsch_llr(pl, nb_re, Qm, reinterpret_cast<int16_t *>(st.d_out()), st.stream()));
+    return 0;
+  };
+  if (st.run(st.top, launch, out_bytes) != 0)
+    return -1;
+  memcpy(llr, st.h_out(), out_bytes);
   return 0;
 }
 
@@ -182,8 +178,8 @@ int32_t nrLDPC_hip_layer_mapping(const int16_t *in, uint32_t n_symbs, uint8_t Nl
   const uint32_t per_layer = n_symbs / Nl;
   if (layer_stride < per_layer)
     return set_error("layer_mapping: layer_stride below n_symbs / Nl");
-  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
-    return set_error("layer_mapping: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (check_mem("layer_mapping", mem) != 0)
+    return -1;
   if (n_symbs && (!in || !out))
     return set_error("null argument");
   if (n_symbs == 0)
@@ -193,31 +189,29 @@ int32_t nrLDPC_hip_layer_mapping(const int16_t *in, uint32_t n_symbs, uint8_t Nl
   if (i0 < o0 + ((size_t)(Nl - 1) * layer_stride * 4u + plane_bytes) && o0 < i0 + in_bytes)
     return set_error("layer_mapping: in and out overlap");
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(in);
-    if (ord < 0 || scr_device_ordinal(out) != ord)
-      return set_error("layer_mapping: DEVICE mem needs `in` and `out` in device memory of one GPU");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
+    DeviceCall dc;
+    if (dc.open("layer_mapping", {{in, 1}, {out, 1}}, DEV_NEEDS_IN_OUT, stream) != 0)
       return -1;
-    UseDevice use(*dv);
-    HIP_TRY(nr_launch_layer_mapping(in, n_symbs, Nl, out, layer_stride, static_cast<hipStream_t>(stream)));
+    HIP_TRY(nr_launch_layer_mapping(in, n_symbs, Nl, out, layer_stride, dc.s));
     return 0;
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
-  if (c.ensure(align_up(in_bytes, 16), in_bytes) != 0)
+  const size_t in_o = st.take(in_bytes);
+  if (st.ensure(in_bytes) != 0)
     return -1;
-  memcpy(c.h_in, in, in_bytes);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, in_bytes, hipMemcpyHostToDevice, c.stream));
+  memcpy(st.h(in_o), in, in_bytes);
   /* the planes side by side on the device; on the host each goes to its place (nothing between them is written) */
-  HIP_TRY(nr_launch_layer_mapping(reinterpret_cast<const int16_t *>(c.d_in), n_symbs, Nl, reinterpret_cast<int16_t *>(c.d_out), per_layer,
-                                  c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, in_bytes, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_layer_mapping(reinterpret_cast<const int16_t *>(st.d(in_o)), n_symbs, Nl, reinterpret_cast<int16_t *>(st.d_out()), per_layer,
+                                    st.stream()));
+    return 0;
+  };
+  if (st.run(in_bytes, launch, in_bytes) != 0)
+    return -1;
   for (uint32_t l = 0; l < Nl; l++)
-    memcpy(reinterpret_cast<uint8_t *>(out) + (size_t)l * layer_stride * 4u, c.h_out + l * plane_bytes, plane_bytes);
+    memcpy(reinterpret_cast<uint8_t *>(out) + (size_t)l * layer_stride * 4u, st.h_out() + l * plane_bytes, plane_bytes);
   return 0;
 }
 

@@ -1,8 +1,8 @@
 /*
  * rx_chest_api.inc.cpp -- PUSCH DMRS channel estimation: the GPU call, its CPU check forms and the descriptors of a PUSCH
- * allocation (included at the end of ldpc_api.cpp, behind rx_grid_api.inc.cpp whose checks and conventions it shares).  The
- * arithmetic: nr_chest.h; the kernel: tb_rx_chest.hip.  Everything the kernel indexes with is checked here, before anything is
- * enqueued.
+ * allocation (included into ldpc_api.cpp; uses rxf_check_common of rx_front_api.inc.cpp and the call scopes, the table layout, the
+ * overlap check and the DMRS helpers of slot_call.inc.cpp).  The arithmetic: nr_chest.h; the kernel: tb_rx_chest.hip.  Everything
+ * the kernel indexes with is checked here, before anything is enqueued.
  */
 
 namespace {
@@ -111,19 +111,12 @@ const nr_gold_tables_t &che_gold_tables()
   return t;
 }
 
-/* the pilot bits of unit u from the symbol's Gold words (word 0 = sequence word w0) */
-uint64_t che_unit_bits(const std::vector<uint32_t> &gold, uint32_t w0, uint32_t first_bit)
-{
-  const uint32_t w = (first_bit >> 5) - w0;
-  return ((uint64_t)gold[w] | ((uint64_t)gold[w + 1] << 32)) >> (first_bit & 31u);
-}
-
 /* one descriptor, one antenna on the CPU: rx = the symbol's subcarrier 0, out = 12 rb_size c16 */
 int che_host_one(const nrLDPC_hip_chest_seg_t &g, const uint32_t *rx, int32_t d, uint32_t *out)
 {
-  const uint32_t np = nr_che_pilots_per_rb(g.mode) * g.rb_size, w0 = (2u * g.dmrs_offset) >> 5, w1 = (2u * (g.dmrs_offset + np) - 1u) >> 5;
-  std::vector<uint32_t> gold(w1 - w0 + 3u);
-  if (nr_hip_gold_words(g.c_init, w0, (uint32_t)gold.size(), gold.data()) != 0)
+  std::vector<uint32_t> gold;
+  uint32_t w0;
+  if (!dmrs_gold_words(g.c_init, g.dmrs_offset, nr_che_pilots_per_rb(g.mode) * g.rb_size, gold, w0))
     return set_error("chest_host: the Gold sequence could not be generated");
   const uint32_t *fwd = nullptr, *inv = nullptr;
   {
@@ -133,7 +126,7 @@ int che_host_one(const nrLDPC_hip_chest_seg_t &g, const uint32_t *rx, int32_t d,
     inv = t.data() + (size_t)nr_che_inv_delay_idx(d) * g.fft_size;
   }
   for (uint32_t u = 0; u < nr_che_units(g.mode, g.rb_size); u++) {
-    const uint64_t bits = che_unit_bits(gold, w0, 2u * (g.dmrs_offset + nr_che_unit_first_pilot(g.mode, u)));
+    const uint64_t bits = dmrs_bits(gold, w0, g.dmrs_offset + nr_che_unit_first_pilot(g.mode, u));
     if (g.mode == NR_CHE_TYPE1_INTERP)
       nr_che_t1_interp(rx, g.fft_size, g.start_re, g.rb_size, g.port, g.dmrs_offset, bits, fwd, inv, u, out + 4u * u);
     else if (g.mode == NR_CHE_TYPE2_INTERP)
@@ -156,8 +149,7 @@ struct ChestPlan {
 
 int che_plan(const nrLDPC_hip_chest_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, ChestPlan &p)
 {
-  struct Range { uint64_t lo, hi; };
-  std::vector<Range> out;
+  std::vector<Range64> out;
   p.jobs.resize(n_seg);
   for (uint32_t i = 0; i < n_seg; i++) {
     const nrLDPC_hip_chest_seg_t &g = seg[i];
@@ -168,7 +160,7 @@ int che_plan(const nrLDPC_hip_chest_seg_t *seg, uint32_t n_seg, uint32_t n_rx, u
     p.rx_lo = std::min(p.rx_lo, g.rx_off + lo);
     p.rx_hi = std::max(p.rx_hi, g.rx_off + hi + (uint64_t)(n_rx - 1) * rx_stride);
     for (uint32_t a = 0; a < n_rx; a++)
-      out.push_back(Range{g.ch_off + (uint64_t)a * ch_stride, g.ch_off + (uint64_t)a * ch_stride + 12u * g.rb_size});
+      out.push_back(Range64{g.ch_off + (uint64_t)a * ch_stride, g.ch_off + (uint64_t)a * ch_stride + 12u * g.rb_size});
     rx_chest_job &j = p.jobs[i];
     memset(&j, 0, sizeof j);
     j.rx_off = g.rx_off;
@@ -180,14 +172,8 @@ int che_plan(const nrLDPC_hip_chest_seg_t *seg, uint32_t n_seg, uint32_t n_rx, u
     j.port = g.port;
     j.delay_off = g.delay_off;
   }
-  for (const Range &r : out) {
-    p.out_lo = std::min(p.out_lo, r.lo);
-    p.out_hi = std::max(p.out_hi, r.hi);
-  }
-  std::sort(out.begin(), out.end(), [](const Range &a, const Range &b) { return a.lo < b.lo; });
-  for (size_t i = 1; i < out.size(); i++)
-    if (out[i].lo < out[i - 1].hi)
-      return set_error("channel_estimation: the output ranges of two (descriptor, antenna) pairs overlap");
+  if (ranges_overlap(out, p.out_lo, p.out_hi))
+    return set_error("channel_estimation: the output ranges of two (descriptor, antenna) pairs overlap");
   /* the workgroup table, mode by mode; the Gold registers of a piece are the same for every antenna */
   for (uint32_t mode = 0; mode < NR_CHE_MODES; mode++)
     for (uint32_t i = 0; i < n_seg; i++) {
@@ -210,19 +196,10 @@ int che_plan(const nrLDPC_hip_chest_seg_t *seg, uint32_t n_seg, uint32_t n_rx, u
   return 0;
 }
 
-size_t che_jobs_bytes(const ChestPlan &p) { return align_up(p.wgs.size() * sizeof(rx_chest_wg), 16) + align_up(p.jobs.size() * sizeof(rx_chest_job), 16); }
-void che_write_jobs(const ChestPlan &p, uint8_t *dst)
+/* the four launches over the tables' device copy */
+int che_launch(const ChestPlan &p, const rx_chest_wg *wgs, const rx_chest_job *jobs, const uint32_t *rx, uint64_t rx_stride, uint32_t *ch,
+               uint64_t ch_stride, const int32_t *delay, hipStream_t s)
 {
-  memcpy(dst, p.wgs.data(), p.wgs.size() * sizeof(rx_chest_wg));
-  memcpy(dst + align_up(p.wgs.size() * sizeof(rx_chest_wg), 16), p.jobs.data(), p.jobs.size() * sizeof(rx_chest_job));
-}
-
-/* the four launches over the uploaded tables at `base` */
-int che_launch(const ChestPlan &p, const uint8_t *base, const uint32_t *rx, uint64_t rx_stride, uint32_t *ch, uint64_t ch_stride, const int32_t *delay,
-               hipStream_t s)
-{
-  const rx_chest_wg *wgs = reinterpret_cast<const rx_chest_wg *>(base);
-  const rx_chest_job *jobs = reinterpret_cast<const rx_chest_job *>(base + align_up(p.wgs.size() * sizeof(rx_chest_wg), 16));
   uint32_t first = 0;
   for (uint32_t mode = 0; mode < NR_CHE_MODES; mode++) {
     HIP_TRY(nr_launch_rx_chest(mode, wgs + first, p.n_wg[mode], jobs, rx, rx_stride, ch, ch_stride, delay, s));
@@ -260,13 +237,12 @@ int32_t nrLDPC_hip_pusch_dmrs_host(uint32_t c_init, uint32_t dmrs_offset, uint32
     return set_error("pusch_dmrs_host: dmrs_offset or n above 2^20");
   if (n == 0)
     return 0;
-  const uint32_t w0 = (2u * dmrs_offset) >> 5;
-  std::vector<uint32_t> gold(((2u * (dmrs_offset + n) - 1u) >> 5) - w0 + 1u);
-  if (nr_hip_gold_words(c_init, w0, (uint32_t)gold.size(), gold.data()) != 0)
+  std::vector<uint32_t> gold;
+  uint32_t w0;
+  if (!dmrs_gold_words(c_init, dmrs_offset, n, gold, w0))
     return set_error("pusch_dmrs_host: the Gold sequence could not be generated");
   for (uint32_t k = 0; k < n; k++) {
-    const uint32_t bit = 2u * (dmrs_offset + k) - 32u * w0;
-    const nr_che_c c = nr_che_pilot((gold[bit >> 5] >> (bit & 31u)) & 3u, dmrs_offset + k, port);
+    const nr_che_c c = nr_che_pilot((uint32_t)dmrs_bits(gold, w0, dmrs_offset + k) & 3u, dmrs_offset + k, port);
     out[2 * (size_t)k] = (int16_t)c.r;
     out[2 * (size_t)k + 1] = (int16_t)c.i;
   }
@@ -298,14 +274,9 @@ int32_t nrLDPC_hip_pusch_chest_segments(const nrLDPC_hip_pusch_alloc_t *alloc, c
     const nrLDPC_hip_pusch_alloc_t &a = alloc[i];
     const nrLDPC_hip_pusch_chest_cfg_t &c = cfg[i];
     const uint32_t N = a.fft_size, type = a.dmrs_config_type;
-    if (a.nr_of_symbols == 0 || a.start_symbol >= NR_RXG_SYMBOLS || a.nr_of_symbols > NR_RXG_SYMBOLS - a.start_symbol)
-      return set_error("pusch_chest_segments: the symbols must lie within the slot's 14");
-    if (a.rb_size == 0)
-      return set_error("pusch_chest_segments: rb_size is 0");
-    if (N == 0 || (uint64_t)a.rb_size * 12u > N)
-      return set_error("pusch_chest_segments: the allocation is wider than fft_size");
-    if (a.first_carrier_offset >= N)
-      return set_error("pusch_chest_segments: first_carrier_offset must be below fft_size");
+    if (alloc_check_symbols("pusch_chest_segments", a.start_symbol, a.nr_of_symbols) != 0 ||
+        alloc_check_width("pusch_chest_segments", a.rb_size, N, a.first_carrier_offset) != 0)
+      return -1;
     if (type > 1)
       return set_error("pusch_chest_segments: dmrs_config_type must be 0 (type 1) or 1 (type 2)");
     if (c.chest_freq > 1)
@@ -331,9 +302,7 @@ int32_t nrLDPC_hip_pusch_chest_segments(const nrLDPC_hip_pusch_alloc_t *alloc, c
       g.start_re = nr_rxg_start_re(a.first_carrier_offset, a.bwp_start, a.rb_start, N);
       g.rb_size = a.rb_size;
       g.dmrs_offset = 12u * (a.bwp_start + a.rb_start) / (type == 0 ? 2u : 3u); /* nr_dmrs_rx.c:84 */
-      /* nr_gold.c:107-108 */
-      g.c_init = (uint32_t)(((1ull << 17) * (NR_RXG_SYMBOLS * c.slot + sym + 1u) * (2ull * c.dmrs_scrambling_id + 1u) + 2ull * c.dmrs_scrambling_id + c.scid) &
-                            0x7fffffffull);
+      g.c_init = dmrs_c_init(c.slot, sym, c.dmrs_scrambling_id, c.scid);
       g.delay_off = (uint32_t)segs.size() * n_rx;
       g.rx_off = a.rx_slot_off + (uint64_t)sym * N;
       g.ch_off = a.ch_off + (uint64_t)sym * N;
@@ -342,12 +311,7 @@ int32_t nrLDPC_hip_pusch_chest_segments(const nrLDPC_hip_pusch_alloc_t *alloc, c
       segs.push_back(g);
     }
   }
-  if (segs.size() > cap)
-    return set_error("pusch_chest_segments: more descriptors than cap");
-  if (!segs.empty())
-    memcpy(seg_out, segs.data(), segs.size() * sizeof segs[0]);
-  *n_seg_out = (uint32_t)segs.size();
-  return 0;
+  return emit_segments(segs, seg_out, cap, n_seg_out, "pusch_chest_segments: more descriptors than cap");
 }
 
 int32_t nrLDPC_hip_pusch_channel_estimation(const int16_t *rxdataF, uint64_t rx_ant_stride, int16_t *ul_ch, uint64_t ch_ant_stride, uint32_t n_rx,
@@ -360,70 +324,60 @@ int32_t nrLDPC_hip_pusch_channel_estimation(const int16_t *rxdataF, uint64_t rx_
   ChestPlan p;
   if (che_plan(seg, n_seg, n_rx, rx_ant_stride, ch_ant_stride, p) != 0)
     return -1;
+  const auto tab = table2(p.wgs, p.jobs);
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
     if (n_seg == 0)
       return 0;
-    const int ord = scr_device_ordinal(ul_ch);
-    if (ord < 0 || !rxf_dev_ok(ul_ch, ord) || !rxf_dev_ok(rxdataF, ord) || (est_delay && !rxf_dev_ok(est_delay, ord)))
-      return set_error("channel_estimation: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
-      return -1;
-    UseDevice use(*dv);
-    if (rxf_check_stream("channel_estimation", static_cast<hipStream_t>(stream)) != 0)
+    DeviceCall dc;
+    if (dc.open("channel_estimation", {{ul_ch, 4}, {rxdataF, 4}, {est_delay, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 ||
+        dc.refuse_capture("channel_estimation") != 0)
       return -1;
     for (uint32_t i = 0; i < n_seg; i++)
-      if (!(p.jobs[i].tab = che_table_device(ord, seg[i].fft_size)))
+      if (!(p.jobs[i].tab = che_table_device(dc.ord, seg[i].fft_size)))
         return -1;
-    TbCtx &c = tls_tb;
-    hipStream_t s;
-    const size_t bytes = che_jobs_bytes(p);
-    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 || c.jobs_d.ensure(bytes) != 0)
+    uint8_t *base = dc.upload(tab);
+    if (!base)
       return -1;
-    che_write_jobs(p, c.jobs_h.p);
-    if (tb_upload_jobs(c, c.jobs_d.p, bytes, s) != 0)
-      return -1;
-    return che_launch(p, c.jobs_d.p, reinterpret_cast<const uint32_t *>(rxdataF), rx_ant_stride, reinterpret_cast<uint32_t *>(ul_ch), ch_ant_stride,
-                      est_delay, s);
+    return che_launch(p, tab.first(base), tab.second(base), reinterpret_cast<const uint32_t *>(rxdataF), rx_ant_stride, reinterpret_cast<uint32_t *>(ul_ch),
+                      ch_ant_stride, est_delay, dc.s);
   }
   if (n_seg == 0)
     return 0;
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
   /* the device works on a copy of the c16 range of the grid the pilots lie in and on the delays of the call's (descriptor,
    * antenna) pairs; the output keeps the caller's alignment phase */
-  const uint64_t out_pad = p.out_lo & 3u;
+  const uint64_t out_bias = p.out_lo - (p.out_lo & 3u);
   for (uint32_t i = 0; i < n_seg; i++) {
     rx_chest_job &j = p.jobs[i];
     if (!(j.tab = che_table_device(g.dev[0].id, seg[i].fft_size)))
       return -1;
     j.rx_off -= p.rx_lo;
-    j.ch_off -= p.out_lo - out_pad;
+    j.ch_off -= out_bias;
     j.delay_off = i * n_rx;
   }
-  const size_t jobs_b = che_jobs_bytes(p), delay_b = align_up((size_t)n_seg * n_rx * 4u, 16), rx_b = align_up((size_t)(p.rx_hi - p.rx_lo) * 4u, 16),
-               out_b = (size_t)(p.out_hi - p.out_lo + out_pad) * 4u;
-  if (c.ensure(jobs_b + delay_b + rx_b, out_b) != 0)
+  const size_t rx_n = (size_t)(p.rx_hi - p.rx_lo) * 4u, out_b = (size_t)(p.out_hi - out_bias) * 4u;
+  const size_t tab_o = st.take(tab.bytes()), delay_o = st.take((size_t)n_seg * n_rx * 4u), rx_o = st.take(rx_n);
+  if (st.ensure(out_b) != 0)
     return -1;
-  che_write_jobs(p, c.h_in);
-  int32_t *dl = reinterpret_cast<int32_t *>(c.h_in + jobs_b);
+  tab.write(st.h(tab_o));
+  int32_t *dl = reinterpret_cast<int32_t *>(st.h(delay_o));
   for (uint32_t i = 0; i < n_seg; i++)
     for (uint32_t a = 0; a < n_rx; a++)
       dl[(size_t)i * n_rx + a] = est_delay ? est_delay[(size_t)seg[i].delay_off + a] : 0;
-  memcpy(c.h_in + jobs_b + delay_b, rxdataF + 2 * p.rx_lo, (size_t)(p.rx_hi - p.rx_lo) * 4u);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + delay_b + rx_b, hipMemcpyHostToDevice, c.stream));
-  if (che_launch(p, c.d_in, reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + delay_b), rx_ant_stride, reinterpret_cast<uint32_t *>(c.d_out),
-                 ch_ant_stride, reinterpret_cast<const int32_t *>(c.d_in + jobs_b), c.stream) != 0)
+  memcpy(st.h(rx_o), rxdataF + 2 * p.rx_lo, rx_n);
+  const auto launch = [&] {
+    return che_launch(p, tab.first(st.d(tab_o)), tab.second(st.d(tab_o)), reinterpret_cast<const uint32_t *>(st.d(rx_o)), rx_ant_stride,
+                      reinterpret_cast<uint32_t *>(st.d_out()), ch_ant_stride, reinterpret_cast<const int32_t *>(st.d(delay_o)), st.stream());
+  };
+  if (st.run(st.top, launch, out_b) != 0)
     return -1;
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_b, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
   /* only the write set goes to the caller's array */
   for (uint32_t i = 0; i < n_seg; i++)
     for (uint32_t a = 0; a < n_rx; a++) {
       const uint64_t at = seg[i].ch_off + (uint64_t)a * ch_ant_stride;
-      memcpy(ul_ch + 2 * at, c.h_out + 4u * (at - (p.out_lo - out_pad)), (size_t)seg[i].rb_size * 48u);
+      memcpy(ul_ch + 2 * at, st.h_out() + 4u * (at - out_bias), (size_t)seg[i].rb_size * 48u);
     }
   return 0;
 }

@@ -1,7 +1,8 @@
 /*
  * rx_front_api.inc.cpp -- the UL receive front's entry points: channel level and channel compensation of the single-layer PUSCH
- * receiver (included at the end of ldpc_api.cpp, behind qam_api.inc.cpp whose checks it shares).  The arithmetic: nr_rx_front.h;
- * the kernels: tb_rx_front.hip.  Everything the kernels index with is checked here, before anything is enqueued.
+ * receiver (included into ldpc_api.cpp; uses qam_check_qm of qam_api.inc.cpp and the call scopes, the table layout and the overlap
+ * check of slot_call.inc.cpp).  The arithmetic: nr_rx_front.h; the kernels: tb_rx_front.hip.  Everything the kernels index with is
+ * checked here, before anything is enqueued.
  */
 
 namespace {
@@ -19,27 +20,13 @@ int rxf_check_common(const char *who, uint32_t n_rx, int32_t mem)
 {
   if (n_rx < 1 || n_rx > NR_RXF_MAX_RX)
     return set_error((std::string(who) + ": n_rx must be 1..8").c_str());
-  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
-    return set_error((std::string(who) + ": mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE").c_str());
-  return 0;
-}
-
-/* graph capture of the two calls is not supported: they upload their descriptors through the thread's page-locked area */
-int rxf_check_stream(const char *who, hipStream_t s)
-{
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-    (void)hipGetLastError();
-    return set_error((std::string(who) + ": the stream is being captured (graph capture of this call is not supported)").c_str());
-  }
-  return 0;
+  return check_mem(who, mem);
 }
 
 /* the segments of a compensation call, without the workgroup table (that needs the address the records are written at) */
 int rxf_plan_compensation(const nrLDPC_hip_rx_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t ant_stride, RxFrontPlan &p)
 {
-  struct Range { uint64_t lo, hi; };
-  std::vector<Range> out;
+  std::vector<Range64> out;
   p.jobs.reserve(n_seg);
   for (uint32_t i = 0; i < n_seg; i++) {
     const nrLDPC_hip_rx_seg_t &g = seg[i];
@@ -56,13 +43,11 @@ int rxf_plan_compensation(const nrLDPC_hip_rx_seg_t *seg, uint32_t n_seg, uint32
       continue;
     const uint64_t first = g.rec_off / 2u + g.sym_off, reach = (uint64_t)(n_rx - 1) * ant_stride + g.nb_re;
     for (uint32_t k = 0; k < g.Qm / 2u; k++)
-      out.push_back(Range{first + (uint64_t)k * g.plane, first + (uint64_t)k * g.plane + g.nb_re});
+      out.push_back(Range64{first + (uint64_t)k * g.plane, first + (uint64_t)k * g.plane + g.nb_re});
     p.rx_lo = std::min(p.rx_lo, g.rx_off);
     p.rx_hi = std::max(p.rx_hi, g.rx_off + reach);
     p.ch_lo = std::min(p.ch_lo, g.ch_off);
     p.ch_hi = std::max(p.ch_hi, g.ch_off + reach);
-    p.out_lo = std::min(p.out_lo, first);
-    p.out_hi = std::max(p.out_hi, out.back().hi);
     rx_front_seg_job j{};
     j.rx_off = g.rx_off;
     j.ch_off = g.ch_off;
@@ -73,10 +58,8 @@ int rxf_plan_compensation(const nrLDPC_hip_rx_seg_t *seg, uint32_t n_seg, uint32
     j.Qm = g.Qm;
     p.jobs.push_back(j);
   }
-  std::sort(out.begin(), out.end(), [](const Range &a, const Range &b) { return a.lo < b.lo; });
-  for (size_t i = 1; i < out.size(); i++)
-    if (out[i].lo < out[i - 1].hi)
-      return set_error("channel_compensation: the output ranges of two segments overlap");
+  if (ranges_overlap(out, p.out_lo, p.out_hi))
+    return set_error("channel_compensation: the output ranges of two segments overlap");
   return 0;
 }
 
@@ -93,13 +76,6 @@ void rxf_place(RxFrontPlan &p, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_
     for (uint32_t q = 0; q * NR_RXF_THREADS < groups; q++)
       p.wgs.push_back(rx_front_wg{(uint32_t)i, q});
   }
-}
-
-size_t rxf_jobs_bytes(const RxFrontPlan &p) { return align_up(p.wgs.size() * sizeof(rx_front_wg), 16) + align_up(p.jobs.size() * sizeof(rx_front_seg_job), 16); }
-void rxf_write_jobs(const RxFrontPlan &p, uint8_t *dst)
-{
-  memcpy(dst, p.wgs.data(), p.wgs.size() * sizeof(rx_front_wg));
-  memcpy(dst + align_up(p.wgs.size() * sizeof(rx_front_wg), 16), p.jobs.data(), p.jobs.size() * sizeof(rx_front_seg_job));
 }
 
 int rxf_plan_level(const nrLDPC_hip_rx_seg_t *fs, uint32_t n_tb, uint32_t n_rx, uint64_t ant_stride, RxFrontPlan &p)
@@ -121,7 +97,21 @@ int rxf_plan_level(const nrLDPC_hip_rx_seg_t *fs, uint32_t n_tb, uint32_t n_rx, 
   return 0;
 }
 
-bool rxf_dev_ok(const void *p, int ord) { return scr_device_ordinal(p) == ord && (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+/* a level call's blocks, then their zeroed state (maxima, counters: two words a block) */
+template <typename Job> Table2<Job, int32_t> rxf_level_tables(const std::vector<Job> &lvl)
+{
+  return Table2<Job, int32_t>{lvl.data(), lvl.size(), nullptr, 2u * lvl.size()};
+}
+
+/* only the segments' entries of the bounce that begins at c16 `bias` of the record array go to the caller's array */
+void rxf_scatter(const RxFrontPlan &p, const uint8_t *bounce, uint64_t bias, int16_t *records)
+{
+  for (const rx_front_seg_job &j : p.jobs)
+    for (uint32_t k = 0; k < j.Qm / 2u; k++) {
+      const uint64_t at = j.out_off + (uint64_t)k * j.plane;
+      memcpy(records + 2 * (at + bias), bounce + 4u * at, (size_t)j.nb_re * 4u);
+    }
+}
 
 } // namespace
 
@@ -191,64 +181,47 @@ int32_t nrLDPC_hip_ulsch_channel_compensation(const int16_t *rxFext, const int16
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
     if (n_seg == 0)
       return 0;
-    const int ord = scr_device_ordinal(records);
-    if (ord < 0 || !rxf_dev_ok(records, ord) || !rxf_dev_ok(rxFext, ord) || !rxf_dev_ok(chFext, ord) || !rxf_dev_ok(shift, ord))
-      return set_error("channel_compensation: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
-      return -1;
-    UseDevice use(*dv);
-    if (rxf_check_stream("channel_compensation", static_cast<hipStream_t>(stream)) != 0)
+    DeviceCall dc;
+    if (dc.open("channel_compensation", {{records, 4}, {rxFext, 4}, {chFext, 4}, {shift, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 ||
+        dc.refuse_capture("channel_compensation") != 0)
       return -1;
     if (p.jobs.empty())
       return 0;
     rxf_place(p, 0, 0, 0, reinterpret_cast<uintptr_t>(records) >> 2);
-    TbCtx &c = tls_tb;
-    hipStream_t s;
-    const size_t bytes = rxf_jobs_bytes(p);
-    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 ||
-        c.jobs_d.ensure(bytes) != 0)
+    const auto tab = table2(p.wgs, p.jobs);
+    uint8_t *base = dc.upload(tab);
+    if (!base)
       return -1;
-    rxf_write_jobs(p, c.jobs_h.p);
-    if (tb_upload_jobs(c, c.jobs_d.p, bytes, s) != 0)
-      return -1;
-    HIP_TRY(nr_launch_rx_compensation(reinterpret_cast<const rx_front_wg *>(c.jobs_d.p), (uint32_t)p.wgs.size(),
-                                      reinterpret_cast<const rx_front_seg_job *>(c.jobs_d.p + align_up(p.wgs.size() * sizeof(rx_front_wg), 16)),
-                                      reinterpret_cast<const uint32_t *>(rxFext), reinterpret_cast<const uint32_t *>(chFext), n_rx, ant_stride, shift,
-                                      reinterpret_cast<uint32_t *>(records), s));
+    HIP_TRY(nr_launch_rx_compensation(tab.first(base), (uint32_t)p.wgs.size(), tab.second(base), reinterpret_cast<const uint32_t *>(rxFext),
+                                      reinterpret_cast<const uint32_t *>(chFext), n_rx, ant_stride, shift, reinterpret_cast<uint32_t *>(records), dc.s));
     return 0;
   }
   if (p.jobs.empty())
     return 0;
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
   /* the device works on copies of the c16 ranges the segments reach; the output keeps the caller's alignment phase */
   const uint64_t out_pad = p.out_lo & 3u;
   rxf_place(p, p.rx_lo, p.ch_lo, p.out_lo - out_pad, 0);
-  const size_t jobs_b = rxf_jobs_bytes(p), shift_b = align_up((size_t)p.n_shift * 4u, 16), rx_b = align_up((size_t)(p.rx_hi - p.rx_lo) * 4u, 16),
-               ch_b = align_up((size_t)(p.ch_hi - p.ch_lo) * 4u, 16), out_b = (size_t)(p.out_hi - p.out_lo + out_pad) * 4u;
-  if (c.ensure(jobs_b + shift_b + rx_b + ch_b, out_b) != 0)
+  const auto tab = table2(p.wgs, p.jobs);
+  const size_t rx_n = (size_t)(p.rx_hi - p.rx_lo) * 4u, ch_n = (size_t)(p.ch_hi - p.ch_lo) * 4u, out_b = (size_t)(p.out_hi - p.out_lo + out_pad) * 4u;
+  const size_t tab_o = st.take(tab.bytes()), shift_o = st.take((size_t)p.n_shift * 4u), rx_o = st.take(rx_n), ch_o = st.take(ch_n);
+  if (st.ensure(out_b) != 0)
     return -1;
-  rxf_write_jobs(p, c.h_in);
-  memcpy(c.h_in + jobs_b, shift, (size_t)p.n_shift * 4u);
-  memcpy(c.h_in + jobs_b + shift_b, rxFext + 2 * p.rx_lo, (size_t)(p.rx_hi - p.rx_lo) * 4u);
-  memcpy(c.h_in + jobs_b + shift_b + rx_b, chFext + 2 * p.ch_lo, (size_t)(p.ch_hi - p.ch_lo) * 4u);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + shift_b + rx_b + ch_b, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_rx_compensation(reinterpret_cast<const rx_front_wg *>(c.d_in), (uint32_t)p.wgs.size(),
-                                    reinterpret_cast<const rx_front_seg_job *>(c.d_in + align_up(p.wgs.size() * sizeof(rx_front_wg), 16)),
-                                    reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + shift_b),
-                                    reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + shift_b + rx_b), n_rx, ant_stride,
-                                    reinterpret_cast<const int32_t *>(c.d_in + jobs_b), reinterpret_cast<uint32_t *>(c.d_out), c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_b, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  /* only the segments' entries go to the caller's array */
-  for (const rx_front_seg_job &j : p.jobs)
-    for (uint32_t k = 0; k < j.Qm / 2u; k++) {
-      const uint64_t at = j.out_off + (uint64_t)k * j.plane;
-      memcpy(records + 2 * (at + p.out_lo - out_pad), c.h_out + 4u * at, (size_t)j.nb_re * 4u);
-    }
+  tab.write(st.h(tab_o));
+  memcpy(st.h(shift_o), shift, (size_t)p.n_shift * 4u);
+  memcpy(st.h(rx_o), rxFext + 2 * p.rx_lo, rx_n);
+  memcpy(st.h(ch_o), chFext + 2 * p.ch_lo, ch_n);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_rx_compensation(tab.first(st.d(tab_o)), (uint32_t)p.wgs.size(), tab.second(st.d(tab_o)), reinterpret_cast<const uint32_t *>(st.d(rx_o)),
+                                      reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, ant_stride, reinterpret_cast<const int32_t *>(st.d(shift_o)),
+                                      reinterpret_cast<uint32_t *>(st.d_out()), st.stream()));
+    return 0;
+  };
+  if (st.run(st.top, launch, out_b) != 0)
+    return -1;
+  rxf_scatter(p, st.h_out(), p.out_lo - out_pad, records);
   return 0;
 }
 
@@ -264,49 +237,36 @@ int32_t nrLDPC_hip_ulsch_channel_level(const int16_t *chFext, uint32_t n_rx, uin
   RxFrontPlan p;
   if (rxf_plan_level(first_sym, n_tb, n_rx, ant_stride, p) != 0)
     return -1;
-  /* the blocks' jobs, then their zeroed state (maxima, counters) */
-  const size_t jobs_b = align_up((size_t)n_tb * sizeof(rx_front_lvl_job), 16), state_b = align_up((size_t)n_tb * 8u, 16);
+  const auto tab = rxf_level_tables(p.lvl);
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(log2_maxh);
-    if (ord < 0 || !rxf_dev_ok(log2_maxh, ord) || !rxf_dev_ok(chFext, ord))
-      return set_error("channel_level: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
+    DeviceCall dc;
+    if (dc.open("channel_level", {{log2_maxh, 4}, {chFext, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 || dc.refuse_capture("channel_level") != 0)
       return -1;
-    UseDevice use(*dv);
-    if (rxf_check_stream("channel_level", static_cast<hipStream_t>(stream)) != 0)
+    uint8_t *base = dc.upload(tab);
+    if (!base)
       return -1;
-    TbCtx &c = tls_tb;
-    hipStream_t s;
-    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_b + state_b) != 0 ||
-        c.jobs_d.ensure(jobs_b + state_b) != 0)
-      return -1;
-    memcpy(c.jobs_h.p, p.lvl.data(), (size_t)n_tb * sizeof(rx_front_lvl_job));
-    memset(c.jobs_h.p + jobs_b, 0, state_b);
-    if (tb_upload_jobs(c, c.jobs_d.p, jobs_b + state_b, s) != 0)
-      return -1;
-    HIP_TRY(nr_launch_rx_level(reinterpret_cast<const rx_front_lvl_job *>(c.jobs_d.p), n_tb, reinterpret_cast<const uint32_t *>(chFext), n_rx,
-                               ant_stride, reinterpret_cast<int32_t *>(c.jobs_d.p + jobs_b), log2_maxh, s));
+    HIP_TRY(nr_launch_rx_level(tab.first(base), n_tb, reinterpret_cast<const uint32_t *>(chFext), n_rx, ant_stride, tab.second(base), log2_maxh, dc.s));
     return 0;
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
   for (rx_front_lvl_job &j : p.lvl)
     j.ch_off -= p.ch_lo;
-  const size_t ch_b = (size_t)(p.ch_hi - p.ch_lo) * 4u;
-  if (c.ensure(jobs_b + state_b + align_up(ch_b, 16), (size_t)n_tb * 4u) != 0)
+  const size_t ch_n = (size_t)(p.ch_hi - p.ch_lo) * 4u, out_b = (size_t)n_tb * 4u;
+  const size_t tab_o = st.take(tab.bytes()), ch_o = st.take(ch_n);
+  if (st.ensure(out_b) != 0)
     return -1;
-  memcpy(c.h_in, p.lvl.data(), (size_t)n_tb * sizeof(rx_front_lvl_job));
-  memset(c.h_in + jobs_b, 0, state_b);
-  memcpy(c.h_in + jobs_b + state_b, chFext + 2 * p.ch_lo, ch_b);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + state_b + ch_b, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_rx_level(reinterpret_cast<const rx_front_lvl_job *>(c.d_in), n_tb, reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + state_b),
-                             n_rx, ant_stride, reinterpret_cast<int32_t *>(c.d_in + jobs_b), reinterpret_cast<int32_t *>(c.d_out), c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, (size_t)n_tb * 4u, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  memcpy(log2_maxh, c.h_out, (size_t)n_tb * 4u);
+  tab.write(st.h(tab_o));
+  memcpy(st.h(ch_o), chFext + 2 * p.ch_lo, ch_n);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_rx_level(tab.first(st.d(tab_o)), n_tb, reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, ant_stride, tab.second(st.d(tab_o)),
+                               reinterpret_cast<int32_t *>(st.d_out()), st.stream()));
+    return 0;
+  };
+  if (st.run(ch_o + ch_n, launch, out_b) != 0)
+    return -1;
+  memcpy(log2_maxh, st.h_out(), out_b);
   return 0;
 }
 

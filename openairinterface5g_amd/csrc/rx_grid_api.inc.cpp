@@ -1,8 +1,8 @@
 /*
  * rx_grid_api.inc.cpp -- the UL receive front read from the OFDM grid: the _grid forms of the two calls of
- * rx_front_api.inc.cpp (included behind it; they share its checks and its plan), the CPU extraction for checking, and the
- * descriptors of a PUSCH allocation.  Where the REs lie: nr_rx_grid.h; the kernels: tb_rx_front.hip.  Everything the kernels
- * index with is checked here, before anything is enqueued.
+ * rx_front_api.inc.cpp (they use its checks, its plan and its scatter, and the call scopes of slot_call.inc.cpp), the CPU extraction
+ * for checking, and the descriptors of a PUSCH allocation.  Where the REs lie: nr_rx_grid.h; the kernels: tb_rx_front.hip.
+ * Everything the kernels index with is checked here, before anything is enqueued.
  */
 
 namespace {
@@ -91,16 +91,6 @@ void rxg_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_b
     gj[i].s = p.jobs[i];
 }
 
-size_t rxg_jobs_bytes(const RxFrontPlan &p, const std::vector<rx_front_grid_job> &gj)
-{
-  return align_up(p.wgs.size() * sizeof(rx_front_wg), 16) + align_up(gj.size() * sizeof(rx_front_grid_job), 16);
-}
-void rxg_write_jobs(const RxFrontPlan &p, const std::vector<rx_front_grid_job> &gj, uint8_t *dst)
-{
-  memcpy(dst, p.wgs.data(), p.wgs.size() * sizeof(rx_front_wg));
-  memcpy(dst + align_up(p.wgs.size() * sizeof(rx_front_wg), 16), gj.data(), gj.size() * sizeof(rx_front_grid_job));
-}
-
 int rxg_plan_level(const nrLDPC_hip_rx_grid_seg_t *fs, uint32_t n_tb, uint32_t n_rx, uint64_t ch_stride, std::vector<rx_front_grid_lvl_job> &lvl,
                    uint64_t &ch_lo, uint64_t &ch_hi)
 {
@@ -159,14 +149,9 @@ int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, ui
     const uint32_t N = a.fft_size, type = a.dmrs_config_type, cdm = a.num_dmrs_cdm_grps_no_data;
     if (qam_check_qm(a.Qm) != 0)
       return set_error("pusch_grid_segments: Qm must be 2, 4, 6 or 8");
-    if (a.nr_of_symbols == 0 || a.start_symbol >= NR_RXG_SYMBOLS || a.nr_of_symbols > NR_RXG_SYMBOLS - a.start_symbol)
-      return set_error("pusch_grid_segments: the symbols must lie within the slot's 14");
-    if (a.rb_size == 0)
-      return set_error("pusch_grid_segments: rb_size is 0");
-    if (N == 0 || (uint64_t)a.rb_size * 12u > N)
-      return set_error("pusch_grid_segments: the allocation is wider than fft_size");
-    if (a.first_carrier_offset >= N)
-      return set_error("pusch_grid_segments: first_carrier_offset must be below fft_size");
+    if (alloc_check_symbols("pusch_grid_segments", a.start_symbol, a.nr_of_symbols) != 0 ||
+        alloc_check_width("pusch_grid_segments", a.rb_size, N, a.first_carrier_offset) != 0)
+      return -1;
     if (type > 1)
       return set_error("pusch_grid_segments: dmrs_config_type must be 0 (type 1) or 1 (type 2)");
     if (cdm < 1 || cdm > 2)
@@ -207,13 +192,10 @@ int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, ui
     if (!have_first)
       return set_error("pusch_grid_segments: no symbol of the allocation has data REs");
   }
-  if (segs.size() > cap)
-    return set_error("pusch_grid_segments: more segments than cap");
-  if (!segs.empty())
-    memcpy(seg_out, segs.data(), segs.size() * sizeof segs[0]);
+  if (emit_segments(segs, seg_out, cap, n_seg_out, "pusch_grid_segments: more segments than cap") != 0)
+    return -1;
   if (!first.empty())
     memcpy(first_sym_out, first.data(), first.size() * sizeof first[0]);
-  *n_seg_out = (uint32_t)segs.size();
   return 0;
 }
 
@@ -232,64 +214,49 @@ int32_t nrLDPC_hip_ulsch_channel_compensation_grid(const int16_t *rxdataF, const
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
     if (n_seg == 0)
       return 0;
-    const int ord = scr_device_ordinal(records);
-    if (ord < 0 || !rxf_dev_ok(records, ord) || !rxf_dev_ok(rxdataF, ord) || !rxf_dev_ok(ul_ch, ord) || !rxf_dev_ok(shift, ord))
-      return set_error("channel_compensation_grid: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
-      return -1;
-    UseDevice use(*dv);
-    if (rxf_check_stream("channel_compensation_grid", static_cast<hipStream_t>(stream)) != 0)
+    DeviceCall dc;
+    if (dc.open("channel_compensation_grid", {{records, 4}, {rxdataF, 4}, {ul_ch, 4}, {shift, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 ||
+        dc.refuse_capture("channel_compensation_grid") != 0)
       return -1;
     if (gj.empty())
       return 0;
     rxg_place(p, gj, 0, 0, 0, reinterpret_cast<uintptr_t>(records) >> 2);
-    TbCtx &c = tls_tb;
-    hipStream_t s;
-    const size_t bytes = rxg_jobs_bytes(p, gj);
-    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 ||
-        c.jobs_d.ensure(bytes) != 0)
+    const auto tab = table2(p.wgs, gj);
+    uint8_t *base = dc.upload(tab);
+    if (!base)
       return -1;
-    rxg_write_jobs(p, gj, c.jobs_h.p);
-    if (tb_upload_jobs(c, c.jobs_d.p, bytes, s) != 0)
-      return -1;
-    HIP_TRY(nr_launch_rx_compensation_grid(reinterpret_cast<const rx_front_wg *>(c.jobs_d.p), (uint32_t)p.wgs.size(),
-                                           reinterpret_cast<const rx_front_grid_job *>(c.jobs_d.p + align_up(p.wgs.size() * sizeof(rx_front_wg), 16)),
-                                           reinterpret_cast<const uint32_t *>(rxdataF), reinterpret_cast<const uint32_t *>(ul_ch), n_rx, rx_ant_stride,
-                                           ch_ant_stride, shift, reinterpret_cast<uint32_t *>(records), s));
+    HIP_TRY(nr_launch_rx_compensation_grid(tab.first(base), (uint32_t)p.wgs.size(), tab.second(base), reinterpret_cast<const uint32_t *>(rxdataF),
+                                           reinterpret_cast<const uint32_t *>(ul_ch), n_rx, rx_ant_stride, ch_ant_stride, shift,
+                                           reinterpret_cast<uint32_t *>(records), dc.s));
     return 0;
   }
   if (gj.empty())
     return 0;
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
   /* the device works on copies of the c16 ranges the segments reach; the output keeps the caller's alignment phase */
   const uint64_t out_pad = p.out_lo & 3u;
   rxg_place(p, gj, p.rx_lo, p.ch_lo, p.out_lo - out_pad, 0);
-  const size_t jobs_b = rxg_jobs_bytes(p, gj), shift_b = align_up((size_t)p.n_shift * 4u, 16), rx_b = align_up((size_t)(p.rx_hi - p.rx_lo) * 4u, 16),
-               ch_b = align_up((size_t)(p.ch_hi - p.ch_lo) * 4u, 16), out_b = (size_t)(p.out_hi - p.out_lo + out_pad) * 4u;
-  if (c.ensure(jobs_b + shift_b + rx_b + ch_b, out_b) != 0)
+  const auto tab = table2(p.wgs, gj);
+  const size_t rx_n = (size_t)(p.rx_hi - p.rx_lo) * 4u, ch_n = (size_t)(p.ch_hi - p.ch_lo) * 4u, out_b = (size_t)(p.out_hi - p.out_lo + out_pad) * 4u;
+  const size_t tab_o = st.take(tab.bytes()), shift_o = st.take((size_t)p.n_shift * 4u), rx_o = st.take(rx_n), ch_o = st.take(ch_n);
+  if (st.ensure(out_b) != 0)
     return -1;
-  rxg_write_jobs(p, gj, c.h_in);
-  memcpy(c.h_in + jobs_b, shift, (size_t)p.n_shift * 4u);
-  memcpy(c.h_in + jobs_b + shift_b, rxdataF + 2 * p.rx_lo, (size_t)(p.rx_hi - p.rx_lo) * 4u);
-  memcpy(c.h_in + jobs_b + shift_b + rx_b, ul_ch + 2 * p.ch_lo, (size_t)(p.ch_hi - p.ch_lo) * 4u);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + shift_b + rx_b + ch_b, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_rx_compensation_grid(reinterpret_cast<const rx_front_wg *>(c.d_in), (uint32_t)p.wgs.size(),
-                                         reinterpret_cast<const rx_front_grid_job *>(c.d_in + align_up(p.wgs.size() * sizeof(rx_front_wg), 16)),
-                                         reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + shift_b),
-                                         reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + shift_b + rx_b), n_rx, rx_ant_stride, ch_ant_stride,
-                                         reinterpret_cast<const int32_t *>(c.d_in + jobs_b), reinterpret_cast<uint32_t *>(c.d_out), c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_b, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  /* only the segments' entries go to the caller's array */
-  for (const rx_front_seg_job &j : p.jobs)
-    for (uint32_t k = 0; k < j.Qm / 2u; k++) {
-      const uint64_t at = j.out_off + (uint64_t)k * j.plane;
-      memcpy(records + 2 * (at + p.out_lo - out_pad), c.h_out + 4u * at, (size_t)j.nb_re * 4u);
-    }
+  tab.write(st.h(tab_o));
+  memcpy(st.h(shift_o), shift, (size_t)p.n_shift * 4u);
+  memcpy(st.h(rx_o), rxdataF + 2 * p.rx_lo, rx_n);
+  memcpy(st.h(ch_o), ul_ch + 2 * p.ch_lo, ch_n);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_rx_compensation_grid(tab.first(st.d(tab_o)), (uint32_t)p.wgs.size(), tab.second(st.d(tab_o)),
+                                           reinterpret_cast<const uint32_t *>(st.d(rx_o)), reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, rx_ant_stride,
+                                           ch_ant_stride, reinterpret_cast<const int32_t *>(st.d(shift_o)), reinterpret_cast<uint32_t *>(st.d_out()),
+                                           st.stream()));
+    return 0;
+  };
+  if (st.run(st.top, launch, out_b) != 0)
+    return -1;
+  rxf_scatter(p, st.h_out(), p.out_lo - out_pad, records);
   return 0;
 }
 
@@ -306,50 +273,37 @@ int32_t nrLDPC_hip_ulsch_channel_level_grid(const int16_t *ul_ch, uint32_t n_rx,
   uint64_t ch_lo, ch_hi;
   if (rxg_plan_level(first_sym, n_tb, n_rx, ch_ant_stride, lvl, ch_lo, ch_hi) != 0)
     return -1;
-  /* the blocks' jobs, then their zeroed state (maxima, counters) */
-  const size_t jobs_b = align_up((size_t)n_tb * sizeof(rx_front_grid_lvl_job), 16), state_b = align_up((size_t)n_tb * 8u, 16);
+  const auto tab = rxf_level_tables(lvl);
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(log2_maxh);
-    if (ord < 0 || !rxf_dev_ok(log2_maxh, ord) || !rxf_dev_ok(ul_ch, ord))
-      return set_error("channel_level_grid: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
+    DeviceCall dc;
+    if (dc.open("channel_level_grid", {{log2_maxh, 4}, {ul_ch, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 || dc.refuse_capture("channel_level_grid") != 0)
       return -1;
-    UseDevice use(*dv);
-    if (rxf_check_stream("channel_level_grid", static_cast<hipStream_t>(stream)) != 0)
+    uint8_t *base = dc.upload(tab);
+    if (!base)
       return -1;
-    TbCtx &c = tls_tb;
-    hipStream_t s;
-    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_b + state_b) != 0 ||
-        c.jobs_d.ensure(jobs_b + state_b) != 0)
-      return -1;
-    memcpy(c.jobs_h.p, lvl.data(), (size_t)n_tb * sizeof(rx_front_grid_lvl_job));
-    memset(c.jobs_h.p + jobs_b, 0, state_b);
-    if (tb_upload_jobs(c, c.jobs_d.p, jobs_b + state_b, s) != 0)
-      return -1;
-    HIP_TRY(nr_launch_rx_level_grid(reinterpret_cast<const rx_front_grid_lvl_job *>(c.jobs_d.p), n_tb, reinterpret_cast<const uint32_t *>(ul_ch), n_rx,
-                                    ch_ant_stride, reinterpret_cast<int32_t *>(c.jobs_d.p + jobs_b), log2_maxh, s));
+    HIP_TRY(nr_launch_rx_level_grid(tab.first(base), n_tb, reinterpret_cast<const uint32_t *>(ul_ch), n_rx, ch_ant_stride, tab.second(base), log2_maxh,
+                                    dc.s));
     return 0;
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
   for (rx_front_grid_lvl_job &j : lvl)
     j.ch_off -= ch_lo;
-  const size_t ch_b = (size_t)(ch_hi - ch_lo) * 4u;
-  if (c.ensure(jobs_b + state_b + align_up(ch_b, 16), (size_t)n_tb * 4u) != 0)
+  const size_t ch_n = (size_t)(ch_hi - ch_lo) * 4u, out_b = (size_t)n_tb * 4u;
+  const size_t tab_o = st.take(tab.bytes()), ch_o = st.take(ch_n);
+  if (st.ensure(out_b) != 0)
     return -1;
-  memcpy(c.h_in, lvl.data(), (size_t)n_tb * sizeof(rx_front_grid_lvl_job));
-  memset(c.h_in + jobs_b, 0, state_b);
-  memcpy(c.h_in + jobs_b + state_b, ul_ch + 2 * ch_lo, ch_b);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + state_b + ch_b, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_rx_level_grid(reinterpret_cast<const rx_front_grid_lvl_job *>(c.d_in), n_tb,
-                                  reinterpret_cast<const uint32_t *>(c.d_in + jobs_b + state_b), n_rx, ch_ant_stride,
-                                  reinterpret_cast<int32_t *>(c.d_in + jobs_b), reinterpret_cast<int32_t *>(c.d_out), c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, (size_t)n_tb * 4u, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  memcpy(log2_maxh, c.h_out, (size_t)n_tb * 4u);
+  tab.write(st.h(tab_o));
+  memcpy(st.h(ch_o), ul_ch + 2 * ch_lo, ch_n);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_rx_level_grid(tab.first(st.d(tab_o)), n_tb, reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, ch_ant_stride,
+                                    tab.second(st.d(tab_o)), reinterpret_cast<int32_t *>(st.d_out()), st.stream()));
+    return 0;
+  };
+  if (st.run(ch_o + ch_n, launch, out_b) != 0)
+    return -1;
+  memcpy(log2_maxh, st.h_out(), out_b);
   return 0;
 }
 

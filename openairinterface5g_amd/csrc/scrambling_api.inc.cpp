@@ -1,6 +1,7 @@
 /*
- * scrambling_api.inc.cpp -- codeword (un)scrambling entry points (included at the end of ldpc_api.cpp; shares its library
- * state).  The sequence itself: nr_gold.h, on the GPU tb_scrambling.hip, on the host nr_hip_gold_words (nr_coding_host.c).
+ * scrambling_api.inc.cpp -- codeword (un)scrambling entry points (included into ldpc_api.cpp; shares its library state, and the
+ * call scopes of slot_call.inc.cpp).  The sequence itself: nr_gold.h, on the GPU tb_scrambling.hip, on the host nr_hip_gold_words
+ * (nr_coding_host.c).
  */
 
 namespace {
@@ -25,21 +26,11 @@ int scr_check_call(const void *p, uint32_t size, int32_t mem, uint32_t n_rnti, u
     return -1;
   if (size > NR_SCR_MAX_BITS)
     return set_error("scrambling: size above 2^21 bits");
-  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
-    return set_error("scrambling: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (check_mem("scrambling", mem) != 0)
+    return -1;
   if (size && !p)
     return set_error("null argument");
   return 0;
-}
-
-/* DEVICE mem: the HIP ordinal of the GPU whose memory holds p (hipMalloc or managed), -1 for anything else */
-int scr_device_ordinal(const void *p)
-{
-  hipPointerAttribute_t at;
-  if (p && hipPointerGetAttributes(&at, p) == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged))
-    return at.device;
-  (void)hipGetLastError();
-  return -1;
 }
 
 /* the scrambled transport-block chain calls: every argument of the batch is checked before anything is enqueued */
@@ -95,28 +86,26 @@ int32_t nrLDPC_hip_codeword_scrambling(const uint8_t *in, uint32_t size, uint8_t
     return 0;
   const uint32_t c_init = nr_gold_c_init(n_RNTI, q, Nid), out_bytes = 4u * ((size + 31u) >> 5);
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(in);
-    if (ord < 0 || scr_device_ordinal(out) != ord)
-      return set_error("scrambling: DEVICE mem needs `in` and `out` in device memory of one GPU");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
+    DeviceCall dc;
+    if (dc.open("scrambling", {{in, 1}, {out, 1}}, DEV_NEEDS_IN_OUT, stream) != 0)
       return -1;
-    UseDevice use(*dv);
-    HIP_TRY(nr_launch_scramble_bits(in, size, c_init, out, static_cast<hipStream_t>(stream)));
+    HIP_TRY(nr_launch_scramble_bits(in, size, c_init, out, dc.s));
     return 0;
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
-  if (c.ensure(align_up(size, 16), out_bytes) != 0)
+  const size_t in_o = st.take(size);
+  if (st.ensure(out_bytes) != 0)
     return -1;
-  memcpy(c.h_in, in, size);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, size, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_scramble_bits(c.d_in, size, c_init, reinterpret_cast<uint32_t *>(c.d_out), c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_bytes, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  memcpy(out, c.h_out, out_bytes);
+  memcpy(st.h(in_o), in, size);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_scramble_bits(st.d(in_o), size, c_init, reinterpret_cast<uint32_t *>(st.d_out()), st.stream()));
+    return 0;
+  };
+  if (st.run(size, launch, out_bytes) != 0)
+    return -1;
+  memcpy(out, st.h_out(), out_bytes);
   return 0;
 }
 
@@ -129,28 +118,27 @@ int32_t nrLDPC_hip_codeword_unscrambling(int16_t *llr, uint32_t size, uint8_t q,
   const uint32_t c_init = nr_gold_c_init(n_RNTI, q, Nid);
   const size_t bytes = (size_t)size * sizeof(int16_t);
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(llr);
-    if (ord < 0)
-      return set_error("unscrambling: DEVICE mem needs `llr` in device memory");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
+    DeviceCall dc;
+    if (dc.open("unscrambling", {{llr, 1}}, "`llr` in device memory", stream) != 0)
       return -1;
-    UseDevice use(*dv);
-    HIP_TRY(nr_launch_unscramble_llr(llr, size, c_init, static_cast<hipStream_t>(stream)));
+    HIP_TRY(nr_launch_unscramble_llr(llr, size, c_init, dc.s));
     return 0;
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
-  if (c.ensure(align_up(bytes, 16), 0) != 0)
+  const size_t llr_o = st.take(bytes);
+  if (st.ensure(0) != 0)
     return -1;
-  memcpy(c.h_in, llr, bytes);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, bytes, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(nr_launch_unscramble_llr(reinterpret_cast<int16_t *>(c.d_in), size, c_init, c.stream));
-  HIP_TRY(hipMemcpyAsync(c.h_in, c.d_in, bytes, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  memcpy(llr, c.h_in, bytes);
+  memcpy(st.h(llr_o), llr, bytes);
+  const auto launch = [&] {
+    HIP_TRY(nr_launch_unscramble_llr(reinterpret_cast<int16_t *>(st.d(llr_o)), size, c_init, st.stream()));
+    return 0;
+  };
+  /* in place: the values come back from the input area */
+  if (st.run(bytes, launch, bytes, true) != 0)
+    return -1;
+  memcpy(llr, st.h(llr_o), bytes);
   return 0;
 }
 

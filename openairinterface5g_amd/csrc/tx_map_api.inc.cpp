@@ -1,8 +1,8 @@
 /*
  * tx_map_api.inc.cpp -- PDSCH resource mapping with DMRS onto the transmit grid: the GPU call, its CPU check forms and the
- * descriptors of a PDSCH allocation (included at the end of ldpc_api.cpp, behind rx_chest_api.inc.cpp whose checks and
- * conventions it shares).  The arithmetic: nr_pdsch_map.h; the kernel: tb_tx_map.hip.  Everything the kernel indexes with is
- * checked here, before anything is enqueued.
+ * descriptors of a PDSCH allocation (included into ldpc_api.cpp; uses che_fft_ok and che_gold_tables of rx_chest_api.inc.cpp and
+ * the call scopes, the table layout, the overlap check and the DMRS helpers of slot_call.inc.cpp).  The arithmetic:
+ * nr_pdsch_map.h; the kernel: tb_tx_map.hip.  Everything the kernel indexes with is checked here, before anything is enqueued.
  */
 
 namespace {
@@ -62,17 +62,15 @@ int txm_host_one(const nrLDPC_hip_pdsch_map_seg_t &g, const uint32_t *lay, uint3
   }
   const nr_pdm_sym s = nr_pdm_sym_make(g.pattern, g.ncdm, g.l_prime, g.port[layer], g.amp);
   std::vector<uint32_t> gold;
-  const uint32_t w0 = (2u * g.dmrs_offset) >> 5;
-  if (g.pattern != NR_PDM_FULL) {
-    gold.resize(((2u * (g.dmrs_offset + nr_pdm_count(s.pmask, n_re))) >> 5) - w0 + 3u);
-    if (nr_hip_gold_words(g.c_init, w0, (uint32_t)gold.size(), gold.data()) != 0)
-      return set_error("pdsch_map_host: the Gold sequence could not be generated");
-  }
+  uint32_t w0 = 0;
+  /* an RE behind the last pilot asks for the bits of the symbol behind the last one */
+  if (g.pattern != NR_PDM_FULL && !dmrs_gold_words(g.c_init, g.dmrs_offset, nr_pdm_count(s.pmask, n_re) + 1u, gold, w0))
+    return set_error("pdsch_map_host: the Gold sequence could not be generated");
   for (uint32_t i = 0; i < n_re; i++) {
     uint64_t bits = 0;
     const uint32_t jlo = nr_pdm_count(s.pmask, i);
     if (g.pattern != NR_PDM_FULL)
-      bits = che_unit_bits(gold, w0, 2u * (g.dmrs_offset + jlo));
+      bits = dmrs_bits(gold, w0, g.dmrs_offset + jlo);
     sym[nr_pdm_wrap(g.start_re, i, g.fft_size)] = nr_pdm_re(&s, lay, i, bits, jlo);
   }
   return 0;
@@ -88,8 +86,7 @@ struct TxMapPlan {
 /* checks and ranges; the workgroup table needs the address the grid is written at (txm_plan_wgs) */
 int txm_plan(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, TxMapPlan &p)
 {
-  struct Range { uint64_t lo, hi; };
-  std::vector<Range> out;
+  std::vector<Range64> out;
   p.jobs.resize(n_seg);
   for (uint32_t i = 0; i < n_seg; i++) {
     const nrLDPC_hip_pdsch_map_seg_t &g = seg[i];
@@ -103,9 +100,9 @@ int txm_plan(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_t
     const uint32_t n_re = 12u * g.rb_size, first = std::min(n_re, g.fft_size - g.start_re);
     for (uint32_t a = 0; a < n_tx; a++) {
       const uint64_t base = g.tx_off + (uint64_t)a * tx_stride;
-      out.push_back(Range{base + g.start_re, base + g.start_re + first});
+      out.push_back(Range64{base + g.start_re, base + g.start_re + first});
       if (first < n_re)
-        out.push_back(Range{base, base + (n_re - first)});
+        out.push_back(Range64{base, base + (n_re - first)});
     }
     tx_map_job &j = p.jobs[i];
     memset(&j, 0, sizeof j);
@@ -123,14 +120,8 @@ int txm_plan(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_t
     for (uint32_t l = 0; l < g.Nl; l++)
       j.ports |= (uint32_t)g.port[l] << (8u * l);
   }
-  for (const Range &r : out) {
-    p.out_lo = std::min(p.out_lo, r.lo);
-    p.out_hi = std::max(p.out_hi, r.hi);
-  }
-  std::sort(out.begin(), out.end(), [](const Range &a, const Range &b) { return a.lo < b.lo; });
-  for (size_t i = 1; i < out.size(); i++)
-    if (out[i].lo < out[i - 1].hi)
-      return set_error("pdsch_resource_mapping: the output ranges of two (descriptor, antenna) pairs overlap");
+  if (ranges_overlap(out, p.out_lo, p.out_hi))
+    return set_error("pdsch_resource_mapping: the output ranges of two (descriptor, antenna) pairs overlap");
   return 0;
 }
 
@@ -166,18 +157,9 @@ void txm_plan_wgs(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_
     }
 }
 
-size_t txm_jobs_bytes(const TxMapPlan &p) { return align_up(p.wgs.size() * sizeof(tx_map_wg), 16) + align_up(p.jobs.size() * sizeof(tx_map_job), 16); }
-void txm_write_jobs(const TxMapPlan &p, uint8_t *dst)
+/* the launches over the tables' device copy */
+int txm_launch(const TxMapPlan &p, const tx_map_wg *wgs, const tx_map_job *jobs, const uint32_t *lay, uint32_t *tx, uint64_t tx_stride, hipStream_t s)
 {
-  memcpy(dst, p.wgs.data(), p.wgs.size() * sizeof(tx_map_wg));
-  memcpy(dst + align_up(p.wgs.size() * sizeof(tx_map_wg), 16), p.jobs.data(), p.jobs.size() * sizeof(tx_map_job));
-}
-
-/* the launches over the uploaded tables at `base` */
-int txm_launch(const TxMapPlan &p, const uint8_t *base, const uint32_t *lay, uint32_t *tx, uint64_t tx_stride, hipStream_t s)
-{
-  const tx_map_wg *wgs = reinterpret_cast<const tx_map_wg *>(base);
-  const tx_map_job *jobs = reinterpret_cast<const tx_map_job *>(base + align_up(p.wgs.size() * sizeof(tx_map_wg), 16));
   uint32_t first = 0;
   for (uint32_t pattern = 0; pattern < NR_PDM_PATTERNS; pattern++) {
     HIP_TRY(nr_launch_tx_map(pattern, wgs + first, p.n_wg[pattern], jobs, lay, tx, tx_stride, s));
@@ -200,13 +182,12 @@ int32_t nrLDPC_hip_pdsch_dmrs_host(uint32_t c_init, uint32_t dmrs_offset, uint32
     return set_error("pdsch_dmrs_host: dmrs_offset or n above 2^20");
   if (n == 0)
     return 0;
-  const uint32_t w0 = (2u * dmrs_offset) >> 5;
-  std::vector<uint32_t> gold(((2u * (dmrs_offset + n) - 1u) >> 5) - w0 + 1u);
-  if (nr_hip_gold_words(c_init, w0, (uint32_t)gold.size(), gold.data()) != 0)
+  std::vector<uint32_t> gold;
+  uint32_t w0;
+  if (!dmrs_gold_words(c_init, dmrs_offset, n, gold, w0))
     return set_error("pdsch_dmrs_host: the Gold sequence could not be generated");
   for (uint32_t k = 0; k < n; k++) {
-    const uint32_t bit = 2u * (dmrs_offset + k) - 32u * w0;
-    const uint32_t c = nr_qam_point(2u, (gold[bit >> 5] >> (bit & 31u)) & 3u);
+    const uint32_t c = nr_qam_point(2u, (uint32_t)dmrs_bits(gold, w0, dmrs_offset + k) & 3u);
     out[2 * (size_t)k] = (int16_t)(c & 0xffffu);
     out[2 * (size_t)k + 1] = (int16_t)(c >> 16);
   }
@@ -234,20 +215,16 @@ int32_t nrLDPC_hip_pdsch_map_segments(const nrLDPC_hip_pdsch_alloc_t *alloc, uin
   for (uint32_t i = 0; i < n_alloc; i++) {
     const nrLDPC_hip_pdsch_alloc_t &a = alloc[i];
     const uint32_t N = a.fft_size, type = a.dmrs_config_type;
-    if (a.nr_of_symbols == 0 || a.start_symbol >= NR_RXG_SYMBOLS || a.nr_of_symbols > NR_RXG_SYMBOLS - a.start_symbol)
-      return set_error("pdsch_map_segments: the symbols must lie within the slot's 14");
+    if (alloc_check_symbols("pdsch_map_segments", a.start_symbol, a.nr_of_symbols) != 0)
+      return -1;
     if (a.Nl < 1 || a.Nl > NR_PDM_MAX_LAYERS)
       return set_error("pdsch_map_segments: Nl must be 1..4");
     if (type > 1)
       return set_error("pdsch_map_segments: dmrs_config_type must be 0 (type 1) or 1 (type 2)");
     if (a.amp < 1 || a.amp > 32767)
       return set_error("pdsch_map_segments: amp must be 1..32767");
-    if (a.rb_size == 0)
-      return set_error("pdsch_map_segments: rb_size is 0");
-    if (N == 0 || (uint64_t)a.rb_size * 12u > N)
-      return set_error("pdsch_map_segments: the allocation is wider than fft_size");
-    if (a.first_carrier_offset >= N)
-      return set_error("pdsch_map_segments: first_carrier_offset must be below fft_size");
+    if (alloc_check_width("pdsch_map_segments", a.rb_size, N, a.first_carrier_offset) != 0)
+      return -1;
     if (a.scid > 1)
       return set_error("pdsch_map_segments: scid must be 0 or 1");
     if (a.dl_dmrs_scrambling_id > 0xffffu)
@@ -298,9 +275,7 @@ int32_t nrLDPC_hip_pdsch_map_segments(const nrLDPC_hip_pdsch_alloc_t *alloc, uin
         g.l_prime = (uint8_t)l_prime;
         memcpy(g.port, port, sizeof port);
         g.dmrs_offset = (a.rb_start + (a.si_rnti ? 0u : a.bwp_start)) * (type == 0 ? 6u : 4u); /* :260-263 */
-        /* nr_gold.c:87-88 */
-        g.c_init = (uint32_t)(((1ull << 17) * (NR_RXG_SYMBOLS * a.slot + sym + 1u) * (2ull * a.dl_dmrs_scrambling_id + 1u) + 2ull * a.dl_dmrs_scrambling_id +
-                               a.scid) & 0x7fffffffull);
+        g.c_init = dmrs_c_init(a.slot, sym, a.dl_dmrs_scrambling_id, a.scid);
       }
       uint32_t pm, dm;
       nr_pdm_masks(g.pattern, g.ncdm, nr_pdm_delta(g.pattern, port[0] < nr_pdm_ports(g.pattern) ? port[0] : 0u), &pm, &dm);
@@ -315,12 +290,7 @@ int32_t nrLDPC_hip_pdsch_map_segments(const nrLDPC_hip_pdsch_alloc_t *alloc, uin
     if (m != a.plane)
       return set_error("pdsch_map_segments: the data REs of the symbols do not add up to plane");
   }
-  if (segs.size() > cap)
-    return set_error("pdsch_map_segments: more descriptors than cap");
-  if (!segs.empty())
-    memcpy(seg_out, segs.data(), segs.size() * sizeof segs[0]);
-  *n_seg_out = (uint32_t)segs.size();
-  return 0;
+  return emit_segments(segs, seg_out, cap, n_seg_out, "pdsch_map_segments: more descriptors than cap");
 }
 
 int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdataF, uint64_t tx_ant_stride, uint32_t n_tx,
@@ -328,8 +298,8 @@ int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdata
 {
   if (n_tx < 1 || n_tx > NR_PDM_MAX_TX)
     return set_error("pdsch_resource_mapping: n_tx must be 1..8");
-  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
-    return set_error("pdsch_resource_mapping: mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE");
+  if (check_mem("pdsch_resource_mapping", mem) != 0)
+    return -1;
   if (n_seg && (!layers || !txdataF || !seg))
     return set_error("null argument");
   TxMapPlan p;
@@ -338,61 +308,54 @@ int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdata
   if (n_seg == 0)
     return 0;
   if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    const int ord = scr_device_ordinal(txdataF);
-    if (ord < 0 || !rxf_dev_ok(txdataF, ord) || !rxf_dev_ok(layers, ord))
-      return set_error("pdsch_resource_mapping: DEVICE mem needs every array in device memory of one GPU, 4-byte aligned");
-    Device *dv = device_for_ordinal(ord);
-    if (!dv)
-      return -1;
-    UseDevice use(*dv);
-    if (rxf_check_stream("pdsch_resource_mapping", static_cast<hipStream_t>(stream)) != 0)
+    DeviceCall dc;
+    if (dc.open("pdsch_resource_mapping", {{txdataF, 4}, {layers, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 ||
+        dc.refuse_capture("pdsch_resource_mapping") != 0)
       return -1;
     txm_plan_wgs(seg, n_seg, n_tx, tx_ant_stride, txdataF, p);
-    TbCtx &c = tls_tb;
-    hipStream_t s;
-    const size_t bytes = txm_jobs_bytes(p);
-    if (tb_begin(s, static_cast<hipStream_t>(stream), false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 || c.jobs_d.ensure(bytes) != 0)
+    const auto tab = table2(p.wgs, p.jobs);
+    uint8_t *base = dc.upload(tab);
+    if (!base)
       return -1;
-    txm_write_jobs(p, c.jobs_h.p);
-    if (tb_upload_jobs(c, c.jobs_d.p, bytes, s) != 0)
-      return -1;
-    return txm_launch(p, c.jobs_d.p, reinterpret_cast<const uint32_t *>(layers), reinterpret_cast<uint32_t *>(txdataF), tx_ant_stride, s);
+    return txm_launch(p, tab.first(base), tab.second(base), reinterpret_cast<const uint32_t *>(layers), reinterpret_cast<uint32_t *>(txdataF),
+                      tx_ant_stride, dc.s);
   }
-  if (ensure_ready() != 0)
+  StagedCall st;
+  if (st.open() != 0)
     return -1;
-  UseDevice use(g.dev[0]);
-  ThreadCtx &c = tls_ctx;
   /* the device reads a copy of the span of the layer planes the descriptors reach and works on a bounce of the span of the grid
    * from the lowest to the highest c16 written */
   for (uint32_t i = 0; i < n_seg; i++) {
     p.jobs[i].tx_off -= p.out_lo;
     p.jobs[i].lay_off -= p.lay_lo;
   }
-  const size_t lay_b = align_up((size_t)(p.lay_hi - p.lay_lo) * 4u, 16), out_b = (size_t)(p.out_hi - p.out_lo) * 4u;
-  /* the table's size does not depend on the phases: one piece more per (descriptor, antenna) at the most */
+  const size_t lay_n = (size_t)(p.lay_hi - p.lay_lo) * 4u, out_b = (size_t)(p.out_hi - p.out_lo) * 4u;
+  /* the workgroup table's phases depend on where the bounce lies, so the buffers come first, for a table of the largest size:
+   * one piece more per (descriptor, antenna) at the most */
   size_t max_wg = 0;
   for (uint32_t i = 0; i < n_seg; i++)
     max_wg += (size_t)n_tx * ((12u * (size_t)seg[i].rb_size + 3u) / (NR_TXM_THREADS * NR_TXM_GROUP) + 1u);
-  const size_t jobs_cap = align_up(max_wg * sizeof(tx_map_wg), 16) + align_up(p.jobs.size() * sizeof(tx_map_job), 16);
-  if (c.ensure(jobs_cap + lay_b, out_b) != 0)
+  if (st.ensure(out_b, Table2<tx_map_wg, const tx_map_job>::bytes(max_wg, p.jobs.size()) + align_up(lay_n, 16)) != 0)
     return -1;
-  txm_plan_wgs(seg, n_seg, n_tx, tx_ant_stride, c.d_out, p);
-  const size_t jobs_b = txm_jobs_bytes(p);
-  txm_write_jobs(p, c.h_in);
-  memcpy(c.h_in + jobs_b, layers + 2 * p.lay_lo, (size_t)(p.lay_hi - p.lay_lo) * 4u);
-  HIP_TRY(hipMemcpyAsync(c.d_in, c.h_in, jobs_b + lay_b, hipMemcpyHostToDevice, c.stream));
-  if (txm_launch(p, c.d_in, reinterpret_cast<const uint32_t *>(c.d_in + jobs_b), reinterpret_cast<uint32_t *>(c.d_out), tx_ant_stride, c.stream) != 0)
+  txm_plan_wgs(seg, n_seg, n_tx, tx_ant_stride, st.d_out(), p);
+  const auto tab = table2(p.wgs, p.jobs);
+  const size_t tab_o = st.take(tab.bytes()), lay_o = st.take(lay_n);
+  tab.write(st.h(tab_o));
+  memcpy(st.h(lay_o), layers + 2 * p.lay_lo, lay_n);
+  const auto launch = [&] {
+    return txm_launch(p, tab.first(st.d(tab_o)), tab.second(st.d(tab_o)), reinterpret_cast<const uint32_t *>(st.d(lay_o)),
+                      reinterpret_cast<uint32_t *>(st.d_out()), tx_ant_stride, st.stream());
+  };
+  if (st.run(st.top, launch, out_b) != 0)
     return -1;
-  HIP_TRY(hipMemcpyAsync(c.h_out, c.d_out, out_b, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
   /* only the write set goes to the caller's array */
   for (uint32_t i = 0; i < n_seg; i++) {
     const uint32_t n_re = 12u * seg[i].rb_size, first = std::min(n_re, seg[i].fft_size - seg[i].start_re);
     for (uint32_t a = 0; a < n_tx; a++) {
       const uint64_t base = seg[i].tx_off + (uint64_t)a * tx_ant_stride;
-      memcpy(txdataF + 2 * (base + seg[i].start_re), c.h_out + 4u * (base + seg[i].start_re - p.out_lo), (size_t)first * 4u);
+      memcpy(txdataF + 2 * (base + seg[i].start_re), st.h_out() + 4u * (base + seg[i].start_re - p.out_lo), (size_t)first * 4u);
       if (first < n_re)
-        memcpy(txdataF + 2 * base, c.h_out + 4u * (base - p.out_lo), (size_t)(n_re - first) * 4u);
+        memcpy(txdataF + 2 * base, st.h_out() + 4u * (base - p.out_lo), (size_t)(n_re - first) * 4u);
     }
   }
   return 0;

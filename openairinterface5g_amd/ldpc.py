@@ -1095,6 +1095,43 @@ EXPORTS += ["nrLDPC_hip_ulsch_channel_level", "nrLDPC_hip_ulsch_channel_compensa
             "nrLDPC_hip_ulsch_level_host"]
 
 
+def _struct_array(T, dicts, keys, bytes_=()):
+    """dicts with the fields `keys` of ctypes structure T (a missing one is 0; those in bytes_ are cut to 8 bits, a sequence fills
+    an array field) -> T[max(n, 1)]; the library checks the values"""
+    arr = (T * max(len(dicts), 1))()
+    for i, d in enumerate(dicts):
+        for k in keys:
+            v = d.get(k, 0)
+            if isinstance(v, (list, tuple)):
+                v = type(getattr(arr[i], k))(*[x & 0xff for x in (list(v) + [0] * 4)[:4]])
+            setattr(arr[i], k, v & 0xff if k in bytes_ else v)
+    return arr
+
+
+def _mem_of(arrays, stream, int32=()):
+    """What the slot-level wrappers pass for their arrays: numpy -> HOST mem, torch -> DEVICE mem on `stream` or on the current
+    stream.  `arrays` are int16, `int32` arrays int32 (None: not given), all C-contiguous and of one kind -- torch tensors on the GPU
+    of the first.  Returns (ptr, numel, mem, stream): ptr(a) = the address of a (None for None), numel(a) = its elements."""
+    given = [a for a in tuple(arrays) + tuple(int32) if a is not None]
+    if isinstance(arrays[0], np.ndarray):
+        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in arrays)
+        assert all(a is None or (a.dtype == np.int32 and a.flags.c_contiguous) for a in int32)
+        return (lambda a: None if a is None else a.ctypes.data), (lambda a: a.size), MEM_HOST, None
+    import torch
+    assert all(a.is_cuda and a.is_contiguous() and a.device == arrays[0].device for a in given)
+    assert all(a.dtype == torch.int16 for a in arrays) and all(a is None or a.dtype == torch.int32 for a in int32)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    return (lambda a: None if a is None else a.data_ptr()), (lambda a: a.numel()), MEM_DEVICE, s
+
+
+def _level_out(ch, out, n):
+    """where a level call writes: numpy -> a new int32[max(n, 1)]; torch -> the caller's `out`, checked"""
+    if isinstance(ch, np.ndarray):
+        return np.zeros(max(n, 1), np.int32)
+    assert out is not None and out.numel() >= n
+    return out
+
+
 class nrLDPC_hip_rx_seg_t(C.Structure):
     _fields_ = [("tb", C.c_uint32), ("Qm", C.c_uint8), ("pad", C.c_uint8 * 3), ("nb_re", C.c_uint32), ("plane", C.c_uint32),
                 ("sym_off", C.c_uint32), ("pad2", C.c_uint32), ("rx_off", C.c_uint64), ("ch_off", C.c_uint64), ("rec_off", C.c_uint64)]
@@ -1117,11 +1154,7 @@ def _rxf_lib():
 
 def _rx_seg_array(segs):
     """dicts (tb, Qm, nb_re, plane, sym_off, rx_off, ch_off, rec_off) -> nrLDPC_hip_rx_seg_t[n]; the library checks the values"""
-    arr = (nrLDPC_hip_rx_seg_t * max(len(segs), 1))()
-    for i, s in enumerate(segs):
-        arr[i] = nrLDPC_hip_rx_seg_t(tb=s["tb"], Qm=s["Qm"] & 0xff, nb_re=s["nb_re"], plane=s.get("plane", 0), sym_off=s.get("sym_off", 0),
-                                     rx_off=s.get("rx_off", 0), ch_off=s.get("ch_off", 0), rec_off=s.get("rec_off", 0))
-    return arr
+    return _struct_array(nrLDPC_hip_rx_seg_t, segs, ("tb", "Qm", "nb_re", "plane", "sym_off", "rx_off", "ch_off", "rec_off"), ("Qm",))
 
 
 def rx_front_segments(tbs, nb_re_per_symbol, rec_off=None):
@@ -1174,21 +1207,11 @@ def ulsch_channel_level(ch, n_rx, ant_stride, first_sym, out=None, stream=None):
     """nrLDPC_hip_ulsch_channel_level: first_sym = one descriptor per block (rx_front_segments).  numpy int16 `ch` -> host call,
     returns int32[n_tb]; torch int16 CUDA tensor -> device call enqueued on `stream` into `out`, a torch int32 CUDA tensor of at
     least n_tb elements on the same GPU; returns `out`."""
-    L = _rxf_lib()
-    n, arr = len(first_sym), _rx_seg_array(first_sym)
-    if isinstance(ch, np.ndarray):
-        assert ch.dtype == np.int16 and ch.flags.c_contiguous
-        res = np.zeros(max(n, 1), np.int32)
-        _check(L.nrLDPC_hip_ulsch_channel_level(ch.ctypes.data, n_rx, ant_stride, arr, n, res.ctypes.data, MEM_HOST, None),
-               "nrLDPC_hip_ulsch_channel_level")
-        return res[:n]
-    import torch
-    assert ch.is_cuda and ch.dtype == torch.int16 and ch.is_contiguous()
-    assert out is not None and out.is_cuda and out.device == ch.device and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(L.nrLDPC_hip_ulsch_channel_level(ch.data_ptr(), n_rx, ant_stride, arr, n, out.data_ptr(), MEM_DEVICE, s),
+    n, res = len(first_sym), _level_out(ch, out, len(first_sym))
+    ptr, _, mem, s = _mem_of((ch,), stream, (res,))
+    _check(_rxf_lib().nrLDPC_hip_ulsch_channel_level(ptr(ch), n_rx, ant_stride, _rx_seg_array(first_sym), n, ptr(res), mem, s),
            "nrLDPC_hip_ulsch_channel_level")
-    return out
+    return res[:n] if mem == MEM_HOST else res
 
 
 def ulsch_channel_compensation(rx, ch, n_rx, ant_stride, segs, shift, records, stream=None):
@@ -1196,20 +1219,11 @@ def ulsch_channel_compensation(rx, ch, n_rx, ant_stride, segs, shift, records, s
     ulsch_channel_level), records = the int16 array the blocks' symbol records lie in, written in place -- only the segments'
     entries.  numpy arrays -> host call; torch CUDA tensors (one GPU, contiguous) -> device call enqueued on `stream`.  Returns
     `records`."""
-    L = _rxf_lib()
-    arr = _rx_seg_array(segs)
     if isinstance(rx, np.ndarray):
-        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (rx, ch, records))
-        sh = np.ascontiguousarray(shift, np.int32)
-        _check(L.nrLDPC_hip_ulsch_channel_compensation(rx.ctypes.data, ch.ctypes.data, n_rx, ant_stride, arr, len(segs), sh.ctypes.data,
-                                                       records.ctypes.data, MEM_HOST, None), "nrLDPC_hip_ulsch_channel_compensation")
-        return records
-    import torch
-    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == rx.device for a in (rx, ch, records))
-    assert shift.is_cuda and shift.dtype == torch.int32 and shift.is_contiguous() and shift.device == rx.device
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(L.nrLDPC_hip_ulsch_channel_compensation(rx.data_ptr(), ch.data_ptr(), n_rx, ant_stride, arr, len(segs), shift.data_ptr(),
-                                                   records.data_ptr(), MEM_DEVICE, s), "nrLDPC_hip_ulsch_channel_compensation")
+        shift = np.ascontiguousarray(shift, np.int32)
+    ptr, _, mem, s = _mem_of((rx, ch, records), stream, (shift,))
+    _check(_rxf_lib().nrLDPC_hip_ulsch_channel_compensation(ptr(rx), ptr(ch), n_rx, ant_stride, _rx_seg_array(segs), len(segs), ptr(shift), ptr(records),
+                                                            mem, s), "nrLDPC_hip_ulsch_channel_compensation")
     return records
 
 
@@ -1257,10 +1271,7 @@ def _rxg_lib():
 
 def _rx_grid_seg_array(segs):
     """dicts with the fields of nrLDPC_hip_rx_grid_seg_t -> an array of them; the library checks the values"""
-    arr = (nrLDPC_hip_rx_grid_seg_t * max(len(segs), 1))()
-    for i, s in enumerate(segs):
-        arr[i] = nrLDPC_hip_rx_grid_seg_t(**{k: (s.get(k, 0) & 0xff if k in ("Qm", "pattern") else s.get(k, 0)) for k in _RXG_SEG_KEYS})
-    return arr
+    return _struct_array(nrLDPC_hip_rx_grid_seg_t, segs, _RXG_SEG_KEYS, ("Qm", "pattern"))
 
 
 def _rxg_p(pattern, j):
@@ -1299,10 +1310,7 @@ def ulsch_extract_host(rx_sym, ch_sym, pattern, fft_size, start_re, nb_re):
 def pusch_grid_segments(allocs, cap=None):
     """nrLDPC_hip_pusch_grid_segments: allocs = dicts with the fields of nrLDPC_hip_pusch_alloc_t.  Returns (segs, first_sym), lists
     of dicts with the fields of nrLDPC_hip_rx_grid_seg_t."""
-    n = len(allocs)
-    arr = (nrLDPC_hip_pusch_alloc_t * max(n, 1))()
-    for i, a in enumerate(allocs):
-        arr[i] = nrLDPC_hip_pusch_alloc_t(**{k: a.get(k, 0) for k in _RXG_ALLOC_KEYS})
+    n, arr = len(allocs), _struct_array(nrLDPC_hip_pusch_alloc_t, allocs, _RXG_ALLOC_KEYS)
     cap = 14 * n if cap is None else cap
     out, first, n_out = (nrLDPC_hip_rx_grid_seg_t * max(cap, 1))(), (nrLDPC_hip_rx_grid_seg_t * max(n, 1))(), C.c_uint32(0)
     _check(_rxg_lib().nrLDPC_hip_pusch_grid_segments(arr, n, out, cap, first, C.byref(n_out)), "nrLDPC_hip_pusch_grid_segments")
@@ -1314,47 +1322,24 @@ def ulsch_channel_level_grid(ch, n_rx, ch_ant_stride, first_sym, out=None, strea
     """nrLDPC_hip_ulsch_channel_level_grid: ch = the full-width channel estimates, first_sym = one grid descriptor per block
     (pusch_grid_segments).  numpy int16 -> host call, returns int32[n_tb]; torch int16 CUDA tensor -> device call enqueued on
     `stream` into `out` (torch int32 CUDA, >= n_tb elements); returns `out`."""
-    L = _rxg_lib()
-    n, arr = len(first_sym), _rx_grid_seg_array(first_sym)
-    if isinstance(ch, np.ndarray):
-        assert ch.dtype == np.int16 and ch.flags.c_contiguous
-        _rxg_check_extent(first_sym, n_rx, 0, ch_ant_stride, None, ch.size // 2)
-        res = np.zeros(max(n, 1), np.int32)
-        _check(L.nrLDPC_hip_ulsch_channel_level_grid(ch.ctypes.data, n_rx, ch_ant_stride, arr, n, res.ctypes.data, MEM_HOST, None),
-               "nrLDPC_hip_ulsch_channel_level_grid")
-        return res[:n]
-    import torch
-    assert ch.is_cuda and ch.dtype == torch.int16 and ch.is_contiguous()
-    assert out is not None and out.is_cuda and out.device == ch.device and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
-    _rxg_check_extent(first_sym, n_rx, 0, ch_ant_stride, None, ch.numel() // 2)
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(L.nrLDPC_hip_ulsch_channel_level_grid(ch.data_ptr(), n_rx, ch_ant_stride, arr, n, out.data_ptr(), MEM_DEVICE, s),
+    n, res = len(first_sym), _level_out(ch, out, len(first_sym))
+    ptr, numel, mem, s = _mem_of((ch,), stream, (res,))
+    _rxg_check_extent(first_sym, n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _check(_rxg_lib().nrLDPC_hip_ulsch_channel_level_grid(ptr(ch), n_rx, ch_ant_stride, _rx_grid_seg_array(first_sym), n, ptr(res), mem, s),
            "nrLDPC_hip_ulsch_channel_level_grid")
-    return out
+    return res[:n] if mem == MEM_HOST else res
 
 
 def ulsch_channel_compensation_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, shift, records, stream=None):
     """nrLDPC_hip_ulsch_channel_compensation_grid: rx = the OFDM grid, ch = the full-width channel estimates, segs = the grid
     descriptors (pusch_grid_segments); shift and records as ulsch_channel_compensation.  numpy arrays -> host call; torch CUDA
     tensors -> device call enqueued on `stream`.  Returns `records`."""
-    L = _rxg_lib()
-    arr = _rx_grid_seg_array(segs)
     if isinstance(rx, np.ndarray):
-        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (rx, ch, records))
-        _rxg_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.size // 2, ch.size // 2)
-        sh = np.ascontiguousarray(shift, np.int32)
-        _check(L.nrLDPC_hip_ulsch_channel_compensation_grid(rx.ctypes.data, ch.ctypes.data, n_rx, rx_ant_stride, ch_ant_stride, arr, len(segs),
-                                                            sh.ctypes.data, records.ctypes.data, MEM_HOST, None),
-               "nrLDPC_hip_ulsch_channel_compensation_grid")
-        return records
-    import torch
-    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == rx.device for a in (rx, ch, records))
-    assert shift.is_cuda and shift.dtype == torch.int32 and shift.is_contiguous() and shift.device == rx.device
-    _rxg_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.numel() // 2, ch.numel() // 2)
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(L.nrLDPC_hip_ulsch_channel_compensation_grid(rx.data_ptr(), ch.data_ptr(), n_rx, rx_ant_stride, ch_ant_stride, arr, len(segs),
-                                                        shift.data_ptr(), records.data_ptr(), MEM_DEVICE, s),
-           "nrLDPC_hip_ulsch_channel_compensation_grid")
+        shift = np.ascontiguousarray(shift, np.int32)
+    ptr, numel, mem, s = _mem_of((rx, ch, records), stream, (shift,))
+    _rxg_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, numel(rx) // 2, numel(ch) // 2)
+    _check(_rxg_lib().nrLDPC_hip_ulsch_channel_compensation_grid(ptr(rx), ptr(ch), n_rx, rx_ant_stride, ch_ant_stride, _rx_grid_seg_array(segs), len(segs),
+                                                                 ptr(shift), ptr(records), mem, s), "nrLDPC_hip_ulsch_channel_compensation_grid")
     return records
 
 
@@ -1400,10 +1385,7 @@ def _chest_lib():
 
 def _chest_seg_array(segs):
     """dicts with the fields of nrLDPC_hip_chest_seg_t -> an array of them; the library checks the values"""
-    arr = (nrLDPC_hip_chest_seg_t * max(len(segs), 1))()
-    for i, s in enumerate(segs):
-        arr[i] = nrLDPC_hip_chest_seg_t(**{k: (s.get(k, 0) & 0xff if k in ("mode", "port") else s.get(k, 0)) for k in _CHEST_SEG_KEYS})
-    return arr
+    return _struct_array(nrLDPC_hip_chest_seg_t, segs, _CHEST_SEG_KEYS, ("mode", "port"))
 
 
 def _chest_check_extent(segs, n_rx, rx_stride, ch_stride, rx_len, ch_len, delay_len):
@@ -1448,10 +1430,7 @@ def pusch_chest_segments(allocs, cfgs, n_rx, cap=None):
     scid, dmrs_scrambling_id, port, chest_freq.  Returns a list of dicts with the fields of nrLDPC_hip_chest_seg_t."""
     n = len(allocs)
     assert len(cfgs) == n
-    arr, carr = (nrLDPC_hip_pusch_alloc_t * max(n, 1))(), (nrLDPC_hip_pusch_chest_cfg_t * max(n, 1))()
-    for i, (a, c) in enumerate(zip(allocs, cfgs)):
-        arr[i] = nrLDPC_hip_pusch_alloc_t(**{k: a.get(k, 0) for k in _RXG_ALLOC_KEYS})
-        carr[i] = nrLDPC_hip_pusch_chest_cfg_t(**{k: c.get(k, 0) for k in _CHEST_CFG_KEYS})
+    arr, carr = _struct_array(nrLDPC_hip_pusch_alloc_t, allocs, _RXG_ALLOC_KEYS), _struct_array(nrLDPC_hip_pusch_chest_cfg_t, cfgs, _CHEST_CFG_KEYS)
     cap = 14 * n if cap is None else cap
     out, n_out = (nrLDPC_hip_chest_seg_t * max(cap, 1))(), C.c_uint32(0)
     _check(_chest_lib().nrLDPC_hip_pusch_chest_segments(arr, carr, n, n_rx, out, cap, C.byref(n_out)), "nrLDPC_hip_pusch_chest_segments")
@@ -1462,24 +1441,12 @@ def pusch_channel_estimation(rx, rx_ant_stride, ch, ch_ant_stride, n_rx, segs, e
     """nrLDPC_hip_pusch_channel_estimation: rx = the OFDM grid, ch = the full-width channel estimates (written), segs = the
     descriptors (pusch_chest_segments), est_delay = int32 per (descriptor, antenna) or None (0 everywhere).  numpy int16 arrays
     -> host call; torch int16 CUDA tensors -> device call enqueued on `stream`.  Returns ch."""
-    L = _chest_lib()
-    arr = _chest_seg_array(segs)
-    if isinstance(rx, np.ndarray):
-        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (rx, ch))
-        dl = None if est_delay is None else np.ascontiguousarray(est_delay, np.int32)
-        _chest_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.size // 2, ch.size // 2, None if dl is None else dl.size)
-        _check(L.nrLDPC_hip_pusch_channel_estimation(rx.ctypes.data, rx_ant_stride, ch.ctypes.data, ch_ant_stride, n_rx, arr, len(segs),
-                                                     None if dl is None else dl.ctypes.data, MEM_HOST, None), "nrLDPC_hip_pusch_channel_estimation")
-        return ch
-    import torch
-    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == rx.device for a in (rx, ch))
-    if est_delay is not None:
-        assert est_delay.is_cuda and est_delay.dtype == torch.int32 and est_delay.is_contiguous() and est_delay.device == rx.device
-    _chest_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, rx.numel() // 2, ch.numel() // 2, None if est_delay is None else est_delay.numel())
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(L.nrLDPC_hip_pusch_channel_estimation(rx.data_ptr(), rx_ant_stride, ch.data_ptr(), ch_ant_stride, n_rx, arr, len(segs),
-                                                 None if est_delay is None else est_delay.data_ptr(), MEM_DEVICE, s),
-           "nrLDPC_hip_pusch_channel_estimation")
+    if isinstance(rx, np.ndarray) and est_delay is not None:
+        est_delay = np.ascontiguousarray(est_delay, np.int32)
+    ptr, numel, mem, s = _mem_of((rx, ch), stream, (est_delay,))
+    _chest_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, numel(rx) // 2, numel(ch) // 2, None if est_delay is None else numel(est_delay))
+    _check(_chest_lib().nrLDPC_hip_pusch_channel_estimation(ptr(rx), rx_ant_stride, ptr(ch), ch_ant_stride, n_rx, _chest_seg_array(segs), len(segs),
+                                                            ptr(est_delay), mem, s), "nrLDPC_hip_pusch_channel_estimation")
     return ch
 
 
@@ -1527,14 +1494,7 @@ def _pdm_lib():
 def _pdm_seg_array(segs):
     """dicts with the fields of nrLDPC_hip_pdsch_map_seg_t (port = a sequence of up to 4) -> an array of them; the library checks the
     values"""
-    arr = (nrLDPC_hip_pdsch_map_seg_t * max(len(segs), 1))()
-    for i, s in enumerate(segs):
-        kw = {k: s.get(k, 0) for k in _PDM_SEG_KEYS if k != "port"}
-        for k in ("pattern", "Nl", "ncdm", "l_prime"):
-            kw[k] &= 0xff
-        ports = list(s.get("port", ())) + [0] * 4
-        arr[i] = nrLDPC_hip_pdsch_map_seg_t(port=(C.c_uint8 * 4)(*[p & 0xff for p in ports[:4]]), **kw)
-    return arr
+    return _struct_array(nrLDPC_hip_pdsch_map_seg_t, segs, _PDM_SEG_KEYS, ("pattern", "Nl", "ncdm", "l_prime"))
 
 
 def _pdm_check_extent(segs, n_tx, tx_stride, lay_len, tx_len):
@@ -1568,10 +1528,7 @@ def pdsch_map_host(layers, seg, layer, tx):
 def pdsch_map_segments(allocs, cap=None):
     """nrLDPC_hip_pdsch_map_segments: allocs = dicts with the fields of nrLDPC_hip_pdsch_alloc_t.  Returns a list of dicts with the
     fields of nrLDPC_hip_pdsch_map_seg_t."""
-    n = len(allocs)
-    arr = (nrLDPC_hip_pdsch_alloc_t * max(n, 1))()
-    for i, a in enumerate(allocs):
-        arr[i] = nrLDPC_hip_pdsch_alloc_t(**{k: a.get(k, 0) for k in _PDM_ALLOC_KEYS})
+    n, arr = len(allocs), _struct_array(nrLDPC_hip_pdsch_alloc_t, allocs, _PDM_ALLOC_KEYS)
     cap = 14 * n if cap is None else cap
     out, n_out = (nrLDPC_hip_pdsch_map_seg_t * max(cap, 1))(), C.c_uint32(0)
     _check(_pdm_lib().nrLDPC_hip_pdsch_map_segments(arr, n, out, cap, C.byref(n_out)), "nrLDPC_hip_pdsch_map_segments")
@@ -1582,18 +1539,8 @@ def pdsch_resource_mapping(layers, tx, tx_ant_stride, n_tx, segs, stream=None):
     """nrLDPC_hip_pdsch_resource_mapping: layers = the layer planes (dlsch_encode_symbols output), tx = the transmit grid (written),
     segs = the descriptors (pdsch_map_segments).  numpy int16 arrays -> host call; torch int16 CUDA tensors -> device call enqueued
     on `stream`.  Returns tx."""
-    L = _pdm_lib()
-    arr = _pdm_seg_array(segs)
-    if isinstance(tx, np.ndarray):
-        assert all(a.dtype == np.int16 and a.flags.c_contiguous for a in (layers, tx))
-        _pdm_check_extent(segs, n_tx, tx_ant_stride, layers.size // 2, tx.size // 2)
-        _check(L.nrLDPC_hip_pdsch_resource_mapping(layers.ctypes.data, tx.ctypes.data, tx_ant_stride, n_tx, arr, len(segs), MEM_HOST, None),
-               "nrLDPC_hip_pdsch_resource_mapping")
-        return tx
-    import torch
-    assert all(a.is_cuda and a.dtype == torch.int16 and a.is_contiguous() and a.device == tx.device for a in (layers, tx))
-    _pdm_check_extent(segs, n_tx, tx_ant_stride, layers.numel() // 2, tx.numel() // 2)
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(L.nrLDPC_hip_pdsch_resource_mapping(layers.data_ptr(), tx.data_ptr(), tx_ant_stride, n_tx, arr, len(segs), MEM_DEVICE, s),
+    ptr, numel, mem, s = _mem_of((tx, layers), stream)
+    _pdm_check_extent(segs, n_tx, tx_ant_stride, numel(layers) // 2, numel(tx) // 2)
+    _check(_pdm_lib().nrLDPC_hip_pdsch_resource_mapping(ptr(layers), ptr(tx), tx_ant_stride, n_tx, _pdm_seg_array(segs), len(segs), mem, s),
            "nrLDPC_hip_pdsch_resource_mapping")
     return tx
