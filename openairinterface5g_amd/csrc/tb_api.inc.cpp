@@ -4,6 +4,9 @@
  * (segmentation, E per segment, decoder rate mode, rate-matching geometry: nr_coding_host.c) and the job lists;
  * every byte of payload/LLR data is touched on the GPU only (tb_chain.hip + the codec kernels).
  */
+#include <memory>
+
+#include "job_layout.h"
 
 namespace {
 
@@ -51,9 +54,12 @@ struct TbPlan {
   size_t pay_lo = 0, pay_hi = 0, cod_lo = 0, cod_hi = 0, harq_lo = 0, harq_hi = 0; /* [lo, hi) of the payload, coded and harq (decode) ranges the blocks touch */
   uint32_t rx_lds_elems = 8; /* LDS the de-matching kernel needs per workgroup (int16 slots) */
   bool out_dense = true; /* the blocks' outputs tile their range: one copy back; else one per block (nothing between them is touched) */
-  size_t o_tb = 0, o_seg = 0, o_acc = 0; /* where the job arrays start in jobs_d: per TB, per segment, the zeroed per-TB state */
+  /* where the job arrays start in jobs_d (the call's upload_jobs lays them out: job_layout.h): per TB, per segment, the zeroed
+   * per-TB state */
+  size_t o_tb = 0, o_seg = 0, o_acc = 0;
   size_t o_enc = 0, o_chk = 0, o_scr = 0, o_tickets = 0, o_parts = 0; /* encode */
   size_t o_iter = 0, o_slots = 0; /* decode */
+  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(jobs_d.p + off); } /* the array at one of them */
   uint32_t max_g = 0; /* encode: the longest block of the scrambling launch (bits, or symbols) */
   int enc_threads = 64, enc_lds = 0; /* encode */
   size_t n_fast = 0, n_gen = 0; /* encode */
@@ -80,21 +86,24 @@ struct TbPlan {
    * 0.9 ms of enqueueing; nothing between the blocks is touched either way) */
   struct OutRun { size_t first, width, pitch; uint32_t rows; };
   std::vector<OutRun> out_runs;
-  void build_out_runs(const uint64_t *off, const size_t *len, uint32_t n)
+  /* out_of(i) = {offset, bytes} of block i's output */
+  template <typename Fn> void build_out_runs(uint32_t n, Fn out_of)
   {
     out_runs.clear();
     for (uint32_t i = 0; i < n; i++) {
+      const std::pair<size_t, size_t> o = out_of(i);
+      const size_t off = o.first, len = o.second;
       if (!out_runs.empty()) {
         OutRun &r = out_runs.back();
         const size_t last = r.first + (size_t)(r.rows - 1) * r.pitch;
-        if (len[i] == r.width && off[i] > last && (r.rows == 1 ? off[i] - last >= r.width : off[i] - last == r.pitch)) {
+        if (len == r.width && off > last && (r.rows == 1 ? off - last >= r.width : off - last == r.pitch)) {
           if (r.rows == 1)
-            r.pitch = (size_t)off[i] - last;
+            r.pitch = off - last;
           r.rows++;
           continue;
         }
       }
-      out_runs.push_back(OutRun{(size_t)off[i], len[i], len[i], 1u});
+      out_runs.push_back(OutRun{off, len, len, 1u});
     }
   }
   uint64_t stamp = 0; /* LRU */
@@ -396,12 +405,12 @@ uint32_t nrLDPC_hip_get_E(uint32_t G, uint32_t C, uint32_t Qm, uint32_t Nl, uint
 int32_t nrLDPC_hip_ulsch_decoder_columns(int32_t BG, uint32_t Zc, uint32_t C, uint32_t F, uint32_t K, uint32_t Tbslbrm, int32_t rv,
                                          uint32_t E, int32_t round, int32_t R)
 {
-  ldpc_code_desc_t *d = new ldpc_code_desc_t;
-  const int rc = ldpc_build_code_desc(BG, (int)Zc, R, d);
+  std::unique_ptr<ldpc_code_desc_t> d(new ldpc_code_desc_t);
+  if (ldpc_build_code_desc(BG, (int)Zc, R, d.get()) != 0) /* (a refused descriptor is not filled in) */
+    return -1;
   const int ncols = d->ncols, ncore = d->ncore;
-  delete d;
   nr_hip_rm_t rm;
-  if (rc != 0 || nr_hip_rate_match_geometry(Tbslbrm, BG, Zc, C, F, K, rv, E, &rm) != 0)
+  if (nr_hip_rate_match_geometry(Tbslbrm, BG, Zc, C, F, K, rv, E, &rm) != 0)
     return -1;
   if (!tb_trunc_enabled() || round != 0)
     return ncols;
@@ -445,39 +454,75 @@ struct TbExtent {
     }                                                                                        \
   } while (0)
 
-/* scr != nullptr (nrLDPC_hip_dlsch_encode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the chain's bit-per-byte output goes
+/* the bytes a DL block leaves at coded + coded_off: G (a bit each), its ceil(G/32) scrambled words, or its G/Qm points */
+size_t tb_tx_out_bytes(const nrLDPC_hip_tb_t &t, bool scr, bool sym)
+{
+  return sym ? (size_t)(t.G / t.Qm) * 4u : scr ? (size_t)((t.G + 31u) / 32u) * 4u : (size_t)t.G;
+}
+
+/* A staged call's outputs back: `src` = this device's copy of the caller's bytes [lo, hi), `dst` = the caller's array or its
+ * page-locked mirror, biased like it.  dense: one copy of the range; else one strided copy per run of blocks (nothing between
+ * the blocks is touched) */
+int tb_copy_outputs(const TbPlan &pl, bool dense, uint8_t *dst, const uint8_t *src, size_t lo, size_t hi, hipStream_t s)
+{
+  if (dense) {
+    HIP_TRY(hipMemcpyAsync(dst + lo, src, hi - lo, hipMemcpyDefault, s));
+    return 0;
+  }
+  for (const TbPlan::OutRun &r : pl.out_runs)
+    HIP_TRY(hipMemcpy2DAsync(dst + r.first, r.pitch, src + (r.first - lo), r.pitch, r.width, r.rows, hipMemcpyDefault, s));
+  return 0;
+}
+/* ... and, where `mirror` stands in for the caller's pageable array `dst` (both biased), the same pieces for the finish call to
+ * hand over (TbCtx::fin_copies; one contiguous block is cut over the helpers) */
+void tb_fin_outputs(TbCtx &c, const TbPlan &pl, bool dense, uint8_t *dst, const uint8_t *mirror, size_t lo, size_t hi)
+{
+  if (dense) {
+    c.fin_copies.push_back(TbCtx::FinCopy{dst + lo, mirror + lo, hi - lo, 1, hi - lo, hi - lo, nullptr});
+    return;
+  }
+  for (const TbPlan::OutRun &r : pl.out_runs)
+    c.fin_copies.push_back(TbCtx::FinCopy{dst + r.first, mirror + r.first, r.width, r.rows, r.pitch, r.pitch, nullptr});
+}
+
+/* the job lists of a plan build, on the host until they are uploaded */
+struct TxJobLists {
+  std::vector<tb_tx_tb_job> tbj;
+  std::vector<tb_tx_seg_job> sj;
+  std::vector<ldpc_enc_job> ej;
+  std::vector<tb_crc_chunk_job> cj;
+  std::vector<tb_scr_tb_job> pj; /* scrambled, three-kernel path: the bytes in scratch, then one packing launch */
+  std::vector<tb_sym_tb_job> qj; /* ... or, for symbols, one scrambling + mapping launch */
+  uint32_t n_tickets = 0; /* scrambled, fused path: the words several segments share, and their parts */
+  size_t n_parts = 0;
+};
+
+/* what the kernels of a call get: the caller's arrays, or this device's copies of the ranges the blocks touch (biased like the
+ * caller's: job offsets stay the caller's).  out_words: scrambled / symbol call on the three-kernel path -- where the packed
+ * words or points go (coded is then the scratch buffer: the segments' bytes, job out_off = scratch offsets) */
+struct TxViews { const uint8_t *payload; uint8_t *coded, *out_words; };
+
+/* one tb_tx_enqueue call: its arguments, the stream it works on, the encoder kernel in use, and its steps in the order they run.
+ * scr != nullptr (nrLDPC_hip_dlsch_encode_scrambled): scr[0 .. ntb) belong to tb[tb0 ..]; the chain's bit-per-byte output goes
  * to scratch, and one more launch packs and scrambles every block into its ceil(G/32) words at coded + coded_off.
  * sym (with scr; nrLDPC_hip_dlsch_encode_symbols): each block's output is its scrambled, mapped and layer-mapped points instead,
  * Nl planes of G / (Qm Nl) c16 words = 4 G / Qm bytes at coded + coded_off -- stored by the fused kernel's symbol instantiation,
  * or (three-kernel path) by one launch from the bytes in scratch */
-int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
-                  const nrLDPC_hip_tb_scr_t *scr = nullptr, bool sym = false)
-{
-  hipStream_t s;
-  if (tb_begin(s, s_direct, staged) != 0)
-    return -1;
-  if (ntb == 0)
-    return 0;
+struct TbTxCall {
+  const nrLDPC_hip_tb_batch_t *b; const uint32_t tb0, ntb; const bool staged; /* as tb_tx_enqueue takes them */
+  const nrLDPC_hip_tb_scr_t *scr; const bool sym;
+  hipStream_t s; TbCtx &c; /* what tb_begin gave the call */
   const nrLDPC_hip_tb_t *tbs = b->tb + tb0;
-  TbCtx &c = tls_tb;
-  const bool fused = ldpc_enc_is_packed() != 0;
-  /* bit 2: scrambled (its key also holds the scr bytes: a scrambled and an unscrambled plan never match); bit 3: symbols (never
-   * a packed-word plan, nor the reverse) */
-  const uint64_t salt[3] = {(fused ? 1u : 0u) | (tb_trunc_enabled() ? 2u : 0u) | (scr ? 4u : 0u) | (sym ? 8u : 0u), 0, 0};
-  const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
-  TbPlan *hit = c.tx.find(tbs, ntb, salt, scr, scr_n);
-  TbPlan &pl = hit ? *hit : c.tx.victim();
-  if (!hit) {
-    std::vector<tb_tx_tb_job> tbj(ntb);
-    std::vector<tb_tx_seg_job> sj;
-    std::vector<ldpc_enc_job> ej;
-    std::vector<tb_crc_chunk_job> cj;
-    /* scrambled, three-kernel path: the bytes in scratch, then one packing launch (pj) */
-    std::vector<tb_scr_tb_job> pj(scr && !sym && !fused ? ntb : 0);
-    std::vector<tb_sym_tb_job> qj(sym && !fused ? ntb : 0); /* ... or, for symbols, one scrambling + mapping launch */
+  const bool fused = ldpc_enc_is_packed() != 0; /* one segment kernel; else segmentation, encoder and rate matching launches */
+
+  /* plan, part 1: the per-TB and per-segment jobs, and what the plan keeps of them */
+  int plan_jobs(TbPlan &pl, TxJobLists &jl)
+  {
+    jl.tbj.resize(ntb);
+    const bool scr_bytes = scr && !fused; /* the segments' bytes stay in scratch for the packing / mapping launch */
+    jl.pj.resize(scr_bytes && !sym ? ntb : 0);
+    jl.qj.resize(sym && !fused ? ntb : 0);
     uint32_t max_g = 0;
-    uint32_t n_tickets = 0; /* scrambled, fused path: the words several segments share, and their parts */
-    size_t n_parts = 0;
     Arena ar;
     int enc_threads = 64, enc_lds = 0;
     TbExtent ex;
@@ -500,38 +545,40 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       const CodeEntry *ce = get_code(t.BG, (int)sg.Zc, t.BG == 1 ? 13 : 15);
       if (!ce)
         return -1;
-      tbj[i].payload_off = t.payload_off;
-      tbj[i].b_off = ar.take(B / 8 + 4);
-      tbj[i].A = t.A;
-      tbj[i].B = B;
-      tbj[i].crc_type = t.A > NR_HIP_MAX_PDSCH_TBS ? NR_HIP_CRC24_A : NR_HIP_CRC16;
+      tb_tx_tb_job &tj = jl.tbj[i];
+      tj.payload_off = t.payload_off;
+      tj.b_off = ar.take(B / 8 + 4);
+      tj.A = t.A;
+      tj.B = B;
+      tj.crc_type = t.A > NR_HIP_MAX_PDSCH_TBS ? NR_HIP_CRC24_A : NR_HIP_CRC16;
       ex.add(ex.pay_lo, ex.pay_hi, (size_t)t.payload_off, (size_t)t.payload_off + t.A / 8);
       /* scrambled: the caller's array takes the packed words.  Fused: the segment kernel stores them itself (out_off = the TB's
        * first byte); three-kernel path: the bytes stay in scratch at byte_base for the packing launch */
-      const size_t out_len = sym ? (size_t)(t.G / t.Qm) * 4u : scr ? (size_t)((t.G + 31u) / 32u) * 4u : (size_t)t.G;
-      const bool scr_bytes = scr && !fused;
+      const size_t out_len = tb_tx_out_bytes(t, scr != nullptr, sym);
       const uint64_t byte_base = scr_bytes ? (uint64_t)ar.take(t.G + 16) : t.coded_off;
-      const size_t seg_first = sj.size();
+      const size_t seg_first = jl.sj.size();
       if (scr_bytes && sym) {
-        qj[i].in_off = byte_base;
-        qj[i].out_off = t.coded_off;
-        qj[i].G = t.G;
-        qj[i].c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
-        qj[i].Qm = t.Qm;
-        qj[i].Nl = t.Nl;
+        tb_sym_tb_job &q = jl.qj[i];
+        q.in_off = byte_base;
+        q.out_off = t.coded_off;
+        q.G = t.G;
+        q.c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
+        q.Qm = t.Qm;
+        q.Nl = t.Nl;
         max_g = std::max(max_g, t.G / t.Qm); /* (symbols) */
       } else if (scr_bytes) {
-        pj[i].in_off = byte_base;
-        pj[i].out_off = t.coded_off;
-        pj[i].G = t.G;
-        pj[i].c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
+        tb_scr_tb_job &p = jl.pj[i];
+        p.in_off = byte_base;
+        p.out_off = t.coded_off;
+        p.G = t.G;
+        p.c_init = nr_gold_c_init(scr[i].n_RNTI, scr[i].q, scr[i].Nid);
         max_g = std::max(max_g, t.G);
       }
       ex.add(ex.cod_lo, ex.cod_hi, (size_t)t.coded_off, (size_t)t.coded_off + out_len);
       ex.cod_sum += out_len;
-      const uint32_t chunk0 = (uint32_t)cj.size();
+      const uint32_t chunk0 = (uint32_t)jl.cj.size();
       for (uint32_t fb = 0; fb < t.A / 8; fb += crc_chunk)
-        cj.push_back(tb_crc_chunk_job{i, fb | (crc_chunk == TB_CRC_CHUNK_SMALL ? 0x80000000u : 0u)});
+        jl.cj.push_back(tb_crc_chunk_job{i, fb | (crc_chunk == TB_CRC_CHUNK_SMALL ? 0x80000000u : 0u)});
       const ldpc_code_desc_t &hc = ce->host;
       const int N = (hc.ncols - 2) * hc.Z;
       int nthr, nlds;
@@ -544,7 +591,7 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
       for (uint32_t r = 0; r < sg.C; r++) {
         tb_tx_seg_job j;
         memset(&j, 0, sizeof(j));
-        j.b_off = fused ? t.payload_off : tbj[i].b_off; /* fused: the segment's bytes come straight from the payload array */
+        j.b_off = fused ? t.payload_off : tj.b_off; /* fused: the segment's bytes come straight from the payload array */
         if (!fused) { /* the fused kernel keeps c and d in LDS */
           j.c_off = ar.take(sg.K / 8 + 4);
           j.d_off = ar.take(N);
@@ -570,10 +617,10 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
           j.crc_len = (B - t.A) / 8;
           j.crc_pos = t.A / 8 - r * ((sg.Kprime - sg.L) >> 3);
           j.crc_chunk0 = chunk0;
-          j.crc_nchunks = (uint32_t)cj.size() - chunk0;
+          j.crc_nchunks = (uint32_t)jl.cj.size() - chunk0;
         }
         r_offset += j.E;
-        sj.push_back(j);
+        jl.sj.push_back(j);
         /* the fused kernel selects the E transmitted bits straight from the code word in LDS: parity columns behind the last
          * position the selection reaches are never looked at, so their rows are not computed -- the segment is encoded on the
          * code cut to the columns it sends (at MCS 27: 2 of BG1's 42 extension rows).  Same output bits. */
@@ -591,145 +638,166 @@ int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bo
         }
         ldpc_enc_job e;
         e.code = ce_seg->dev; e.in_off = j.c_off; e.out_off = j.d_off; e.Kb = (int32_t)sg.Kb; e.pad = 0;
-        ej.push_back(e);
+        jl.ej.push_back(e);
       }
       /* the words the block's segments share (tb_tx_settle_word), their tickets and part slots.  (Symbol store: a segment's
        * points are its own: nr_hip_get_E gives every segment whole layer groups) */
       if (scr && fused && !sym)
-        tb_tx_scr_plan(&sj[seg_first], sj.size() - seg_first, &n_tickets, &n_parts);
+        tb_tx_scr_plan(&jl.sj[seg_first], jl.sj.size() - seg_first, &jl.n_tickets, &jl.n_parts);
     }
-    const size_t n_seg = sj.size();
-    const size_t o_tb = 0, o_seg = align_up(tbj.size() * sizeof(tb_tx_tb_job), 16),
-                 o_enc = o_seg + align_up(n_seg * sizeof(tb_tx_seg_job), 16),
-                 o_chk = o_enc + align_up(n_seg * sizeof(ldpc_enc_job), 16),
-                 o_acc = o_chk + align_up(cj.size() * sizeof(tb_crc_chunk_job), 16),
-                 /* CRC accumulators, uploaded as zeros: one per block (unfused path, atomics) / one per chunk (fused) */
-                 o_scr = o_acc + align_up(std::max<size_t>(ntb, cj.size()) * sizeof(uint32_t), 16),
-                 o_tk = o_scr + align_up(pj.size() * sizeof(tb_scr_tb_job) + qj.size() * sizeof(tb_sym_tb_job), 16), /* tickets: zeros, left zero */
-                 o_pt = o_tk + align_up((size_t)n_tickets * 4, 16),                /* parts */
-                 jobs_bytes = o_pt + align_up(n_parts * 4, 16);
-    if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_bytes) != 0 || pl.jobs_d.ensure(jobs_bytes) != 0)
-      return -1;
-    memset(c.jobs_h.p + o_acc, 0, o_scr - o_acc);
-    memcpy(c.jobs_h.p + o_scr, pj.data(), pj.size() * sizeof(tb_scr_tb_job));
-    memcpy(c.jobs_h.p + o_scr, qj.data(), qj.size() * sizeof(tb_sym_tb_job)); /* (one of the two is empty) */
-    memset(c.jobs_h.p + o_tk, 0, jobs_bytes - o_tk);
-    memcpy(c.jobs_h.p + o_chk, cj.data(), cj.size() * sizeof(tb_crc_chunk_job));
-    memcpy(c.jobs_h.p + o_tb, tbj.data(), tbj.size() * sizeof(tb_tx_tb_job));
-    memcpy(c.jobs_h.p + o_seg, sj.data(), n_seg * sizeof(tb_tx_seg_job));
-    memcpy(c.jobs_h.p + o_enc, ej.data(), n_seg * sizeof(ldpc_enc_job));
-    if (tb_upload_jobs(c, pl.jobs_d.p, jobs_bytes, s) != 0)
-      return -1;
-    pl.n_seg = n_seg; pl.n_aux = cj.size(); pl.scratch_top = ar.top;
+    pl.n_seg = jl.sj.size(); pl.n_aux = jl.cj.size(); pl.scratch_top = ar.top;
     pl.pay_lo = ex.pay_lo; pl.pay_hi = ex.pay_hi; pl.cod_lo = ex.cod_lo; pl.cod_hi = ex.cod_hi;
     pl.out_dense = ex.cod_sum == ex.cod_hi - ex.cod_lo;
-    {
-      std::vector<uint64_t> off(ntb);
-      std::vector<size_t> len(ntb);
-      for (uint32_t i = 0; i < ntb; i++) {
-        off[i] = tbs[i].coded_off;
-        len[i] = sym ? (size_t)(tbs[i].G / tbs[i].Qm) * 4u : scr ? (size_t)((tbs[i].G + 31u) / 32u) * 4u : (size_t)tbs[i].G;
-      }
-      pl.build_out_runs(off.data(), len.data(), ntb);
-    }
-    pl.o_tb = o_tb; pl.o_seg = o_seg; pl.o_enc = o_enc; pl.o_chk = o_chk; pl.o_acc = o_acc; pl.o_scr = o_scr;
-    pl.max_g = max_g; pl.o_tickets = o_tk; pl.o_parts = o_pt;
+    pl.build_out_runs(ntb, [&](uint32_t i) {
+      return std::pair<size_t, size_t>((size_t)tbs[i].coded_off, tb_tx_out_bytes(tbs[i], scr != nullptr, sym));
+    });
+    pl.max_g = max_g;
     pl.enc_threads = enc_threads; pl.enc_lds = enc_lds;
-    pl.remember(tbs, ntb, salt, scr, scr_n);
+    return 0;
   }
-  if (c.scratch.ensure(pl.scratch_top + 16) != 0) /* (+16: the fused kernel reads whole dwords around a segment's bytes) */
-    return -1;
-  const size_t n_seg = pl.n_seg;
-  const size_t o_tb = pl.o_tb, o_seg = pl.o_seg, o_enc = pl.o_enc, o_chk = pl.o_chk, o_acc = pl.o_acc;
-  const int enc_threads = pl.enc_threads, enc_lds = pl.enc_lds;
-  const uint8_t *payload = b->payload;
-  uint8_t *coded = static_cast<uint8_t *>(b->coded);
-  uint8_t *out_words = nullptr; /* scrambled, three-kernel path: where the packed words go (coded is then the scratch buffer) */
-  if (staged) {
-    const size_t pay_lo = pl.pay_lo, pay_n = pl.pay_hi - pl.pay_lo, cod_lo = pl.cod_lo, cod_n = pl.cod_hi - pl.cod_lo;
-    if (c.io_payload.ensure(pay_n) != 0 || c.io_coded.ensure(cod_n) != 0)
+
+  /* plan, part 2: the job buffer's layout, its upload, and the plan's places in it */
+  int upload_jobs(TbPlan &pl, const TxJobLists &jl)
+  {
+    JobLayout lay;
+    pl.o_tb = lay.add(jl.tbj);
+    pl.o_seg = lay.add(jl.sj);
+    pl.o_enc = lay.add(jl.ej);
+    pl.o_chk = lay.add(jl.cj);
+    /* CRC accumulators, uploaded as zeros: one per block (unfused path, atomics) / one per chunk (fused) */
+    pl.o_acc = lay.zeros(std::max<size_t>(ntb, jl.cj.size()) * sizeof(uint32_t));
+    pl.o_scr = sym ? lay.add(jl.qj) : lay.add(jl.pj); /* (both empty on the fused path) */
+    pl.o_tickets = lay.zeros((size_t)jl.n_tickets * 4); /* zeros, left zero */
+    pl.o_parts = lay.zeros(jl.n_parts * 4);
+    if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(lay.upload_bytes()) != 0 || pl.jobs_d.ensure(lay.device_bytes()) != 0)
       return -1;
-    const uint8_t *pay_src = b->payload + pay_lo;
-    if (!(b->mem & NRLDPC_HIP_MEM_DEVICE) && needs_bounce(pay_src, pay_n)) { /* pageable: bounced (TbCtx::fin_copies) */
-      if (c.payload_h.ensure(pay_n) != 0)
+    lay.write(c.jobs_h.p);
+    return tb_upload_jobs(c, pl.jobs_d.p, lay.upload_bytes(), s);
+  }
+
+  /* a plan for the call's descriptors in `pl` (a cache slot given up for it: invalid until the last line) */
+  int build_plan(TbPlan &pl, const uint64_t salt[3], size_t scr_n)
+  {
+    TxJobLists jl;
+    if (plan_jobs(pl, jl) != 0 || upload_jobs(pl, jl) != 0)
+      return -1;
+    pl.remember(tbs, ntb, salt, scr, scr_n);
+    return 0;
+  }
+
+  /* stage in: v arrives as the caller's arrays; a staged call gets this device's copy of the payload range and room for the
+   * coded range */
+  int stage_in(const TbPlan &pl, TxViews &v)
+  {
+    if (staged) {
+      const size_t pay_lo = pl.pay_lo, pay_n = pl.pay_hi - pl.pay_lo;
+      if (c.io_payload.ensure(pay_n) != 0 || c.io_coded.ensure(pl.cod_hi - pl.cod_lo) != 0)
         return -1;
-      bounce_copy(c.payload_h.p, pay_n, pay_src, pay_n, pay_n, 1);
-      pay_src = c.payload_h.p;
+      const uint8_t *pay_src = b->payload + pay_lo;
+      if (!(b->mem & NRLDPC_HIP_MEM_DEVICE) && needs_bounce(pay_src, pay_n)) { /* pageable: bounced (TbCtx::fin_copies) */
+        if (c.payload_h.ensure(pay_n) != 0)
+          return -1;
+        bounce_copy(c.payload_h.p, pay_n, pay_src, pay_n, pay_n, 1);
+        pay_src = c.payload_h.p;
+      }
+      HIP_TRY(hipMemcpyAsync(c.io_payload.p, pay_src, pay_n, hipMemcpyDefault, s));
+      v.payload = c.io_payload.p - pay_lo;
+      v.coded = c.io_coded.p - pl.cod_lo;
     }
-    HIP_TRY(hipMemcpyAsync(c.io_payload.p, pay_src, pay_n, hipMemcpyDefault, s));
-    payload = c.io_payload.p - pay_lo;
-    coded = c.io_coded.p - cod_lo;
+    if (scr && !fused) {
+      v.out_words = v.coded;
+      v.coded = c.scratch.p;
+    }
+    return 0;
   }
-  if (scr && !fused) {
-    out_words = coded;
-    coded = c.scratch.p; /* the segments' bytes: job out_off = scratch offsets */
-  }
-  const tb_tx_tb_job *d_tb = reinterpret_cast<const tb_tx_tb_job *>(pl.jobs_d.p + o_tb);
-  const tb_tx_seg_job *d_seg = reinterpret_cast<const tb_tx_seg_job *>(pl.jobs_d.p + o_seg);
-  uint32_t *d_acc = reinterpret_cast<uint32_t *>(pl.jobs_d.p + o_acc);
-  TB_DEBUG_STAGE("tx: entry + copies in");
-  HIP_TRY(tb_launch_tx_crc(d_tb, ntb, reinterpret_cast<const tb_crc_chunk_job *>(pl.jobs_d.p + o_chk), (uint32_t)pl.n_aux,
-                           payload, c.scratch.p, d_acc, G().crc_pow_24a_long, G().crc_pow[NR_HIP_CRC16], fused ? 0 : 1, s));
-  const ldpc_enc_job *d_enc = reinterpret_cast<const ldpc_enc_job *>(pl.jobs_d.p + o_enc);
-  if (fused) {
-    /* workgroup size: 256 threads let every CU hold eight segments (a whole 1664-segment slot is resident at once);
-     * a launch that does not even fill the GPU four deep takes 512 and halves the rounds of its long stages */
-    const int fused_threads = n_seg <= (size_t)4 * (size_t)G().n_cus ? 512 : enc_threads;
-    TB_DEBUG_STAGE("tx: TB CRC launch");
-    if (sym)
-      HIP_TRY(tb_launch_tx_fused_sym(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS + TB_TX_FUSED_SYM_LDS, payload,
-                                     coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
-    else if (scr)
-      HIP_TRY(tb_launch_tx_fused_scr(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS + TB_TX_FUSED_SCR_LDS, payload,
-                                     coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.o_tickets),
-                                     reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.o_parts), s));
-    else
-      HIP_TRY(tb_launch_tx_fused(d_seg, d_enc, (uint32_t)n_seg, fused_threads, enc_lds + TB_TX_FUSED_EXTRA_LDS, payload, coded,
-                                 G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
-    TB_DEBUG_STAGE("tx: fused segment launch");
-  } else {
-    HIP_TRY(tb_launch_tx_segment(d_seg, (uint32_t)n_seg, c.scratch.p, G().crc_pow[NR_HIP_CRC24_B], s));
+
+  /* launch: TB CRC, the segments (one fused launch, or segmentation + encoder + rate matching), then packing or mapping */
+  int launch(const TbPlan &pl, const TxViews &v)
+  {
+    const tb_tx_seg_job *d_seg = pl.at<const tb_tx_seg_job>(pl.o_seg);
+    const ldpc_enc_job *d_enc = pl.at<const ldpc_enc_job>(pl.o_enc);
+    uint32_t *d_acc = pl.at<uint32_t>(pl.o_acc);
+    const uint32_t n_seg = (uint32_t)pl.n_seg;
+    TB_DEBUG_STAGE("tx: entry + copies in");
+    HIP_TRY(tb_launch_tx_crc(pl.at<const tb_tx_tb_job>(pl.o_tb), ntb, pl.at<const tb_crc_chunk_job>(pl.o_chk), (uint32_t)pl.n_aux, v.payload,
+                             c.scratch.p, d_acc, G().crc_pow_24a_long, G().crc_pow[NR_HIP_CRC16], fused ? 0 : 1, s));
+    if (fused) {
+      /* workgroup size: 256 threads let every CU hold eight segments (a whole 1664-segment slot is resident at once);
+       * a launch that does not even fill the GPU four deep takes 512 and halves the rounds of its long stages */
+      const int fused_threads = pl.n_seg <= (size_t)4 * (size_t)G().n_cus ? 512 : pl.enc_threads;
+      const int lds = pl.enc_lds + TB_TX_FUSED_EXTRA_LDS;
+      TB_DEBUG_STAGE("tx: TB CRC launch");
+      if (sym)
+        HIP_TRY(tb_launch_tx_fused_sym(d_seg, d_enc, n_seg, fused_threads, lds + TB_TX_FUSED_SYM_LDS, v.payload, v.coded,
+                                       G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
+      else if (scr)
+        HIP_TRY(tb_launch_tx_fused_scr(d_seg, d_enc, n_seg, fused_threads, lds + TB_TX_FUSED_SCR_LDS, v.payload, v.coded,
+                                       G().crc_pow[NR_HIP_CRC24_B], d_acc, pl.at<uint32_t>(pl.o_tickets), pl.at<uint32_t>(pl.o_parts), s));
+      else
+        HIP_TRY(tb_launch_tx_fused(d_seg, d_enc, n_seg, fused_threads, lds, v.payload, v.coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
+      TB_DEBUG_STAGE("tx: fused segment launch");
+      return 0;
+    }
+    HIP_TRY(tb_launch_tx_segment(d_seg, n_seg, c.scratch.p, G().crc_pow[NR_HIP_CRC24_B], s));
     ldpc_enc_args ea;
     memset(&ea, 0, sizeof(ea));
     ea.in = c.scratch.p;
     ea.out = c.scratch.p;
     ea.jobs = d_enc;
-    HIP_TRY(ldpc_launch_enc_jobs(ea, enc_threads, enc_lds, (uint32_t)n_seg, s));
-    HIP_TRY(tb_launch_tx_ratematch(d_seg, (uint32_t)n_seg, c.scratch.p, coded, s));
+    HIP_TRY(ldpc_launch_enc_jobs(ea, pl.enc_threads, pl.enc_lds, n_seg, s));
+    HIP_TRY(tb_launch_tx_ratematch(d_seg, n_seg, c.scratch.p, v.coded, s));
     TB_DEBUG_STAGE("tx: segment + rate matching launches");
+    if (sym) {
+      HIP_TRY(nr_launch_scramble_map_tb(pl.at<const tb_sym_tb_job>(pl.o_scr), ntb, pl.max_g, c.scratch.p, v.out_words, s));
+      TB_DEBUG_STAGE("tx: scrambled, mapped, layer-mapped store");
+    } else if (scr) {
+      HIP_TRY(nr_launch_scramble_bits_tb(pl.at<const tb_scr_tb_job>(pl.o_scr), ntb, pl.max_g, c.scratch.p, v.out_words, s));
+      TB_DEBUG_STAGE("tx: packed scrambled store");
+    }
+    return 0;
   }
-  if (sym && !fused) {
-    HIP_TRY(nr_launch_scramble_map_tb(reinterpret_cast<const tb_sym_tb_job *>(pl.jobs_d.p + pl.o_scr), ntb, pl.max_g, c.scratch.p,
-                                      out_words, s));
-    TB_DEBUG_STAGE("tx: scrambled, mapped, layer-mapped store");
-  } else if (scr && !fused) {
-    HIP_TRY(nr_launch_scramble_bits_tb(reinterpret_cast<const tb_scr_tb_job *>(pl.jobs_d.p + pl.o_scr), ntb, pl.max_g, c.scratch.p,
-                                       out_words, s));
-    TB_DEBUG_STAGE("tx: packed scrambled store");
-  }
-  if (staged) {
-    uint8_t *hc = static_cast<uint8_t *>(b->coded);
-    const size_t cod_lo = pl.cod_lo, cod_n = pl.cod_hi - pl.cod_lo;
-    uint8_t *out = hc; /* where the copies go: the caller's array, or (pageable array) this thread's page-locked mirror of it */
-    if (!(b->mem & NRLDPC_HIP_MEM_DEVICE) && needs_bounce(hc + cod_lo, cod_n)) {
-      if (c.coded_h.ensure(cod_n) != 0)
+
+  /* stage out: the coded range back -- to the caller's array, or (pageable array) to this thread's page-locked mirror of it,
+   * which tb_tx_finish hands over */
+  int stage_out(const TbPlan &pl, const TxViews &)
+  {
+    uint8_t *hc = static_cast<uint8_t *>(b->coded), *out = hc;
+    const size_t cod_lo = pl.cod_lo, cod_hi = pl.cod_hi;
+    if (!(b->mem & NRLDPC_HIP_MEM_DEVICE) && needs_bounce(hc + cod_lo, cod_hi - cod_lo)) {
+      if (c.coded_h.ensure(cod_hi - cod_lo) != 0)
         return -1;
       out = c.coded_h.p - cod_lo;
-      if (pl.out_dense) {
-        c.fin_copies.push_back(TbCtx::FinCopy{hc + cod_lo, c.coded_h.p, cod_n, 1, cod_n, cod_n, nullptr}); /* (one contiguous block: cut over the helpers) */
-      } else {
-        for (const TbPlan::OutRun &r : pl.out_runs)
-          c.fin_copies.push_back(TbCtx::FinCopy{hc + r.first, out + r.first, r.width, r.rows, r.pitch, r.pitch, nullptr});
-      }
+      tb_fin_outputs(c, pl, pl.out_dense, hc, out, cod_lo, cod_hi);
     }
-    if (pl.out_dense) {
-      HIP_TRY(hipMemcpyAsync(out + cod_lo, c.io_coded.p, cod_n, hipMemcpyDefault, s));
-    } else {
-      for (const TbPlan::OutRun &r : pl.out_runs)
-        HIP_TRY(hipMemcpy2DAsync(out + r.first, r.pitch, c.io_coded.p + (r.first - cod_lo), r.pitch, r.width, r.rows, hipMemcpyDefault, s));
-    }
+    return tb_copy_outputs(pl, pl.out_dense, out, c.io_coded.p, cod_lo, cod_hi, s);
   }
-  return 0;
+};
+
+/* the hit / miss branch around the steps of TbTxCall */
+int tb_tx_enqueue(const nrLDPC_hip_tb_batch_t *b, uint32_t tb0, uint32_t ntb, bool staged, hipStream_t s_direct,
+                  const nrLDPC_hip_tb_scr_t *scr = nullptr, bool sym = false)
+{
+  hipStream_t s;
+  if (tb_begin(s, s_direct, staged) != 0)
+    return -1;
+  if (ntb == 0)
+    return 0;
+  TbCtx &c = tls_tb;
+  TbTxCall call{b, tb0, ntb, staged, scr, sym, s, c};
+  /* bit 2: scrambled (its key also holds the scr bytes: a scrambled and an unscrambled plan never match); bit 3: symbols (never
+   * a packed-word plan, nor the reverse) */
+  const uint64_t salt[3] = {(call.fused ? 1u : 0u) | (tb_trunc_enabled() ? 2u : 0u) | (scr ? 4u : 0u) | (sym ? 8u : 0u), 0, 0};
+  const size_t scr_n = scr ? (size_t)ntb * sizeof(nrLDPC_hip_tb_scr_t) : 0;
+  TbPlan *hit = c.tx.find(call.tbs, ntb, salt, scr, scr_n);
+  TbPlan &pl = hit ? *hit : c.tx.victim();
+  if (!hit && call.build_plan(pl, salt, scr_n) != 0)
+    return -1;
+  if (c.scratch.ensure(pl.scratch_top + 16) != 0) /* (+16: the fused kernel reads whole dwords around a segment's bytes) */
+    return -1;
+  TxViews v{b->payload, static_cast<uint8_t *>(b->coded), nullptr};
+  if (call.stage_in(pl, v) != 0 || call.launch(pl, v) != 0)
+    return -1;
+  return staged ? call.stage_out(pl, v) : 0;
 }
 
 int tb_tx_finish(const nrLDPC_hip_tb_batch_t *b, uint32_t ntb)
@@ -1193,15 +1261,7 @@ struct TbRxCall {
     pl.pay_lo = ex.pay_lo; pl.pay_hi = ex.pay_hi; pl.cod_lo = ex.cod_lo; pl.cod_hi = ex.cod_hi;
     pl.harq_lo = harq_lib ? 0 : ex.harq_lo; pl.harq_hi = harq_lib ? 0 : ex.harq_hi;
     pl.out_dense = ex.pay_sum == ex.pay_hi - ex.pay_lo;
-    {
-      std::vector<uint64_t> off(ntb);
-      std::vector<size_t> len(ntb);
-      for (uint32_t i = 0; i < ntb; i++) {
-        off[i] = tbs[i].payload_off;
-        len[i] = tbs[i].A / 8;
-      }
-      pl.build_out_runs(off.data(), len.data(), ntb);
-    }
+    pl.build_out_runs(ntb, [&](uint32_t i) { return std::pair<size_t, size_t>((size_t)tbs[i].payload_off, tbs[i].A / 8); });
     pl.harq_runs.swap(runs);
     pl.n_legacy_seg = jl.sj_legacy.size(); pl.n_legacy_tb = n_legacy_tb; pl.any_fused = any_fused;
     pl.rx_lds_elems = rx_lds_elems;
@@ -1217,33 +1277,20 @@ struct TbRxCall {
     std::vector<ldpc_dec_job> single_jobs(jl.single.size());
     for (size_t q = 0; q < jl.single.size(); q++)
       single_jobs[q] = jl.single[q].dj;
-    const size_t n_seg = jl.sj.size();
-    const size_t o_tb = 0, o_seg = align_up(jl.tbj.size() * sizeof(tb_rx_tb_job), 16),
-                 o_leg = o_seg + align_up(n_seg * sizeof(tb_rx_seg_job), 16),
-                 o_single = o_leg + align_up(jl.sj_legacy.size() * sizeof(tb_rx_seg_job), 16),
-                 o_mj0 = o_single + align_up(single_jobs.size() * sizeof(ldpc_dec_job), 16),
-                 o_mg0 = o_mj0 + align_up(jl.mjobs[0].size() * sizeof(ldpc_dec_job), 16),
-                 o_mj1 = o_mg0 + align_up(jl.mgrp[0].size() * sizeof(ldpc_dec_mgroup), 16),
-                 o_mg1 = o_mj1 + align_up(jl.mjobs[1].size() * sizeof(ldpc_dec_job), 16),
-                 o_acc = o_mg1 + align_up(jl.mgrp[1].size() * sizeof(ldpc_dec_mgroup), 16), /* per TB: CRC accumulators, abort
-                                                                                            flags, finished-segment counters:
-                                                                                            uploaded as zeros, left zero */
-                 o_slots = o_acc + align_up((size_t)ntb * 4 * sizeof(uint32_t), 16), /* (+ per TB: generation) */
-                 jobs_bytes = o_slots + align_up(n_seg * sizeof(uint64_t), 16), /* per segment: the fused kernel's slots */
-                 o_iter = jobs_bytes; /* n_iter lives behind the uploaded part in the same device buffer */
-    if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(jobs_bytes) != 0 ||
-        pl.jobs_d.ensure(o_iter + n_seg * sizeof(int32_t)) != 0)
+    JobLayout lay;
+    pl.o_tb = lay.add(jl.tbj);
+    pl.o_seg = lay.add(jl.sj);
+    pl.legacy_off = lay.add(jl.sj_legacy);
+    const size_t o_single = lay.add(single_jobs);
+    const size_t o_mj0 = lay.add(jl.mjobs[0]), o_mg0 = lay.add(jl.mgrp[0]), o_mj1 = lay.add(jl.mjobs[1]), o_mg1 = lay.add(jl.mgrp[1]);
+    /* per TB: CRC accumulators, abort flags, finished-segment counters (+ generation): uploaded as zeros, left zero */
+    pl.o_acc = lay.zeros((size_t)ntb * 4 * sizeof(uint32_t));
+    pl.o_slots = lay.zeros(jl.sj.size() * sizeof(uint64_t)); /* per segment: the fused kernel's slots */
+    pl.o_iter = lay.reserve(jl.sj.size() * sizeof(int32_t)); /* n_iter lives behind the uploaded part in the same device buffer */
+    if (tb_wait_upload(c) != 0 || c.jobs_h.ensure(lay.upload_bytes()) != 0 || pl.jobs_d.ensure(lay.device_bytes()) != 0)
       return -1;
-    memset(c.jobs_h.p + o_acc, 0, jobs_bytes - o_acc);
-    memcpy(c.jobs_h.p + o_tb, jl.tbj.data(), jl.tbj.size() * sizeof(tb_rx_tb_job));
-    memcpy(c.jobs_h.p + o_seg, jl.sj.data(), n_seg * sizeof(tb_rx_seg_job));
-    memcpy(c.jobs_h.p + o_leg, jl.sj_legacy.data(), jl.sj_legacy.size() * sizeof(tb_rx_seg_job));
-    memcpy(c.jobs_h.p + o_single, single_jobs.data(), single_jobs.size() * sizeof(ldpc_dec_job));
-    memcpy(c.jobs_h.p + o_mj0, jl.mjobs[0].data(), jl.mjobs[0].size() * sizeof(ldpc_dec_job));
-    memcpy(c.jobs_h.p + o_mg0, jl.mgrp[0].data(), jl.mgrp[0].size() * sizeof(ldpc_dec_mgroup));
-    memcpy(c.jobs_h.p + o_mj1, jl.mjobs[1].data(), jl.mjobs[1].size() * sizeof(ldpc_dec_job));
-    memcpy(c.jobs_h.p + o_mg1, jl.mgrp[1].data(), jl.mgrp[1].size() * sizeof(ldpc_dec_mgroup));
-    if (tb_upload_jobs(c, pl.jobs_d.p, jobs_bytes, s) != 0)
+    lay.write(c.jobs_h.p);
+    if (tb_upload_jobs(c, pl.jobs_d.p, lay.upload_bytes(), s) != 0)
       return -1;
     for (TbPlan::DecLaunch &dl : dec)
       dl.jobs_off += o_single;
@@ -1252,7 +1299,6 @@ struct TbRxCall {
     if (!jl.mgrp[1].empty())
       dec.push_back(TbPlan::DecLaunch{3, o_mj1, o_mg1, (uint32_t)jl.mgrp[1].size(), jl.m_threads[1], jl.m_lds[1], false});
     pl.dec.swap(dec);
-    pl.o_tb = o_tb; pl.o_seg = o_seg; pl.o_iter = o_iter; pl.o_acc = o_acc; pl.o_slots = o_slots; pl.legacy_off = o_leg;
     return 0;
   }
 
@@ -1397,10 +1443,9 @@ struct TbRxCall {
   int launch(const TbPlan &pl, const RxViews &v)
   {
     auto [llr, harq, payload, ack, iter_max, harq_bounce, harq_mirror] = v;
-    int32_t *d_iter = reinterpret_cast<int32_t *>(pl.jobs_d.p + pl.o_iter);
-    const tb_rx_seg_job *d_seg = reinterpret_cast<const tb_rx_seg_job *>(pl.jobs_d.p + pl.o_seg);
-    const tb_rx_seg_job *d_leg = reinterpret_cast<const tb_rx_seg_job *>(pl.jobs_d.p + pl.legacy_off);
-    const tb_rx_tb_job *d_tb = reinterpret_cast<const tb_rx_tb_job *>(pl.jobs_d.p + pl.o_tb);
+    int32_t *d_iter = pl.at<int32_t>(pl.o_iter);
+    const tb_rx_seg_job *d_seg = pl.at<const tb_rx_seg_job>(pl.o_seg), *d_leg = pl.at<const tb_rx_seg_job>(pl.legacy_off);
+    const tb_rx_tb_job *d_tb = pl.at<const tb_rx_tb_job>(pl.o_tb);
     if (c.timing) {
       for (hipEvent_t &e : c.tev)
         if (!e)
@@ -1424,13 +1469,13 @@ struct TbRxCall {
     for (int k = 0; k < 4; k++)
       da.crc_pow_tbl[k] = G().crc_pow[k];
     da.crc_pow_tbl[NR_HIP_CRC24_A] = G().crc_pow_24a_long;
-    uint32_t *d_acc = reinterpret_cast<uint32_t *>(pl.jobs_d.p + pl.o_acc);
+    uint32_t *d_acc = pl.at<uint32_t>(pl.o_acc);
     int *d_abort = reinterpret_cast<int *>(d_acc) + ntb; /* zero on entry, left zero by the verdict */
     da.tb_abort = d_abort;
     tb_rx_fused_args fx;
     fx.segs = d_seg; fx.tbs = d_tb; fx.llr = llr; fx.harq = harq; fx.payload = payload; fx.ack = ack; fx.iter_max = iter_max;
     fx.done = d_abort + ntb; fx.gen = reinterpret_cast<uint32_t *>(d_abort + 2 * ntb);
-    fx.slots = reinterpret_cast<unsigned long long *>(pl.jobs_d.p + pl.o_slots); fx.pow24a = G().crc_pow_24a_long;
+    fx.slots = pl.at<unsigned long long>(pl.o_slots); fx.pow24a = G().crc_pow_24a_long;
     fx.stagger_ticks = fx.stagger_cus = fx.stagger_slots = 0;
     fx.lrow_off = 0;
     fx.mute = 0;
@@ -1464,8 +1509,8 @@ struct TbRxCall {
       const TbPlan::DecLaunch &dl = pl.dec[k];
       const size_t lane = n_side ? k % (n_side + 1) : 0;
       hipStream_t s = lane ? c.side[lane - 1] : s_call; /* (shadows the call's stream inside the loop) */
-      da.jobs = reinterpret_cast<const ldpc_dec_job *>(pl.jobs_d.p + dl.jobs_off);
-      da.mgroups = reinterpret_cast<const ldpc_dec_mgroup *>(pl.jobs_d.p + dl.grp_off);
+      da.jobs = pl.at<const ldpc_dec_job>(dl.jobs_off);
+      da.mgroups = pl.at<const ldpc_dec_mgroup>(dl.grp_off);
       if (dl.kind == 0 && dl.fused) {
         /* more than one workgroup per CU in the first round: staggered start (tb_chain.h).  NRLDPC_HIP_TB_STAGGER_US = the
          * offset between the two workgroups of a CU (k workgroups: 2 / k of it each).  Default 0 = off: measured level to
@@ -1547,13 +1592,9 @@ struct TbRxCall {
      * shares the staging area: with payload offsets that do not grow with the block index a later piece's range can span
      * blocks an earlier piece has already delivered, so there only the blocks themselves are copied, run by run */
     const bool several_pieces = st && st->call_ntb != ntb;
-    if (pl.out_dense || (pay_dst != b->payload && !several_pieces)) {
-      HIP_TRY(hipMemcpyAsync(pay_dst + pl.pay_lo, c.io_payload.p, pl.pay_hi - pl.pay_lo, hipMemcpyDefault, s));
-    } else {
-      for (const TbPlan::OutRun &r : pl.out_runs)
-        HIP_TRY(hipMemcpy2DAsync(pay_dst + r.first, r.pitch, c.io_payload.p + (r.first - pl.pay_lo), r.pitch, r.width, r.rows,
-                                 hipMemcpyDefault, s));
-    }
+    const bool whole_range = pl.out_dense || (pay_dst != b->payload && !several_pieces);
+    if (tb_copy_outputs(pl, whole_range, pay_dst, c.io_payload.p, pl.pay_lo, pl.pay_hi, s) != 0)
+      return -1;
     if (harq_staged)
       for (const TbPlan::HarqRun &r : pl.harq_runs) {
         /* a bounced run comes down in pieces of ~8 MB with an event behind each: tb_rx_finish hands piece k over to the

@@ -312,6 +312,45 @@ def test_repeated_descriptors_reuse_the_plan(hip):
             row += segs[i]
 
 
+@pytest.mark.parametrize("pinned", [False, True])
+def test_dlsch_encode_host_gapped_blocks(hip, pinned):
+    """The staged copy back of a host-buffer encode whose outputs do not tile their range: three equal blocks at one pitch (one
+    strided copy of three rows), a fourth 100 bytes behind them (a run of its own), payloads with gaps too; pageable numpy arrays
+    (bounced by the CPU in the finish call) and page-locked ones.  Every block equals the oracle chain's, every byte outside
+    the blocks keeps its sentinel -- on a plan miss, on the hit that follows, and on the miss into a new slot after one rv changed."""
+    import ctypes as C
+    m = hip.ldpc
+    L = m._tb_lib()
+    rng = np.random.default_rng(1203)
+    # (A = 4008 for the two-segment block: the smallest size from 4000 on whose segments are whole bytes; 4000 itself is refused)
+    small = dict(A=valid_tbs(1000, 2), G=2400, BG=2, Qm=2, Nl=1, rv=0, tbslbrm=0)
+    big = dict(A=valid_tbs(4000, 2), G=12000, BG=2, Qm=4, Nl=1, rv=0, tbslbrm=0)
+    assert (small["A"], big["A"]) == (1000, 4008) and O.segmentation(None, O.len_with_crc(1, big["A"]), 2)["C"] == 2
+    tbs = [dict(small), dict(small), dict(small), dict(big)]
+    pitch = small["G"] + 48
+    # (the page-locked run's offsets are shifted: its descriptors are new to the plan cache, so its first call is a miss as well)
+    co = [16 * pinned + x for x in (0, pitch, 2 * pitch, 2 * pitch + small["G"] + 100)]
+    po = [3 + pinned + x for x in (0, 125 + 7, 2 * 125 + 8, 3 * 125 + 38)]
+    n_pay, n_cod = po[3] + big["A"] // 8 + 9, co[3] + big["G"] + 21
+    keep = [m.PinnedArray(n_pay, np.uint8), m.PinnedArray(n_cod, np.uint8)] if pinned else None
+    pay, coded = (keep[0].a, keep[1].a) if pinned else (np.zeros(n_pay, np.uint8), np.zeros(n_cod, np.uint8))
+    for call, rv0 in enumerate((0, 0, 2)):           # a miss, a hit (new payload), a miss into a new slot
+        tbs[0]["rv"] = rv0
+        pay[:] = rng.integers(0, 256, n_pay, dtype=np.uint8)
+        coded[:] = 0xA5
+        arr = m._tb_array(tbs, po, co, None)
+        b = m.nrLDPC_hip_tb_batch_t(n_tb=len(tbs), tb=arr, payload=pay.ctypes.data, coded=coded.ctypes.data, harq=None, harq_stride=0,
+                                    ack=None, iter_max=None, mem=m.MEM_HOST, stream=None)
+        assert L.nrLDPC_hip_dlsch_encode(C.byref(b)) == 0, m.last_error()
+        outside = np.ones(n_cod, bool)
+        for i, t in enumerate(tbs):
+            ref = O.dlsch_encode(t, pay[po[i]:po[i] + t["A"] // 8])
+            assert np.array_equal(coded[co[i]:co[i] + t["G"]], ref), (call, i)
+            outside[co[i]:co[i] + t["G"]] = False
+        assert outside.sum() == 16 * pinned + 48 + 48 + 100 + 21 and (coded[outside] == 0xA5).all(), call
+    del keep
+
+
 def test_small_transport_blocks_share_workgroups(hip):
     """A batch with enough segments to fill the GPU: the small single-segment transport blocks of the same code, cap and
     CRC length are decoded several to a workgroup (tb_api.inc.cpp groups them, ldpc_dec_fast_mblock.h decodes a group --
