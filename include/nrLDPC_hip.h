@@ -569,7 +569,8 @@ int32_t nrLDPC_hip_pusch_chest_segments(const nrLDPC_hip_pusch_alloc_t *alloc, c
  * Deviations from the reference: every data RE of a FULL symbol is mulhrs (the reference's scalar tail, the
  * last len % 4 REs of each piece of a symbol, omits the final shift, :428-435, :460-467), and the pattern is decided by i, never
  * by the grid subcarrier (allowed_xlsch_re_in_dmrs_symbol takes diff = fft_size at the first subcarrier, dmrs_nr.c:45-48).
- * PTRS, precoding matrices other than unit, interleaved VRB mapping and CSI-RS / SSB collisions are not built.
+ * PTRS, interleaved VRB mapping and CSI-RS / SSB collisions are not built; precoding matrices other than unit: the precoded call
+ * below.
  * mem = HOST: synchronous; stages the span of the layer planes the descriptors reach, works on a bounce of the span of the grid
  * from the lowest to the highest c16 written, and copies only the write set back.  mem = DEVICE enqueues on `stream` (one launch
  * per pattern present); the descriptors go through the calling thread's page-locked job area.
@@ -638,6 +639,56 @@ int32_t nrLDPC_hip_pdsch_map_host(const int16_t *layers, const nrLDPC_hip_pdsch_
 int32_t nrLDPC_hip_pdsch_dmrs_host(uint32_t c_init, uint32_t dmrs_offset, uint32_t n, int16_t *out);
 int32_t nrLDPC_hip_pdsch_map_segments(const nrLDPC_hip_pdsch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_pdsch_map_seg_t *seg_out, uint32_t cap,
                                       uint32_t *n_seg_out);
+/* ---------------------------------------------------------------------------------------------------
+ * PDSCH resource mapping with precoding: the same mapping, then layers to antenna ports through per-PRG matrices -- both branches
+ * of the precoding loop of nr_generate_pdsch (nr_dlsch.c:486-589) with nr_layer_precoder_simd (openair1/PHY/MODULATION/
+ * nr_modulation.c:720-821).  pdsch_resource_mapping stays as it is; this call takes the same descriptors plus, parallel to them,
+ * one nrLDPC_hip_pdsch_prg_t each: prg_size (rel15->precodingAndBeamforming.prg_size; 0 = unit precoding of the whole descriptor)
+ * and the range pmi_off, pmi_count of the descriptor's PMIs in the flat list pmi_list[n_pmi] (prgs_list[].pm_idx, one per PRG), and
+ * the precoding-matrix table pm[n_pm] (gNB_config.pmi_list.pmi_pdu; nfapi_nr_pm_pdu_t with room for 8 ports), found by pm_idx, in
+ * any order.  Let m_l[i] be what pdsch_resource_mapping yields for layer l at allocation subcarrier i.  RE i lies in RB i / 12, its
+ * pmi = prg_size > 0 ? pmi_list[pmi_off + (i / 12) / prg_size] : 0.  Antenna a < n_tx receives
+ *   pmi == 0   m_a[i] for a < Nl, otherwise 0: a copy, bit for bit the unit call's result.  Unit and other PRGs may be mixed.
+ *   pmi != 0   the sum over l = 0 .. Nl - 1, in this order, from 0, accumulated with adds_epi16 (saturating per component), of
+ *              x w >> 15 with x = m_l[i], w = weights[l][a] of the matrix whose pm_idx is pmi:
+ *                re = low16((x.r w.r + x.i nwi) as wrapping int32 >> 15), nwi = -w.i cast to int16 (-(-32768) stays -32768)
+ *                im = low16((x.r w.i + x.i w.r) as wrapping int32 >> 15); the shifted value is cut to 16 bits, not saturated.
+ * Deviation from the reference: it sends the one RB step of a symbol that reaches or crosses fft_size through
+ * nr_layer_precoder_cm (c16maddShift, tools_defs.h:226-231), which accumulates with wrap-around and negates w.i in int32; here
+ * every RE is the SIMD definition above.  The two agree whenever no accumulation leaves int16 and no w.i is -32768.
+ * Read and written as pdsch_resource_mapping: exactly the 12 rb_size c16 per (descriptor, antenna < n_tx), overwritten, wrapping
+ * at fft_size.  The matrices and PMI lists are host memory in both mem modes: the PMIs are resolved against the table on the host
+ * and travel, with the matrices in use, in the descriptors' one upload through the calling thread's page-locked job area.
+ * Refused before anything is enqueued or written: everything pdsch_resource_mapping refuses; a NULL prg; with a PMI that is not
+ * 0: n_tx < 2, a NULL table, a PMI that no table entry carries, numLayers != Nl, num_ant_ports < n_tx or > 8; pm_idx == 0 in the
+ * table or a pm_idx twice in it; a PMI range shorter than ceil(rb_size / prg_size) or reaching outside pmi_list (a NULL pmi_list
+ * has no entries).  With prg_size = 0 the range is not looked at.
+ * pdsch_precode_host: one descriptor and antenna `ant` < n_tx on the CPU from the same header, no GPU; tx_off and lay_off apply
+ * (the caller adds ant tx_ant_stride to tx_off).  0 / -1.
+ * pdsch_precode_segments (host only, no GPU): pdsch_map_segments' descriptors for each allocation plus, per descriptor, the
+ * allocation's alloc_prg[i]: every symbol of an allocation shares the range.  Refused: what pdsch_map_segments refuses (under its
+ * name), a range shorter than ceil(rb_size / prg_size) or reaching beyond n_pmi, more than cap descriptors. */
+typedef struct nrLDPC_hip_pm_pdu {
+  uint16_t pm_idx;           /* 1..65535; 0 is the unit matrix and has no entry */
+  uint16_t numLayers;
+  uint16_t num_ant_ports;    /* >= n_tx, <= 8 */
+  uint16_t pad;
+  int16_t weights[4][8][2];  /* [layer][antenna port] (Re, Im), Q15 */
+} nrLDPC_hip_pm_pdu_t;
+typedef struct nrLDPC_hip_pdsch_prg {
+  uint32_t prg_size;         /* RBs per PRG; 0: unit precoding */
+  uint32_t pmi_off;          /* the descriptor's first PMI in pmi_list */
+  uint32_t pmi_count;        /* >= ceil(rb_size / prg_size) */
+} nrLDPC_hip_pdsch_prg_t;
+int32_t nrLDPC_hip_pdsch_resource_mapping_precoded(const int16_t *layers, int16_t *txdataF, uint64_t tx_ant_stride, uint32_t n_tx,
+                                                   const nrLDPC_hip_pdsch_map_seg_t *seg, const nrLDPC_hip_pdsch_prg_t *prg, uint32_t n_seg,
+                                                   const uint16_t *pmi_list, uint32_t n_pmi, const nrLDPC_hip_pm_pdu_t *pm, uint32_t n_pm, int32_t mem,
+                                                   void *stream);
+int32_t nrLDPC_hip_pdsch_precode_host(const int16_t *layers, const nrLDPC_hip_pdsch_map_seg_t *seg, const nrLDPC_hip_pdsch_prg_t *prg,
+                                      const uint16_t *pmi_list, uint32_t n_pmi, const nrLDPC_hip_pm_pdu_t *pm, uint32_t n_pm, uint32_t n_tx, uint32_t ant,
+                                      int16_t *txdataF);
+int32_t nrLDPC_hip_pdsch_precode_segments(const nrLDPC_hip_pdsch_alloc_t *alloc, const nrLDPC_hip_pdsch_prg_t *alloc_prg, uint32_t n_alloc, uint32_t n_pmi,
+                                          nrLDPC_hip_pdsch_map_seg_t *seg_out, nrLDPC_hip_pdsch_prg_t *prg_out, uint32_t cap, uint32_t *n_seg_out);
 /* ---------------------------------------------------------------------------------------------------
  * The reference's OFFLOAD plugin slot (`ldpc_interface_offload`, loaded with the suffix "_t2": nr_init.c:138-139).  Same
  * signatures as LDPCdecoder / LDPCencoder, the semantics of nrLDPC_decoder/nrLDPC_decoder_offload.c:1036-1140: one

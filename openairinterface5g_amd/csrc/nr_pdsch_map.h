@@ -20,6 +20,14 @@
  * Two defects of the reference are not reproduced: the scalar tail of the FULL loop that omits the final
  * shift (:428-435, :460-467), and allowed_xlsch_re_in_dmrs_symbol's diff = fft_size at the allocation's first subcarrier
  * (dmrs_nr.c:45-48).  Here the pattern is decided by i, never by the grid subcarrier.
+ *
+ * Precoding (nr_dlsch.c:486-589): antenna a of an RE whose PRG has pmi = 0 takes layer a's value, or 0 behind the layers, as a
+ * copy; with pmi != 0 it is the sum over the layers l = 0 .. Nl - 1 of m_l w[l][a] as nr_layer_precoder_simd computes it
+ * (nr_modulation.c:785-811): per term the two madd_epi16 sums as wrapping int32, >> 15, the low 16 bits; w.i negated as an int16
+ * (-(-32768) stays -32768); the terms accumulated from 0 with adds_epi16, which saturates (nr_pdm_prec_term, nr_pdm_adds16,
+ * nr_pdm_antenna).  The reference's nr_layer_precoder_cm for the RB step at the end of the symbol is not reproduced (DESIGN
+ * section 5).  The pilots of all layers come out of one run of Gold bits: it starts at the pilot number that the port with the
+ * latest pilots (nr_pdm_last_pmask) has reached, which is at most 2 below every other port's.
  */
 #ifndef NR_PDSCH_MAP_H
 #define NR_PDSCH_MAP_H
@@ -135,6 +143,45 @@ NR_PDM_HD uint32_t nr_pdm_re(const nr_pdm_sym *s, const uint32_t *lay, uint32_t 
   }
   return 0u;
 }
+/* the pilot mask of the ports with the largest delta: nr_pdm_count of it is the smallest among all ports at every i */
+NR_PDM_HD uint32_t nr_pdm_last_pmask(uint32_t pattern)
+{
+  uint32_t pm = 0, dm = 0;
+  if (pattern != NR_PDM_FULL)
+    nr_pdm_masks(pattern, 1u, pattern == NR_PDM_DMRS2 ? 4u : 1u, &pm, &dm);
+  return pm;
+}
+
+/* ---- precoding: layers to one antenna ---- */
+/* one term of nr_layer_precoder_simd: x w >> 15, the sums wrapping in 32 bits, the shifted value cut to 16 bits */
+NR_PDM_HD uint32_t nr_pdm_prec_term(uint32_t x, uint32_t w)
+{
+  const int32_t xr = (int16_t)(x & 0xffffu), xi = (int16_t)(x >> 16), wr = (int16_t)(w & 0xffffu), wi = (int16_t)(w >> 16);
+  const int32_t nwi = (int16_t)(-wi); /* c16conj: the negation is cast back to int16 */
+  const uint32_t re = (uint32_t)(xr * wr) + (uint32_t)(xi * nwi), im = (uint32_t)(xr * wi) + (uint32_t)(xi * wr);
+  return nr_pdm_pack((int32_t)re >> 15, (int32_t)im >> 15);
+}
+NR_PDM_HD int32_t nr_pdm_sat16(int32_t v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }
+/* simde_mm_adds_epi16 per component */
+NR_PDM_HD uint32_t nr_pdm_adds16(uint32_t y, uint32_t t)
+{
+  return nr_pdm_pack(nr_pdm_sat16((int16_t)(y & 0xffffu) + (int16_t)(t & 0xffffu)), nr_pdm_sat16((int16_t)(y >> 16) + (int16_t)(t >> 16)));
+}
+/* antenna ant's value of one RE from the mapped values m[l] of its layers l < Nl (the others are not read).  pmi == 0: the copy of
+ * layer ant, 0 behind the layers; otherwise w[l] = weights[l][ant] of the PRG's matrix */
+NR_PDM_HD uint32_t nr_pdm_antenna(const uint32_t *m, const uint32_t *w, uint32_t Nl, uint32_t ant, uint32_t pmi)
+{
+  uint32_t y = 0u;
+  for (uint32_t l = 0; l < NR_PDM_MAX_LAYERS; l++)
+    if (l < Nl) {
+      if (pmi)
+        y = nr_pdm_adds16(y, nr_pdm_prec_term(m[l], w[l]));
+      else if (l == ant)
+        y = m[l];
+    }
+  return y;
+}
+
 /* (k0 + off) % N for k0 < N, off < N */
 NR_PDM_HD uint32_t nr_pdm_wrap(uint32_t k0, uint32_t off, uint32_t N) { return k0 + off >= N ? k0 + off - N : k0 + off; }
 #endif

@@ -87,10 +87,12 @@ struct DeviceCall {
     return 0;
   }
   /* the tables to the device, on the stream and ahead of the launches: their device copy, nullptr + error when that fails */
-  template <typename T> uint8_t *upload(const T &tables)
+  template <typename T> uint8_t *upload(const T &tables) { return upload(tables, tables.bytes()); }
+  /* a call with more than two arrays lays them out with JobLayout (job_layout.h): still one upload */
+  uint8_t *upload(const JobLayout &lay) { return upload(lay, lay.upload_bytes()); }
+  template <typename T> uint8_t *upload(const T &tables, size_t bytes)
   {
     TbCtx &c = tls_tb;
-    const size_t bytes = tables.bytes();
     hipStream_t on;
     if (tb_begin(on, s, false) != 0 || tb_wait_upload(c) != 0 || c.jobs_h.ensure(bytes) != 0 || c.jobs_d.ensure(bytes) != 0)
       return nullptr;

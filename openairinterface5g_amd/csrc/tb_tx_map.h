@@ -30,7 +30,22 @@ typedef struct tx_map_wg {
   uint32_t w0, x1, x2, pad;
 } tx_map_wg;
 
+/* precoding (nr_tx_precode_kernel), per descriptor: RB b of the allocation belongs to PRG b / prg_size (never 0 here: unit
+ * precoding of a whole descriptor is one PRG as wide as the allocation), whose matrix is pmx[pmx_off + PRG]: 0 = unit, otherwise 1 +
+ * the index into the call's matrices -- resolved on the host, nothing is searched on the device */
+typedef struct tx_map_prg {
+  uint32_t prg_size, pmx_off;
+} tx_map_prg;
+/* one precoding matrix: the weight of layer l for antenna a as a c16 word */
+typedef struct tx_map_pm {
+  uint32_t w[4][8];
+} tx_map_pm;
+
 /* n_wg workgroups of one pattern (NR_PDM_*); wgs[n_wg] and jobs[] in device memory; lay / tx 4-byte aligned */
 hipError_t nr_launch_tx_map(uint32_t pattern, const tx_map_wg *wgs, uint32_t n_wg, const tx_map_job *jobs, const uint32_t *lay, uint32_t *tx,
                             uint64_t tx_ant_stride, hipStream_t s);
+/* the same with precoding: prgs[] parallel to jobs[]; a workgroup's Gold registers stand at the word of the pilot number that
+ * nr_pdm_last_pmask has reached at its first RE, for every antenna */
+hipError_t nr_launch_tx_precode(uint32_t pattern, const tx_map_wg *wgs, uint32_t n_wg, const tx_map_job *jobs, const tx_map_prg *prgs, const uint16_t *pmx,
+                                const tx_map_pm *mats, const uint32_t *lay, uint32_t *tx, uint64_t tx_ant_stride, hipStream_t s);
 #endif

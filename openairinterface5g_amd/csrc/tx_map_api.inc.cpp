@@ -84,16 +84,16 @@ struct TxMapPlan {
 };
 
 /* checks and ranges; the workgroup table needs the address the grid is written at (txm_plan_wgs) */
-int txm_plan(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, TxMapPlan &p)
+int txm_plan(const char *who, const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, TxMapPlan &p)
 {
   std::vector<Range64> out;
   p.jobs.resize(n_seg);
   for (uint32_t i = 0; i < n_seg; i++) {
     const nrLDPC_hip_pdsch_map_seg_t &g = seg[i];
-    if (txm_check_seg("pdsch_resource_mapping", g) != 0)
+    if (txm_check_seg(who, g) != 0)
       return -1;
     if (n_tx < g.Nl)
-      return set_error("pdsch_resource_mapping: n_tx is below a descriptor's Nl");
+      return set_error((std::string(who) + ": n_tx is below a descriptor's Nl").c_str());
     const uint64_t lay0 = g.lay_off / 2u + g.sym_off;
     p.lay_lo = std::min(p.lay_lo, lay0);
     p.lay_hi = std::max(p.lay_hi, lay0 + (uint64_t)(g.Nl - 1u) * g.plane + g.nb_re);
@@ -121,12 +121,14 @@ int txm_plan(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_t
       j.ports |= (uint32_t)g.port[l] << (8u * l);
   }
   if (ranges_overlap(out, p.out_lo, p.out_hi))
-    return set_error("pdsch_resource_mapping: the output ranges of two (descriptor, antenna) pairs overlap");
+    return set_error((std::string(who) + ": the output ranges of two (descriptor, antenna) pairs overlap").c_str());
   return 0;
 }
 
-/* the workgroup table, pattern by pattern; tx = the address the kernel is given, the jobs' tx_off as they will be launched */
-void txm_plan_wgs(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, const void *tx, TxMapPlan &p)
+/* the workgroup table, pattern by pattern; tx = the address the kernel is given, the jobs' tx_off as they will be launched.
+ * precoded: every antenna needs the pilots of every layer, so its Gold registers stand where the port with the latest pilots is */
+void txm_plan_wgs(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, const void *tx, TxMapPlan &p,
+                  bool precoded = false)
 {
   const uint64_t word0 = (uint64_t)(reinterpret_cast<uintptr_t>(tx) >> 2);
   for (uint32_t pattern = 0; pattern < NR_PDM_PATTERNS; pattern++)
@@ -141,7 +143,9 @@ void txm_plan_wgs(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_
         w.ant = a;
         w.phase = (uint32_t)((word0 + j.tx_off + (uint64_t)a * tx_stride + j.start_re) & 3u);
         uint32_t pm = 0, dm = 0;
-        if (a < g.Nl)
+        if (precoded)
+          pm = nr_pdm_last_pmask(pattern);
+        else if (a < g.Nl)
           nr_pdm_masks(pattern, g.ncdm, nr_pdm_delta(pattern, g.port[a]), &pm, &dm);
         for (uint32_t q = 0; (uint64_t)q * NR_TXM_THREADS * NR_TXM_GROUP < (uint64_t)j.n_re + w.phase; q++) {
           w.piece = q;
@@ -166,6 +170,29 @@ int txm_launch(const TxMapPlan &p, const tx_map_wg *wgs, const tx_map_job *jobs,
     first += p.n_wg[pattern];
   }
   return 0;
+}
+
+/* HOST mem: the workgroup table at its largest, one piece more per (descriptor, antenna) than the REs alone need */
+size_t txm_max_wg(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx)
+{
+  size_t max_wg = 0;
+  for (uint32_t i = 0; i < n_seg; i++)
+    max_wg += (size_t)n_tx * ((12u * (size_t)seg[i].rb_size + 3u) / (NR_TXM_THREADS * NR_TXM_GROUP) + 1u);
+  return max_wg;
+}
+/* HOST mem: only the write set goes from the bounce (its c16 0 = out_lo of the grid) to the caller's array */
+void txm_scatter(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_ant_stride, const uint8_t *bounce, uint64_t out_lo,
+                 int16_t *txdataF)
+{
+  for (uint32_t i = 0; i < n_seg; i++) {
+    const uint32_t n_re = 12u * seg[i].rb_size, first = std::min(n_re, seg[i].fft_size - seg[i].start_re);
+    for (uint32_t a = 0; a < n_tx; a++) {
+      const uint64_t base = seg[i].tx_off + (uint64_t)a * tx_ant_stride;
+      memcpy(txdataF + 2 * (base + seg[i].start_re), bounce + 4u * (base + seg[i].start_re - out_lo), (size_t)first * 4u);
+      if (first < n_re)
+        memcpy(txdataF + 2 * base, bounce + 4u * (base - out_lo), (size_t)(n_re - first) * 4u);
+    }
+  }
 }
 
 } // namespace
@@ -303,7 +330,7 @@ int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdata
   if (n_seg && (!layers || !txdataF || !seg))
     return set_error("null argument");
   TxMapPlan p;
-  if (txm_plan(seg, n_seg, n_tx, tx_ant_stride, p) != 0)
+  if (txm_plan("pdsch_resource_mapping", seg, n_seg, n_tx, tx_ant_stride, p) != 0)
     return -1;
   if (n_seg == 0)
     return 0;
@@ -332,9 +359,7 @@ int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdata
   const size_t lay_n = (size_t)(p.lay_hi - p.lay_lo) * 4u, out_b = (size_t)(p.out_hi - p.out_lo) * 4u;
   /* the workgroup table's phases depend on where the bounce lies, so the buffers come first, for a table of the largest size:
    * one piece more per (descriptor, antenna) at the most */
-  size_t max_wg = 0;
-  for (uint32_t i = 0; i < n_seg; i++)
-    max_wg += (size_t)n_tx * ((12u * (size_t)seg[i].rb_size + 3u) / (NR_TXM_THREADS * NR_TXM_GROUP) + 1u);
+  const size_t max_wg = txm_max_wg(seg, n_seg, n_tx);
   if (st.ensure(out_b, Table2<tx_map_wg, const tx_map_job>::bytes(max_wg, p.jobs.size()) + align_up(lay_n, 16)) != 0)
     return -1;
   txm_plan_wgs(seg, n_seg, n_tx, tx_ant_stride, st.d_out(), p);
@@ -348,16 +373,7 @@ int32_t nrLDPC_hip_pdsch_resource_mapping(const int16_t *layers, int16_t *txdata
   };
   if (st.run(st.top, launch, out_b) != 0)
     return -1;
-  /* only the write set goes to the caller's array */
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const uint32_t n_re = 12u * seg[i].rb_size, first = std::min(n_re, seg[i].fft_size - seg[i].start_re);
-    for (uint32_t a = 0; a < n_tx; a++) {
-      const uint64_t base = seg[i].tx_off + (uint64_t)a * tx_ant_stride;
-      memcpy(txdataF + 2 * (base + seg[i].start_re), st.h_out() + 4u * (base + seg[i].start_re - p.out_lo), (size_t)first * 4u);
-      if (first < n_re)
-        memcpy(txdataF + 2 * base, st.h_out() + 4u * (base - p.out_lo), (size_t)(n_re - first) * 4u);
-    }
-  }
+  txm_scatter(seg, n_seg, n_tx, tx_ant_stride, st.h_out(), p.out_lo, txdataF);
   return 0;
 }
 

@@ -1544,3 +1544,99 @@ def pdsch_resource_mapping(layers, tx, tx_ant_stride, n_tx, segs, stream=None):
     _check(_pdm_lib().nrLDPC_hip_pdsch_resource_mapping(ptr(layers), ptr(tx), tx_ant_stride, n_tx, _pdm_seg_array(segs), len(segs), mem, s),
            "nrLDPC_hip_pdsch_resource_mapping")
     return tx
+
+
+# ---------------------------------------------------------------------------------------------------------
+# PDSCH resource mapping with precoding (include/nrLDPC_hip.h: pdsch_resource_mapping_precoded and its host forms)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_pdsch_resource_mapping_precoded", "nrLDPC_hip_pdsch_precode_host", "nrLDPC_hip_pdsch_precode_segments"]
+
+
+class nrLDPC_hip_pm_pdu_t(C.Structure):
+    _fields_ = [("pm_idx", C.c_uint16), ("numLayers", C.c_uint16), ("num_ant_ports", C.c_uint16), ("pad", C.c_uint16),
+                ("weights", C.c_int16 * 2 * 8 * 4)]
+
+
+class nrLDPC_hip_pdsch_prg_t(C.Structure):
+    _fields_ = [("prg_size", C.c_uint32), ("pmi_off", C.c_uint32), ("pmi_count", C.c_uint32)]
+
+
+_PDM_PRG_KEYS = ("prg_size", "pmi_off", "pmi_count")
+
+
+def _pre_lib():
+    L = _pdm_lib()
+    S, A, G, M = (C.POINTER(nrLDPC_hip_pdsch_map_seg_t), C.POINTER(nrLDPC_hip_pdsch_alloc_t), C.POINTER(nrLDPC_hip_pdsch_prg_t),
+                  C.POINTER(nrLDPC_hip_pm_pdu_t))
+    L.nrLDPC_hip_pdsch_resource_mapping_precoded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, S, G, C.c_uint32, C.c_void_p, C.c_uint32, M,
+                                                             C.c_uint32, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_pdsch_resource_mapping_precoded.restype = C.c_int32
+    L.nrLDPC_hip_pdsch_precode_host.argtypes = [C.c_void_p, S, G, C.c_void_p, C.c_uint32, M, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.nrLDPC_hip_pdsch_precode_host.restype = C.c_int32
+    L.nrLDPC_hip_pdsch_precode_segments.argtypes = [A, G, C.c_uint32, C.c_uint32, S, G, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.nrLDPC_hip_pdsch_precode_segments.restype = C.c_int32
+    return L
+
+
+def pdsch_pm_table(mats):
+    """The precoding-matrix table: dicts with pm_idx, numLayers, num_ant_ports and weights = int16 [layers <= 4][ports <= 8][2]
+    (Re, Im; what is not given is 0) -> (array of nrLDPC_hip_pm_pdu_t or None, n).  None / an empty list: no table."""
+    if not mats:
+        return None, 0
+    arr = (nrLDPC_hip_pm_pdu_t * len(mats))()
+    for i, d in enumerate(mats):
+        arr[i].pm_idx, arr[i].numLayers, arr[i].num_ant_ports = d["pm_idx"], d["numLayers"], d["num_ant_ports"]
+        w = np.asarray(d["weights"], np.int16)
+        assert w.ndim == 3 and w.shape[0] <= 4 and w.shape[1] <= 8 and w.shape[2] == 2
+        full = np.zeros((4, 8, 2), np.int16)
+        full[:w.shape[0], :w.shape[1]] = w
+        C.memmove(arr[i].weights, full.ctypes.data, full.nbytes)
+    return arr, len(mats)
+
+
+def _pre_args(segs, prgs, pmi_list, pm):
+    """the descriptors' PRG records, the flat PMI list and the matrix table as the C calls take them"""
+    if len(prgs) != len(segs):
+        raise ValueError("one PRG record per descriptor")
+    pmi = np.ascontiguousarray(pmi_list if pmi_list is not None else [], np.uint16)
+    tab, n_pm = pdsch_pm_table(pm)
+    return _struct_array(nrLDPC_hip_pdsch_prg_t, prgs, _PDM_PRG_KEYS), pmi, (pmi.ctypes.data if pmi.size else None), int(pmi.size), tab, n_pm
+
+
+def pdsch_precode_host(layers, seg, prg, pmi_list, pm, n_tx, ant, tx):
+    """nrLDPC_hip_pdsch_precode_host: one descriptor, antenna `ant` of n_tx, on the CPU (csrc/nr_pdsch_map.h, no GPU).  prg = dict with
+    prg_size, pmi_off, pmi_count; pmi_list = the flat PMI list; pm = the matrix table (dicts, see pdsch_pm_table) or None.  tx = int16
+    grid (written in place at seg's tx_off).  Returns tx."""
+    assert layers.dtype == np.int16 and tx.dtype == np.int16 and layers.flags.c_contiguous and tx.flags.c_contiguous
+    _pdm_check_extent([seg], 1, 0, layers.size // 2, tx.size // 2)
+    garr, keep, pmi_p, n_pmi, tab, n_pm = _pre_args([seg], [prg], pmi_list, pm)
+    _check(_pre_lib().nrLDPC_hip_pdsch_precode_host(layers.ctypes.data, _pdm_seg_array([seg]), garr, pmi_p, n_pmi, tab, n_pm, n_tx, ant, tx.ctypes.data),
+           "nrLDPC_hip_pdsch_precode_host")
+    return tx
+
+
+def pdsch_precode_segments(allocs, alloc_prgs, n_pmi, cap=None):
+    """nrLDPC_hip_pdsch_precode_segments: allocs as for pdsch_map_segments, alloc_prgs = one dict (prg_size, pmi_off, pmi_count) per
+    allocation, n_pmi = the length of the flat PMI list.  Returns (descriptors, their PRG records), two lists of dicts."""
+    n = len(allocs)
+    if len(alloc_prgs) != n:
+        raise ValueError("one PRG record per allocation")
+    arr, garr = _struct_array(nrLDPC_hip_pdsch_alloc_t, allocs, _PDM_ALLOC_KEYS), _struct_array(nrLDPC_hip_pdsch_prg_t, alloc_prgs, _PDM_PRG_KEYS)
+    cap = 14 * n if cap is None else cap
+    out, gout, n_out = (nrLDPC_hip_pdsch_map_seg_t * max(cap, 1))(), (nrLDPC_hip_pdsch_prg_t * max(cap, 1))(), C.c_uint32(0)
+    _check(_pre_lib().nrLDPC_hip_pdsch_precode_segments(arr, garr, n, n_pmi, out, gout, cap, C.byref(n_out)), "nrLDPC_hip_pdsch_precode_segments")
+    return ([{k: (list(out[i].port) if k == "port" else int(getattr(out[i], k))) for k in _PDM_SEG_KEYS} for i in range(n_out.value)],
+            [{k: int(getattr(gout[i], k)) for k in _PDM_PRG_KEYS} for i in range(n_out.value)])
+
+
+def pdsch_resource_mapping_precoded(layers, tx, tx_ant_stride, n_tx, segs, prgs, pmi_list, pm, stream=None):
+    """nrLDPC_hip_pdsch_resource_mapping_precoded: as pdsch_resource_mapping plus prgs = one dict (prg_size, pmi_off, pmi_count) per
+    descriptor (pdsch_precode_segments), pmi_list = the flat PMI list and pm = the matrix table (dicts, see pdsch_pm_table; None: no
+    table) -- host memory in both modes.  numpy int16 arrays -> host call; torch int16 CUDA tensors -> device call enqueued on
+    `stream`.  Returns tx."""
+    ptr, numel, mem, s = _mem_of((tx, layers), stream)
+    _pdm_check_extent(segs, n_tx, tx_ant_stride, numel(layers) // 2, numel(tx) // 2)
+    garr, keep, pmi_p, n_pmi, tab, n_pm = _pre_args(segs, prgs, pmi_list, pm)
+    _check(_pre_lib().nrLDPC_hip_pdsch_resource_mapping_precoded(ptr(layers), ptr(tx), tx_ant_stride, n_tx, _pdm_seg_array(segs), garr, len(segs), pmi_p,
+                                                                 n_pmi, tab, n_pm, mem, s), "nrLDPC_hip_pdsch_resource_mapping_precoded")
+    return tx

@@ -7,14 +7,23 @@ nrLDPC_hip_pdsch_resource_mapping, in one process, timed with HIP events.
 
 The call refuses a capturing stream, so nothing is replayed from a graph: every timed call is enqueued behind a filler (four
 encode calls) that keeps the GPU busy while the host enqueues, and the events around it see GPU time -- the descriptor upload
-and the kernels -- not the host's enqueueing.  The legs alternate inside one loop so that they see the same machine:
+and the kernels -- not the host's enqueueing.  (That holds while the filler outlasts the host: on the first hardware run it did
+not, the calls' plans for 832 descriptors take the host longer than four encode launches take the GPU, and the events measured
+the enqueue; profiles/r13/README.md has the kernel times from a trace beside them.)  The legs alternate inside one loop so that they see the same machine:
 
   mapping                    the mapping call alone (three launches: the patterns FULL and DMRS1 are present)
   device_copy                a plain device copy that reads the bytes the call reads (4 per data RE of the layer) and writes
                              the bytes it writes (4 per RE and antenna)
   encode_symbols             the slot's dlsch_encode_symbols, the figure the mapping is small or large against
 
-Before timing, the chain runs once and the grid of one block is compared with the host form's.
+The precoding arm, in the same loop: the same slot with two layers per block (Nl = 2, ports 0 and 1, layer planes of random
+values), n_tx = 4, prg_size = 2 and PMIs 1, 2, 1, ... (none 0) through two 2 x 4 matrices:
+
+  precoded                   nrLDPC_hip_pdsch_resource_mapping_precoded
+  unit_same_descriptors      nrLDPC_hip_pdsch_resource_mapping with n_tx = 4 on the same descriptors: the same bytes written
+  copy_of_bytes_written      a plain device copy of as many bytes as either call writes
+
+Before timing, each chain runs once and the grid of one block is compared with the host form's.
 """
 import json
 import sys
@@ -74,6 +83,40 @@ def device_copy():
     copy_dst[bytes_read:].fill_(0)                           # the rest is written without a read: pilots and zero planes
 
 
+# ---- the precoding arm ----
+LP = m._pre_lib()
+Nl2 = 2
+allocs2 = [dict(a, Nl=Nl2, dmrs_ports=0b11, lay_off=2 * i * Nl2 * S) for i, a in enumerate(allocs)]
+n_prg = (rb + 1) // 2
+pmis = [1 + (q & 1) for q in range(n_prg)] * n
+segs2, prgs2 = m.pdsch_precode_segments(allocs2, [dict(prg_size=2, pmi_off=i * n_prg, pmi_count=n_prg) for i in range(n)], len(pmis))
+assert len(segs2) == 13 * n
+seg2_arr = m._pdm_seg_array(segs2)
+prg2_arr = m._struct_array(m.nrLDPC_hip_pdsch_prg_t, prgs2, m._PDM_PRG_KEYS)
+pmi_arr = np.ascontiguousarray(pmis, np.uint16)
+table = [dict(pm_idx=t + 1, numLayers=Nl2, num_ant_ports=n_tx, weights=rng.integers(-16384, 16385, (Nl2, n_tx, 2)).astype(np.int16)) for t in range(2)]
+pm_arr, n_pm = m.pdsch_pm_table(table)
+with torch.cuda.stream(side):
+    layers2 = torch.randint(-32768, 32768, (n * Nl2 * S, 2), dtype=torch.int16, device="cuda")
+    tx2 = torch.zeros(n_tx, stride, 2, dtype=torch.int16, device="cuda")
+    written_src = torch.zeros(bytes_written, dtype=torch.uint8, device="cuda")
+    written_dst = torch.zeros(bytes_written, dtype=torch.uint8, device="cuda")
+torch.cuda.synchronize()
+
+
+def precoded():
+    assert LP.nrLDPC_hip_pdsch_resource_mapping_precoded(layers2.data_ptr(), tx2.data_ptr(), stride, n_tx, seg2_arr, prg2_arr, len(segs2), pmi_arr.ctypes.data,
+                                                         len(pmis), pm_arr, n_pm, m.MEM_DEVICE, s_ptr) == 0, m.last_error()
+
+
+def unit_same_descriptors():
+    assert LM.nrLDPC_hip_pdsch_resource_mapping(layers2.data_ptr(), tx2.data_ptr(), stride, n_tx, seg2_arr, len(segs2), m.MEM_DEVICE, s_ptr) == 0, m.last_error()
+
+
+def copy_of_bytes_written():
+    written_dst.copy_(written_src)
+
+
 def filler():
     for _ in range(4):
         encode_symbols()
@@ -92,7 +135,18 @@ for s in segs[13 * i0:13 * i0 + 13]:
 lo, hi = i0 * 14 * N, (i0 + 1) * 14 * N
 res = {"reps": reps, "n_tb": n, "n_tx": n_tx, "Nl": 1, "Qm": Qm, "fft_size": N, "rb": rb, "descriptors": len(segs),
        "device_equals_host_form": bool(np.array_equal(got[:, lo:hi], want[:, lo:hi])), "bytes_read": bytes_read, "bytes_written": bytes_written}
-legs = {"mapping": mapping, "device_copy": device_copy, "encode_symbols": encode_symbols}
+with torch.cuda.stream(side):
+    precoded()
+torch.cuda.synchronize()
+lay2_h, got2 = layers2.cpu().numpy(), tx2.cpu().numpy()
+want2 = np.zeros((n_tx, stride, 2), np.int16)
+for s, g in zip(segs2[13 * i0:13 * i0 + 13], prgs2[13 * i0:13 * i0 + 13]):
+    for a in range(n_tx):
+        m.pdsch_precode_host(lay2_h, s, g, pmis, table, n_tx, a, want2[a])
+res.update({"precoded_Nl": Nl2, "precoded_prg_size": 2, "precoded_equals_host_form": bool(np.array_equal(got2[:, lo:hi], want2[:, lo:hi])),
+            "precoded_block_is_not_zero": bool(want2[:, lo:hi].any())})
+legs = {"mapping": mapping, "device_copy": device_copy, "encode_symbols": encode_symbols, "precoded": precoded,
+        "unit_same_descriptors": unit_same_descriptors, "copy_of_bytes_written": copy_of_bytes_written}
 for fn in legs.values():
     with torch.cuda.stream(side):
         for _ in range(3):
@@ -117,4 +171,8 @@ for k in ("mapping", "device_copy"):
 med = lambda k: float(np.median(ts[k]))
 res["mapping_over_copy"] = {"median": med("mapping") / med("device_copy"), "min": float(np.min(ts["mapping"]) / np.min(ts["device_copy"]))}
 res["mapping_over_encode"] = {"median": med("mapping") / med("encode_symbols")}
+for k in ("precoded", "unit_same_descriptors", "copy_of_bytes_written"):
+    res[k + "_bytes_written_share_of_hbm_peak"] = {"median": bytes_written / (med(k) * 1e-3) / HBM_PEAK}
+res["precoded_over_unit"] = {"median": med("precoded") / med("unit_same_descriptors"), "min": float(np.min(ts["precoded"]) / np.min(ts["unit_same_descriptors"]))}
+res["precoded_over_copy"] = {"median": med("precoded") / med("copy_of_bytes_written"), "min": float(np.min(ts["precoded"]) / np.min(ts["copy_of_bytes_written"]))}
 print(json.dumps(res))
