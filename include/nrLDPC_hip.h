@@ -373,8 +373,8 @@ int32_t nrLDPC_hip_layer_mapping(const int16_t *in, uint32_t n_symbs, uint8_t Nl
  * NR_TRANSPORT/nr_ulsch_demodulation.c:1612-1647 with nr_ulsch_scale_channel :382-415 and nr_ulsch_channel_level :434-466) and
  * nr_ulsch_channel_compensation (:468-577: matched filter and maximum ratio combining over the receive antennas) on the GPU, from
  * the extracted REs and channel estimates (rxFext[aarx], chFext[aarx] of inner_rx, :1281-1324) to the symbol records
- * nrLDPC_hip_ulsch_decode_symbols reads.  nrOfLayers == 1 and rho == NULL only; two layers, transform precoding and PTRS are
- * not here; the _grid calls below read the OFDM grid itself.  rxFext / chFext are c16 arrays (int16 re, im), antenna a's values ant_stride c16
+ * nrLDPC_hip_ulsch_decode_symbols reads.  nrOfLayers == 1 and rho == NULL only; transform precoding and PTRS are
+ * not here; the _grid calls below read the OFDM grid itself, and two layers of 64QAM / 256QAM take the MMSE calls behind them.  rxFext / chFext are c16 arrays (int16 re, im), antenna a's values ant_stride c16
  * behind antenna 0's; n_rx = 1..8.  A descriptor (host memory) names one OFDM symbol's data REs of one transport block:
  *   channel_compensation: for each of the n_seg segments and each RE r < nb_re, over the antennas in order (csrc/nr_rx_front.h
  *     has the arithmetic, with int16 sums that wrap and packs that saturate exactly where the reference's do), with
@@ -491,6 +491,44 @@ int32_t nrLDPC_hip_ulsch_extract_host(const int16_t *rxdataF, const int16_t *ul_
                                       uint32_t nb_re, int16_t *rxFext, int16_t *chFext);
 int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_rx_grid_seg_t *seg_out, uint32_t cap,
                                        nrLDPC_hip_rx_grid_seg_t *first_sym_out, uint32_t *n_seg_out);
+/* Two layers, 64QAM and 256QAM: the reference's MMSE receiver (inner_rx, nr_ulsch_demodulation.c:1348-1389: Qm >= 6 goes through
+ * nr_ulsch_mmse_2layers :869-1260 and then the per-layer nr_ulsch_compute_llr) from the OFDM grid and the per-layer channel
+ * estimates to the symbol records nrLDPC_hip_ulsch_decode_symbols reads with Nl = 2, bit for bit; csrc/nr_rx_mmse.h has the
+ * arithmetic.  The descriptors are those of the _grid calls above (pusch_grid_segments derives them, with plane = G/Qm = twice the
+ * allocation's REs and sym_off = llr_offset[symbol]/Qm counted per layer); n_rx = 2 or 4, the antenna counts the reference
+ * accepts (:915-941).  The estimates of layer l, antenna a ("pair" l n_rx + a, :917-935) lie at ch_off + (l n_rx + a)
+ * ch_ant_stride + p(j): 2 n_rx arrays.
+ *   mmse_2layers_grid: per RE the two layers' matched filters over the antennas (:505-548), H^H H with saturating sums (:646-687,
+ *     :756-867), nvar[tb] added to its diagonal when it is not 0 (:1103-1113, a 32-bit add on the packed word, as written), the
+ *     determinant (:580-640); then per quad of four consecutive REs counted from the segment's RE 0 -- one 128-bit vector --
+ *     the shared shift b = log2_approx(sum of det >> 2) - 8, the magnitudes (the same for both layers) and y0 d - y1 b,
+ *     y1 a - y0 c (:1174-1256, :689-750), with s = shift[tb] clamped to 0..31.  A last quad that is only partly inside nb_re
+ *     computes with the reference's zero padding in its outer lanes (they enter the sum, with what nvar makes of them).  Layer
+ *     de-mapping (:1431-1438) is in the store: RE r of layer l is c16 index 2 (sym_off + r) + l of each plane k < Qm/2.  The
+ *     write set per segment is exactly entries 2 sym_off .. 2 (sym_off + nb_re) - 1 of each of the Qm/2 planes, overwritten.
+ *   channel_level_grid_mmse: log2_maxh[tb] = max(0, (log2_approx(avgs) >> 1) - 3) (:1639-1647), avgs = max(0, the 2 n_rx pairs'
+ *     averages) of the measurement symbol scaled by nr_ulsch_scale_channel with shift_ch_ext = log2_approx(max_ch[tb] >> 11)
+ *     (:1614, the general branch :392-402).
+ * max_ch and nvar come out of the reference's channel estimator (nr_ul_channel_estimation.c:187, :468-469); the estimator
+ * here does not produce them, so they are inputs, one value per tb like shift, read from device memory in DEVICE mode.
+ * mem modes, staging and refusals are those of the _grid calls; further refusals: Qm other than 6 or 8 (two layers of QPSK /
+ * 16QAM take the ML receiver, which writes LLRs and is not built), n_rx other than 2 or 4, 2 (sym_off + nb_re) > plane, a NULL
+ * nvar / max_ch or (DEVICE) one that is not device memory of that GPU, two segments whose doubled output ranges overlap.
+ * One deviation: where the reference aborts (AssertFatal :1181, a determinant lane <= 0) the arithmetic goes on with what the
+ * instructions give (a quad of zero determinants: b = -8); such a block fails its CRC.
+ * mmse_2layers_host / level_mmse_host: the same arithmetic on the CPU, no GPU involved, for checking: one segment from extracted
+ * arrays (chFext: the 2 n_rx pairs ant_stride apart, rxFext: the n_rx antennas ant_stride apart; out = layer 0's Qm/2 planes of
+ * nb_re c16, then layer 1's) / one block (avg, when not NULL, receives the 2 n_rx averages).  0 / -1. */
+int32_t nrLDPC_hip_ulsch_channel_level_grid_mmse(const int16_t *ul_ch, uint32_t n_rx, uint64_t ch_ant_stride,
+                                                 const nrLDPC_hip_rx_grid_seg_t *first_sym, uint32_t n_tb, const int32_t *max_ch,
+                                                 int32_t *log2_maxh, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_mmse_2layers_grid(const int16_t *rxdataF, const int16_t *ul_ch, uint32_t n_rx, uint64_t rx_ant_stride,
+                                           uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, const int32_t *shift,
+                                           const uint32_t *nvar, int16_t *records, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_mmse_2layers_host(const int16_t *rxFext, const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re,
+                                           uint8_t Qm, int32_t shift, uint32_t nvar, int16_t *out);
+int32_t nrLDPC_hip_ulsch_level_mmse_host(const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re, int32_t max_ch,
+                                         int32_t *avg, int32_t *log2_maxh);
 /* ---------------------------------------------------------------------------------------------------
  * PUSCH DMRS channel estimation from the OFDM grid: nr_pusch_channel_estimation (openair1/PHY/NR_ESTIMATION/
  * nr_ul_channel_estimation.c:67-473) for one list of descriptors, one per (allocation, DMRS symbol), times n_rx antennas.  It

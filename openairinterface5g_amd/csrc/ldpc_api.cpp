@@ -37,6 +37,8 @@
 #include "nr_pdsch_map.h"
 #include "tb_tx_map.h"
 #include "tb_rx_front.h"
+#include "nr_rx_mmse.h"
+#include "tb_rx_mmse.h"
 #include "ldpc_enc_packed_core.h"
 
 namespace {
@@ -1511,6 +1513,7 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "qam_api.inc.cpp"
 #include "rx_front_api.inc.cpp"
 #include "rx_grid_api.inc.cpp"
+#include "rx_mmse_api.inc.cpp"
 #include "rx_chest_api.inc.cpp"
 #include "tx_map_api.inc.cpp"
 #include "tx_precode_api.inc.cpp"

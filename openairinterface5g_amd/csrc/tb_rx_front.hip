@@ -12,6 +12,7 @@
 #include "nr_rx_front.h"
 #include "nr_rx_grid.h"
 #include "tb_rx_front.h"
+#include "tb_rx_level.h"
 
 typedef uint32_t rxf_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -249,40 +250,23 @@ hipError_t nr_launch_rx_compensation_grid(const rx_front_wg *wgs, uint32_t n_wg,
 }
 
 /* ---- channel level: workgroup (block b, antenna a) sums the terms of b's measurement symbol on antenna a; the block's maximum
- * and the count of antennas done are device-scope atomics, and the last antenna to arrive writes log2_maxh ---- */
+ * and the count of antennas done are device-scope atomics, and the last antenna to arrive writes log2_maxh (tb_rx_level.h) ---- */
 /* GRID: Job = rx_front_grid_lvl_job, term r is the estimate of PUSCH subcarrier p(r) */
 template <bool GRID, typename Job>
 __device__ __forceinline__ void rx_level_body(const Job *__restrict__ jobs, const uint32_t *__restrict__ ch, uint32_t n_rx, uint64_t ant_stride, int32_t *mx,
                                               int32_t *cnt, int32_t *__restrict__ log2_maxh)
 {
-  __shared__ uint32_t part[NR_RXF_THREADS / 64];
   const uint32_t b = blockIdx.x / n_rx, a = blockIdx.x % n_rx;
   const Job j = jobs[b];
   const uint32_t len = nr_rxf_level_len(j.nb_re), x = (uint32_t)nr_rxf_factor2(len);
   const uint32_t *h = ch + j.ch_off + (size_t)a * ant_stride;
-  uint32_t sum = 0; /* wrapping int32 */
-  for (uint32_t r = threadIdx.x; r < j.nb_re; r += NR_RXF_THREADS) {
+  const auto term = [&](uint32_t r) {
     if constexpr (GRID)
-      sum += (uint32_t)nr_rxf_level_term(h[nr_rxg_p(j.pattern, r)], x);
+      return nr_rxf_level_term(h[nr_rxg_p(j.pattern, r)], x);
     else
-      sum += (uint32_t)nr_rxf_level_term(h[r], x);
-  }
-  for (int off = 32; off; off >>= 1)
-    sum += __shfl_xor(sum, off);
-  if ((threadIdx.x & 63u) == 0)
-    part[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x != 0)
-    return;
-  sum = 0;
-  for (int k = 0; k < NR_RXF_THREADS / 64; k++)
-    sum += part[k];
-  /* mx starts at 0: avgs = max(0, ...) (:1634-1637) */
-  __hip_atomic_fetch_max(&mx[b], nr_rxf_level_avg((int32_t)sum, len), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  /* release: the maximum above is out before the count; acquire: the last one sees every maximum before it */
-  if (__hip_atomic_fetch_add(&cnt[b], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) != (int32_t)n_rx - 1)
-    return;
-  log2_maxh[j.tb] = nr_rxf_log2_maxh(__hip_atomic_load(&mx[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), n_rx);
+      return nr_rxf_level_term(h[r], x);
+  };
+  rx_level_sum(b, n_rx, j.nb_re, len, term, [&](int32_t avgs) { return nr_rxf_log2_maxh(avgs, n_rx); }, mx, cnt, &log2_maxh[j.tb]);
 }
 
 __global__ void __launch_bounds__(NR_RXF_THREADS)

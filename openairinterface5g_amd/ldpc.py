@@ -1344,6 +1344,96 @@ def ulsch_channel_compensation_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, 
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Two-layer MMSE receiver for 64QAM / 256QAM (include/nrLDPC_hip.h: the _mmse calls; csrc/nr_rx_mmse.h)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_ulsch_channel_level_grid_mmse", "nrLDPC_hip_ulsch_mmse_2layers_grid", "nrLDPC_hip_ulsch_mmse_2layers_host",
+            "nrLDPC_hip_ulsch_level_mmse_host"]
+
+
+def _rxm_lib():
+    L = _rxg_lib()
+    P = C.POINTER(nrLDPC_hip_rx_grid_seg_t)
+    L.nrLDPC_hip_ulsch_channel_level_grid_mmse.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, P, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                           C.c_void_p]
+    L.nrLDPC_hip_ulsch_channel_level_grid_mmse.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_mmse_2layers_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, P, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_mmse_2layers_grid.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_mmse_2layers_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint8, C.c_int32, C.c_uint32,
+                                                     C.c_void_p]
+    L.nrLDPC_hip_ulsch_mmse_2layers_host.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_level_mmse_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.nrLDPC_hip_ulsch_level_mmse_host.restype = C.c_int32
+    return L
+
+
+def _rxm_check_records(segs, rec_len):
+    """a segment's doubled output range must lie inside `records` (rec_len in int16)"""
+    for s in segs:
+        if s["nb_re"] and s["Qm"] in (6, 8) and s["rec_off"] + 2 * ((s["Qm"] // 2 - 1) * s["plane"] + 2 * (s["sym_off"] + s["nb_re"])) > rec_len:
+            raise ValueError("a segment's entries leave the record array")
+
+
+def ulsch_mmse_2layers_host(rx, ch, n_rx, ant_stride, nb_re, Qm, shift, nvar):
+    """The two-layer MMSE receiver for one segment on the CPU (csrc/nr_rx_mmse.h, no GPU): rx = numpy int16 c16, antenna a's RE r
+    at c16 index a * ant_stride + r; ch the same for pair l * n_rx + a.  Returns int16[2, Qm/2, nb_re, 2]: per layer y, mag_a, mag_b,
+    mag_c."""
+    rx, ch = np.ascontiguousarray(rx, np.int16).reshape(-1), np.ascontiguousarray(ch, np.int16).reshape(-1)
+    if n_rx in (2, 4):
+        assert rx.size >= 2 * ((n_rx - 1) * ant_stride + nb_re) and ch.size >= 2 * ((2 * n_rx - 1) * ant_stride + nb_re)
+    np_ = Qm // 2 if Qm in (6, 8) else 1
+    out = np.zeros((2, np_, max(nb_re, 1), 2), np.int16)
+    _check(_rxm_lib().nrLDPC_hip_ulsch_mmse_2layers_host(rx.ctypes.data, ch.ctypes.data, n_rx, ant_stride, nb_re, Qm, shift, nvar, out.ctypes.data),
+           "nrLDPC_hip_ulsch_mmse_2layers_host")
+    return out.reshape(-1)[:2 * np_ * nb_re * 2].reshape(2, np_, nb_re, 2)
+
+
+def ulsch_level_mmse_host(ch, n_rx, ant_stride, nb_re, max_ch):
+    """The channel level of one two-layer block's measurement symbol on the CPU (no GPU): (log2_maxh, int32[2 n_rx] averages)."""
+    ch = np.ascontiguousarray(ch, np.int16).reshape(-1)
+    if n_rx in (2, 4):
+        assert ch.size >= 2 * ((2 * n_rx - 1) * ant_stride + nb_re)
+    avg, out = np.zeros(8, np.int32), np.zeros(1, np.int32)
+    _check(_rxm_lib().nrLDPC_hip_ulsch_level_mmse_host(ch.ctypes.data, n_rx, ant_stride, nb_re, max_ch, avg.ctypes.data, out.ctypes.data),
+           "nrLDPC_hip_ulsch_level_mmse_host")
+    return int(out[0]), avg[:2 * n_rx]
+
+
+def ulsch_channel_level_grid_mmse(ch, n_rx, ch_ant_stride, first_sym, max_ch, out=None, stream=None):
+    """nrLDPC_hip_ulsch_channel_level_grid_mmse: ch = the full-width channel estimates of the 2 n_rx (layer, antenna) pairs,
+    ch_ant_stride apart; first_sym = one grid descriptor per block; max_ch = int32 per block.  numpy -> host call, returns
+    int32[n_tb]; torch CUDA tensors -> device call enqueued on `stream` into `out` (torch int32 CUDA, >= n_tb elements); returns
+    `out`."""
+    n, res = len(first_sym), _level_out(ch, out, len(first_sym))
+    if isinstance(ch, np.ndarray):
+        max_ch = np.ascontiguousarray(max_ch, np.int32)
+    ptr, numel, mem, s = _mem_of((ch,), stream, (res, max_ch))
+    assert numel(max_ch) >= n
+    _rxg_check_extent(first_sym, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _check(_rxm_lib().nrLDPC_hip_ulsch_channel_level_grid_mmse(ptr(ch), n_rx, ch_ant_stride, _rx_grid_seg_array(first_sym), n, ptr(max_ch), ptr(res),
+                                                               mem, s), "nrLDPC_hip_ulsch_channel_level_grid_mmse")
+    return res[:n] if mem == MEM_HOST else res
+
+
+def ulsch_mmse_2layers_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, shift, nvar, records, stream=None):
+    """nrLDPC_hip_ulsch_mmse_2layers_grid: rx = the OFDM grid (n_rx antennas), ch = the full-width channel estimates (2 n_rx
+    pairs), segs = the grid descriptors (pusch_grid_segments with plane = G/Qm); shift = int32 per block (the output of
+    ulsch_channel_level_grid_mmse), nvar = int32 per block holding the uint32 noise variance; records = the int16 array the blocks'
+    symbol records lie in, written in place -- only the segments' entries.  numpy arrays -> host call; torch CUDA tensors -> device
+    call enqueued on `stream`.  Returns `records`."""
+    if isinstance(rx, np.ndarray):
+        shift = np.ascontiguousarray(shift, np.int32)
+        nvar = np.ascontiguousarray(np.asarray(nvar).astype(np.uint32).view(np.int32))
+    ptr, numel, mem, s = _mem_of((rx, ch, records), stream, (shift, nvar))
+    _rxg_check_extent(segs, n_rx, rx_ant_stride, 0, numel(rx) // 2, None)
+    _rxg_check_extent(segs, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _rxm_check_records(segs, numel(records))
+    _check(_rxm_lib().nrLDPC_hip_ulsch_mmse_2layers_grid(ptr(rx), ptr(ch), n_rx, rx_ant_stride, ch_ant_stride, _rx_grid_seg_array(segs), len(segs),
+                                                         ptr(shift), ptr(nvar), ptr(records), mem, s), "nrLDPC_hip_ulsch_mmse_2layers_grid")
+    return records
+
+
+# ---------------------------------------------------------------------------------------------------------
 # PUSCH DMRS channel estimation (include/nrLDPC_hip.h: pusch_channel_estimation and its host forms; csrc/nr_chest.h)
 # ---------------------------------------------------------------------------------------------------------
 EXPORTS += ["nrLDPC_hip_pusch_channel_estimation", "nrLDPC_hip_pusch_chest_host", "nrLDPC_hip_pusch_dmrs_host", "nrLDPC_hip_delay_table_host",
