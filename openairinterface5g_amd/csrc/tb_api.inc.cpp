@@ -725,16 +725,11 @@ struct TbTxCall {
       /* workgroup size: 256 threads let every CU hold eight segments (a whole 1664-segment slot is resident at once);
        * a launch that does not even fill the GPU four deep takes 512 and halves the rounds of its long stages */
       const int fused_threads = pl.n_seg <= (size_t)4 * (size_t)G().n_cus ? 512 : pl.enc_threads;
-      const int lds = pl.enc_lds + TB_TX_FUSED_EXTRA_LDS;
+      const tb_tx_out mode = sym ? TB_TX_OUT_SYMBOLS : (scr ? TB_TX_OUT_PACKED : TB_TX_OUT_BYTES);
       TB_DEBUG_STAGE("tx: TB CRC launch");
-      if (sym)
-        HIP_TRY(tb_launch_tx_fused_sym(d_seg, d_enc, n_seg, fused_threads, lds + TB_TX_FUSED_SYM_LDS, v.payload, v.coded,
-                                       G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
-      else if (scr)
-        HIP_TRY(tb_launch_tx_fused_scr(d_seg, d_enc, n_seg, fused_threads, lds + TB_TX_FUSED_SCR_LDS, v.payload, v.coded,
-                                       G().crc_pow[NR_HIP_CRC24_B], d_acc, pl.at<uint32_t>(pl.o_tickets), pl.at<uint32_t>(pl.o_parts), s));
-      else
-        HIP_TRY(tb_launch_tx_fused(d_seg, d_enc, n_seg, fused_threads, lds, v.payload, v.coded, G().crc_pow[NR_HIP_CRC24_B], d_acc, s));
+      /* (tickets and parts: empty unless the plan is a packed store's) */
+      HIP_TRY(tb_launch_tx_fused(mode, d_seg, d_enc, n_seg, fused_threads, pl.enc_lds, v.payload, v.coded, G().crc_pow[NR_HIP_CRC24_B], d_acc,
+                                 pl.at<uint32_t>(pl.o_tickets), pl.at<uint32_t>(pl.o_parts), s));
       TB_DEBUG_STAGE("tx: fused segment launch");
       return 0;
     }

@@ -18,22 +18,42 @@ hipError_t tb_launch_tx_crc(const tb_tx_tb_job *jobs, uint32_t n_tb, const tb_cr
                             const uint32_t *pow16, int with_final, hipStream_t s);
 hipError_t tb_launch_tx_segment(const tb_tx_seg_job *jobs, uint32_t n, uint8_t *scratch, const uint32_t *pow24b, hipStream_t s);
 hipError_t tb_launch_tx_ratematch(const tb_tx_seg_job *jobs, uint32_t n, const uint8_t *scratch, uint8_t *coded, hipStream_t s);
-/* segmentation + CB CRC + encoding + rate matching + interleaving in one kernel (bit-packed encoder); lds_bytes =
- * the encoder's LDS (ldpc_enc_launch_shape) + TB_TX_FUSED_EXTRA_LDS */
+/* segmentation + CB CRC + encoding + rate matching + interleaving in one kernel (bit-packed encoder, tb_tx_core.h).  Its LDS
+ * behind the encoder's (ldpc_enc_launch_shape): the CB CRC's meeting place, the segment's bytes, the selection chunk's Qm <= 8
+ * sub-streams (the CRC byte table lies there until the selection starts), then what the store form adds (tb_jobs.h):
+ * the chunk's sequence words and the carry words (TB_TX_FUSED_SCR_LDS) or the constellation (TB_TX_FUSED_SYM_LDS). */
 #define TB_TX_SEL_SYMS 2048 /* modulation symbols per selection chunk: Qm sub-streams of that many bits are staged in LDS */
-#define TB_TX_FUSED_EXTRA_LDS (8 + 1056 + 16 + 8 * (TB_TX_SEL_SYMS / 32 + 1) * 4)
+#define TB_TX_SEL_STRIDE (TB_TX_SEL_SYMS / 32 + 1) /* words from one sub-stream to the next */
+#define TB_TX_SEG_LDS (1056 + 16) /* K / 8 <= 1056 segment bytes; the image is written in dwords and cleared to K / 8 + 8 */
+#define TB_TX_FUSED_EXTRA_LDS (8 + TB_TX_SEG_LDS + 8 * TB_TX_SEL_STRIDE * 4)
+struct tb_tx_fused_lds {
+  uint32_t *red;    /* [2] */
+  uint8_t *c;       /* [TB_TX_SEG_LDS] */
+  uint32_t *tab;    /* [256], = sel */
+  uint32_t *sel;    /* [8][TB_TX_SEL_STRIDE] */
+  uint32_t *seq;    /* [TB_TX_SCR_WORDS], packed and symbol store only */
+  uint32_t *behind; /* the packed store's carry words / the symbol store's constellation */
+};
+TB_HD tb_tx_fused_lds tb_tx_fused_carve(uint32_t *behind_encoder)
+{
+  tb_tx_fused_lds l;
+  l.red = behind_encoder;
+  l.c = reinterpret_cast<uint8_t *>(l.red + 2);
+  l.tab = l.sel = reinterpret_cast<uint32_t *>(l.c + TB_TX_SEG_LDS);
+  l.seq = l.sel + 8 * TB_TX_SEL_STRIDE;
+  l.behind = l.seq + TB_TX_SCR_WORDS;
+  return l;
+}
+/* what a segment's workgroup stores: E bytes holding a bit each at coded + out_off; the packed, scrambled words (jobs' c_init /
+ * bit_off / h_* / t_*, tb_tx_scr.h): ceil(G/32) per TB at coded + out_off, tickets[] zero on entry and on exit, parts[] one slot
+ * per (shared word, segment); the symbols (nrLDPC_hip_dlsch_encode_symbols; jobs' c_init / bit_off / Nl / plane, tb_tx_sym.h):
+ * 4 G / Qm bytes of layer planes per TB at coded + out_off */
+enum tb_tx_out { TB_TX_OUT_BYTES, TB_TX_OUT_PACKED, TB_TX_OUT_SYMBOLS };
 struct ldpc_enc_job;
-hipError_t tb_launch_tx_fused(const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
-                              const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, hipStream_t s);
-/* the same with the packed, scrambled store (jobs' c_init / bit_off / h_* / t_*): ceil(G/32) words per TB at coded + out_off;
- * lds_bytes includes TB_TX_FUSED_SCR_LDS; tickets[] zero on entry and on exit, parts[] one slot per (shared word, segment) */
-hipError_t tb_launch_tx_fused_scr(const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
-                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets,
-                                  uint32_t *parts, hipStream_t s);
-/* the same with the symbol store (nrLDPC_hip_dlsch_encode_symbols; jobs' c_init / bit_off / Nl / plane, tb_tx_sym.h): 4 G / Qm
- * bytes of layer planes per TB at coded + out_off; lds_bytes includes TB_TX_FUSED_SYM_LDS */
-hipError_t tb_launch_tx_fused_sym(const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
-                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, hipStream_t s);
+/* enc_lds = the encoder's LDS; tickets, parts: TB_TX_OUT_PACKED only (nullptr otherwise) */
+hipError_t tb_launch_tx_fused(tb_tx_out mode, const tb_tx_seg_job *jobs, const struct ldpc_enc_job *ejobs, uint32_t n, int n_threads,
+                              int enc_lds, const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc,
+                              uint32_t *tickets, uint32_t *parts, hipStream_t s);
 hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,
                                 int8_t *scratch, hipStream_t s, int wide = 0);
 /* scrambled codewords: each segment's LLRs are unscrambled on the way in (jobs' c_init / bit_off; tb_rx_core.h) */

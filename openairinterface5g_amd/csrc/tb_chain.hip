@@ -26,6 +26,7 @@
 #define TB_RX_STORE_WINDOW 2
 #endif
 #include "tb_rx_core.h"
+#include "tb_tx_core.h"
 #include "tb_tx_sym.h"
 #include "tb_tx_scr.h"
 #include "nr_qam.h"
@@ -91,19 +92,6 @@ __device__ __forceinline__ void tb_build_crc_tab(const uint32_t *__restrict__ po
  * (reg = (reg << 8) ^ tab[(reg >> 24) ^ byte], LDS look-ups), then moves the piece's register R to the end of the
  * string: R(x) * x^n_after mod g = XOR over the set bits b of R of pow[b - 32 + n_after] (or the bit itself, shifted,
  * while it still fits under the generator's degree).  Valid in lane 0 of every wave. */
-/* R(x) * Q(x) mod g for left-aligned registers of a degree-DEG generator (poly = x^DEG mod g, left aligned): one Horner
- * step per coefficient of R -- the power Q = x^n mod g is ONE table look-up, where summing pow[] over the set bits of R
- * was a dozen dependent global loads per thread (the TB CRC kernels spent most of their 13-17 us there). */
-template <int DEG> __device__ __forceinline__ uint32_t tb_crc_mulmod(uint32_t R, uint32_t Q, uint32_t poly)
-{
-  uint32_t x = 0;
-#pragma unroll
-  for (int k = 31; k >= 32 - DEG; k--) {
-    x = (x << 1) ^ ((uint32_t)((int32_t)x >> 31) & poly);
-    x ^= (0u - ((R >> k) & 1u)) & Q;
-  }
-  return x;
-}
 template <int SPAN, int DEG>
 __device__ __forceinline__ uint32_t tb_partial_crc(const uint8_t *__restrict__ data, uint32_t nbits, uint32_t first, uint32_t count,
                                                    const uint32_t *__restrict__ pow, const uint32_t *tab)
@@ -252,82 +240,9 @@ __global__ void __launch_bounds__(TB_THREADS) tb_tx_ratematch_kernel(const tb_tx
 /* ---- TX 2+3 fused: segmentation + CB CRC + bit-packed LDPC encoding + rate matching + interleaving --------------
  * One workgroup per code block; the segment bytes, the code word (ldpc_enc_packed_core.h) and the selection all stay
  * in LDS: HBM traffic = the segment's payload bytes in, E output bytes out (no c / d round trip through scratch). */
-/* Interleaver output of one chunk of modulation symbols from its QM packed sub-streams (tb_tx_fused_kernel):
- * f[sy * QM + i] = bit sy of sub-stream i.  A thread takes 8 symbols: one byte of every sub-stream in, 8 QM bytes out, every
- * shift a compile-time constant (2 VALU per output byte; the first version did a division and a look-up per byte).
- * `dst` = where the chunk's first symbol goes; its alignment decides the store width. */
-template <int QM>
-__device__ __forceinline__ void tb_tx_store_syms(const uint32_t *sel, uint32_t sel_stride, uint32_t nsym, uint8_t *__restrict__ dst, int tid,
-                                                 int nt)
-{
-  const uint32_t ngrp = nsym >> 3, al = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u);
-  for (uint32_t g = tid; g < ngrp; g += nt) {
-    uint32_t win[QM];
-#pragma unroll
-    for (int i = 0; i < QM; i++)
-      win[i] = sel[i * sel_stride + (g >> 2)] >> (8u * (g & 3u));
-    /* output dword w of the group (compile-time shifts); formed right where it is stored, so that at most one is live
-     * (all 2 QM of them next to the eight windows pushed the kernel to 99 VGPRs = four waves per SIMD, and a 1664-segment
-     * slot then runs in two rounds of workgroups) */
-    /* QM = 6, 8: the 8 QM output bits of the group as two bit strings first -- symbols 0..3 and 4..7; bit sy of a sub-stream goes
-     * to position sy QM by ONE multiplication (x * (1 + 2^(QM-1) + 2^(2QM-2) + 2^(3QM-3)) puts bit k of a nibble at k + (QM-1) j
-     * for j = 0..3, of which j = k is the wanted QM k; no two of the sixteen positions coincide when QM - 1 >= 4, so nothing
-     * carries) -- then every nibble of a string becomes a dword of bytes by another one.  84 instead of ~150 VALU per group. */
-    uint32_t f_lo = 0, f_hi = 0;
-    if constexpr (QM == 6 || QM == 8) {
-      constexpr uint32_t M = 1u | (1u << (QM - 1)) | (1u << (2 * QM - 2)) | (1u << (3 * QM - 3));
-      constexpr uint32_t K = 1u | (1u << QM) | (1u << (2 * QM)) | (1u << (3 * QM));
-#pragma unroll
-      for (int i = 0; i < QM; i++) {
-        f_lo |= (((win[i] & 0xfu) * M) & K) << i;
-        f_hi |= ((((win[i] >> 4) & 0xfu) * M) & K) << i;
-      }
-    }
-    auto word = [&](int w) -> uint32_t {
-      if constexpr (QM == 6 || QM == 8) {
-        const uint32_t nib = ((w < QM ? f_lo : f_hi) >> (4 * (w < QM ? w : w - QM))) & 0xfu;
-        return (nib * 0x00204081u) & 0x01010101u;
-      }
-      uint32_t v = 0;
-#pragma unroll
-      for (int b = 0; b < 4; b++) {
-        const int m = 4 * w + b, sy = m / QM, i = m - sy * QM;
-        v |= ((win[i] >> sy) & 1u) << (8 * b);
-      }
-      return v;
-    };
-    uint8_t *o = dst + (size_t)g * (8 * QM);
-    if (al == 0) {
-#pragma unroll
-      for (int w = 0; w < 2 * QM; w++)
-        reinterpret_cast<uint32_t *>(o)[w] = word(w);
-    } else if (al == 2) {
-#pragma unroll
-      for (int w = 0; w < 2 * QM; w++) {
-        const uint32_t v = word(w);
-        reinterpret_cast<uint16_t *>(o)[2 * w] = (uint16_t)v;
-        reinterpret_cast<uint16_t *>(o)[2 * w + 1] = (uint16_t)(v >> 16);
-      }
-    } else {
-#pragma unroll
-      for (int w = 0; w < 2 * QM; w++) {
-        const uint32_t v = word(w);
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-          o[4 * w + b] = (uint8_t)(v >> (8 * b));
-      }
-    }
-  }
-  for (uint32_t m = ngrp * 8u * QM + tid; m < nsym * QM; m += nt) { /* the last, partial group */
-    const uint32_t sy = m / QM, i = m - sy * QM;
-    dst[m] = (uint8_t)((sel[i * sel_stride + (sy >> 5)] >> (sy & 31u)) & 1u);
-  }
-}
-
-typedef uint32_t tb_u32x4_t __attribute__((ext_vector_type(4)));
-template <typename J> __device__ __forceinline__ uint32_t crc_len_of(J j) { return j->crc_len; }
 /* SCR: the packed, scrambled store (tb_tx_fused_scr_kernel, tb_tx_scr.h) instead of the bit-per-byte one (tb_tx_fused_kernel); SCR + SYM:
- * the scrambled, mapped and layer-mapped points (tb_tx_fused_sym_kernel, tb_tx_sym.h) */
+ * the scrambled, mapped and layer-mapped points (tb_tx_fused_sym_kernel, tb_tx_sym.h).  The per-thread phases between the
+ * barriers are tb_tx_core.h's and the encoder's. */
 template <bool SCR, bool SYM = false>
 __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, const uint8_t *scratch, uint8_t *coded,
                                                  const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets, uint32_t *parts)
@@ -341,8 +256,9 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
   const int Z = code->Z, tid = threadIdx.x, nt = blockDim.x;
   ldpc_encp_lds L;
   ldpc_encp_carve(reinterpret_cast<uint32_t *>(fsm), code, L);
-  uint32_t *red = L.RP + code->nrows + 1;
-  uint8_t *c = reinterpret_cast<uint8_t *>(red + 2);
+  const tb_tx_fused_lds T = tb_tx_fused_carve(L.RP + code->nrows + 1);
+  uint32_t *const red = T.red, *const tab = T.tab; /* (the CRC byte table: the selection area is free until the end) */
+  uint8_t *const c = T.c;
 #ifdef TB_TIMING /* diagnostic build (tools/tb_tx_timing.py): workgroup 0 logs the clock after every phase into the first
                     bytes BEHIND the last segment's output (the tool's buffer is that much longer) */
   long long *tlog = reinterpret_cast<long long *>(coded + ((jobs[gridDim.x - 1].out_off + jobs[gridDim.x - 1].E + 15) & ~15ull));
@@ -358,24 +274,18 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
 #endif
   TB_TLOG();
 
-  /* c_r = b[r*(K'-L) ..] || CRC24B (C > 1) || zero fillers (nr_segmentation.c:147-175).  Everything the later phases
-   * read from global memory is requested here, in one go: the segment's bytes, the encoder's edge table (the first part
+  /* ---- requests.  c_r = b[r*(K'-L) ..] || CRC24B (C > 1) || zero fillers (nr_segmentation.c:147-175).  Everything the later
+   * phases read from global memory is requested here, in one go: the segment's bytes, the encoder's edge table (the first part
    * of its phase 0), the eight table seeds and this thread's power of x for the CRC. */
   const uint32_t Kprime = j->Kprime, Lcrc = j->L, segbytes = (Kprime - Lcrc) >> 3, kbytes = (j->K + 7) >> 3;
   const uint8_t *src = scratch + j->b_off + (size_t)j->r * segbytes;
-  uint32_t *tab = reinterpret_cast<uint32_t *>(c + 1056 + 16); /* CRC byte table: the selection area is free until the end */
   const bool with_crc = j->C > 1;
-  /* CRC piece of this thread: bytes [P tid, P tid + P) of the segment, P = the fewest bytes that fit the pieces into ONE wave (the
-   * recurrence over a piece is a chain of dependent table look-ups, but moving a piece's register to the end of the string
-   * costs ~200 VALU instructions per wave that has a piece: the kernel is issue bound when a slot's segments fill the GPU); n_after = bits behind the piece */
-  const uint32_t P = (segbytes + 63u) / 64u < 4u ? 4u : (segbytes + 63u) / 64u;
-  const uint32_t q0 = P * (uint32_t)tid, qn = q0 < segbytes ? (segbytes - q0 < P ? segbytes - q0 : P) : 0u;
-  const uint32_t n_after = 8u * (segbytes - q0 - qn);
+  const tb_tx_crc_piece piece = tb_tx_crc_piece_of(segbytes, (uint32_t)tid);
   uint32_t xq = 0;
   if (with_crc) {
     tb_build_crc_tab(pow24b, tab);
-    if (qn && n_after >= 24u)
-      xq = pow24b[n_after - 24u]; /* x^n_after mod g, left aligned (pow[j] = x^(j + 24) mod g) */
+    if (tb_tx_crc_piece_needs_pow(piece))
+      xq = pow24b[piece.n_after - 24u]; /* x^n_after mod g, left aligned */
   }
   /* the segment that ends the transport block takes the TB CRC from the accumulator the partial-CRC kernel left (and
    * clears it for the next call): no kernel of its own for three bytes per transport block */
@@ -389,8 +299,8 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
   const uint32_t a0 = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u), ndw = (segbytes + 3u) >> 2;
   const uint32_t *__restrict__ src32 = reinterpret_cast<const uint32_t *>(src - a0);
   /* `scratch` is the caller's PAYLOAD array: no dword is touched that does not hold a byte of this transport block (the TB
-   * CRC bytes, which the last segment's share of b ends with, do not exist there: they come from the accumulator below) */
-  const uint32_t src_bytes = crc_len_of(j) ? j->crc_pos : segbytes, last_dw = (a0 + src_bytes + 3u) >> 2;
+   * CRC bytes, which the last segment's share of b ends with, do not exist there: they come from the accumulator above) */
+  const uint32_t src_bytes = crc_len ? crc_pos : segbytes, last_dw = (a0 + src_bytes + 3u) >> 2;
   uint32_t g_lo[5], g_hi[5], g_et[5], g_rp = 0;
 #pragma unroll
   for (int k = 0; k < 5; k++) {
@@ -407,35 +317,18 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
   }
   if (tid <= code->nrows)
     g_rp = (uint32_t)code->row_ptr[tid];
+  /* ---- the LDS image: segment words, edge table, row pointers, zeros */
 #pragma unroll
   for (int k = 0; k < 5; k++) {
     const uint32_t w = (uint32_t)tid + (uint32_t)k * (uint32_t)nt;
-    if (w < ndw) {
-      uint32_t v = __builtin_amdgcn_alignbyte(g_hi[k], g_lo[k], a0);
-#pragma unroll
-      for (int b = 0; b < 4; b++) { /* TB CRC bytes (last segment only); nothing behind the segment's last byte */
-        const uint32_t q = 4u * w + (uint32_t)b, kk = q - crc_pos;
-        if (kk < crc_len)
-          v = (v & ~(0xffu << (8 * b))) | (((tb_crc >> (24 - 8 * kk)) & 0xffu) << (8 * b));
-        if (q >= segbytes)
-          v &= ~(0xffu << (8 * b));
-      }
-      reinterpret_cast<uint32_t *>(c)[w] = v;
-    }
+    if (w < ndw)
+      reinterpret_cast<uint32_t *>(c)[w] = tb_tx_seg_word(g_hi[k], g_lo[k], a0, w, segbytes, crc_pos, crc_len, tb_crc);
     if (w < (uint32_t)code->nedges)
       L.ET[w] = g_et[k];
   }
-  for (uint32_t w = (uint32_t)tid + 5u * (uint32_t)nt; w < ndw; w += nt) { /* (workgroups of fewer than 64 threads: never) */
-    uint32_t v = __builtin_amdgcn_alignbyte(w + 1 < last_dw ? src32[w + 1] : 0u, w < last_dw ? src32[w] : 0u, a0);
-    for (int b = 0; b < 4; b++) {
-      const uint32_t q = 4u * w + (uint32_t)b, kk = q - crc_pos;
-      if (kk < crc_len)
-        v = (v & ~(0xffu << (8 * b))) | (((tb_crc >> (24 - 8 * kk)) & 0xffu) << (8 * b));
-      if (q >= segbytes)
-        v &= ~(0xffu << (8 * b));
-    }
-    reinterpret_cast<uint32_t *>(c)[w] = v;
-  }
+  for (uint32_t w = (uint32_t)tid + 5u * (uint32_t)nt; w < ndw; w += nt) /* (workgroups of fewer than 64 threads: never) */
+    reinterpret_cast<uint32_t *>(c)[w] =
+        tb_tx_seg_word(w + 1 < last_dw ? src32[w + 1] : 0u, w < last_dw ? src32[w] : 0u, a0, w, segbytes, crc_pos, crc_len, tb_crc);
   for (int e = tid + 5 * nt; e < code->nedges; e += nt)
     L.ET[e] = code->enc_et[e];
   if (tid <= code->nrows)
@@ -455,23 +348,9 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
   }
   __syncthreads();
   TB_TLOG();
+  /* ---- CB CRC24B over the segment's bytes in LDS (tb_tx_crc_piece_reg); the pieces meet in red[0] */
   if (with_crc) {
-    /* CB CRC24B over the segment's bytes in LDS: a thread runs the byte-table recurrence of crc_byte.c:184-218 over its
-     * piece, then moves its 24-bit register R to the end of the string: R(x) * x^n_after mod g, one Horner step per
-     * coefficient of R with x^n_after mod g from the power table (one load per thread, requested above).  The first
-     * version looked up one power per set BIT in global memory, one dependent load after the other: 40 % of the kernel. */
-    uint32_t reg = 0;
-    for (uint32_t i = 0; i < qn; i++)
-      reg = (reg << 8) ^ tab[(reg >> 24) ^ c[q0 + i]];
-    uint32_t x = reg;
-    if (qn && n_after) {
-      if (n_after >= 24u) {
-        x = tb_crc_mulmod<24>(reg, xq, 0x80006300u); /* (crc_byte.c:50: poly24b) */
-      } else { /* 8 or 16 bits behind the piece: as many zero bytes through the table */
-        for (uint32_t b = 0; b < n_after; b += 8)
-          x = (x << 8) ^ tab[x >> 24];
-      }
-    }
+    uint32_t x = tb_tx_crc_piece_reg(piece, c, tab, xq);
     for (int off = 32; off; off >>= 1)
       x ^= __shfl_xor(x, off);
     if ((tid & 63) == 0 && x)
@@ -482,6 +361,7 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
     __syncthreads();
   }
   TB_TLOG();
+  /* ---- the encoder: the code word's packed columns L.B */
   if (ldpc_encp32_applies(code)) {
     /* Zc % 32 == 0 (ldpc_enc_packed32.h): the information columns are the segment's dwords with byte and bit order reversed,
      * every produced word goes straight into its periodic string -- no extension phases, three barriers fewer */
@@ -491,7 +371,7 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
       ldpc_encp32_info(L, g32, i, reinterpret_cast<const uint32_t *>(c)[i]);
     __syncthreads();
     TB_TLOG();
-    TB_TLOG();
+    TB_TLOG(); /* (twice: the log's indices are the general path's) */
     ldpc_encp32_lambda(L, g32, tid, nt);
     __syncthreads();
     TB_TLOG();
@@ -504,140 +384,78 @@ __device__ __forceinline__ void tb_tx_fused_body(const tb_tx_seg_job *jobs, cons
     __syncthreads();
     TB_TLOG();
   } else {
-  {
     /* the rest of the encoder's phase 0: information columns from the MSB-first bytes */
     const int kbf = code->kb_full, W = ldpc_encp_W(Z), bs = W + 1, nin = (kbf * Z + 7) >> 3;
     for (int i = tid; i < kbf * W; i += nt) {
       const int col = i / W, w = i - col * W;
-      const uint32_t b0 = (uint32_t)(col * Z + 32 * w), j0 = b0 >> 3;
-      uint64_t v = 0;
-      for (int q = 0; q < 5; q++)
-        v = (v << 8) | ((int)j0 + q < nin ? c[j0 + q] : 0u);
-      const uint32_t m = (uint32_t)(v >> (8 - (b0 & 7u)));
-      L.B[col * bs + w] = __builtin_bitreverse32(m) & ldpc_encp_mask(Z, w);
+      L.B[col * bs + w] = tb_tx_info_word(c, nin, Z, col, w);
     }
-  }
-  __syncthreads();
-  TB_TLOG();
-  for (int ph = 1; ph <= 3; ph++) {
-    ldpc_encp_phase(ph, code, ej->Kb, c, L, nullptr, tid, nt);
+    __syncthreads();
+    TB_TLOG();
+    for (int ph = 1; ph <= 3; ph++) {
+      ldpc_encp_phase(ph, code, ej->Kb, c, L, nullptr, tid, nt);
+      __syncthreads();
+      TB_TLOG();
+    }
+    /* phases 4 .. 11 -- the four core parity columns, one after the other, W <= 12 items each: ONE wave walks them without
+     * workgroup barriers (ldpc_encp_core_parity_wave), the others wait at the barrier below.  Eight barrier-separated phases of 12 active lanes were 10 k of the kernel's 62 k clocks. */
+    if (tid < 64)
+      ldpc_encp_core_parity_wave(code, L, tid);
+    __syncthreads();
+    TB_TLOG();
+    ldpc_encp_phase(12, code, ej->Kb, c, L, nullptr, tid, nt);
     __syncthreads();
     TB_TLOG();
   }
-  /* phases 4 .. 11 -- the four core parity columns, one after the other, W <= 12 items each: ONE wave walks them without
-   * workgroup barriers (ldpc_encp_core_parity_wave), the others wait at the barrier below.  Eight barrier-separated phases of 12 active lanes were 10 k of the kernel's 62 k clocks. */
-  if (tid < 64)
-    ldpc_encp_core_parity_wave(code, L, tid);
-  __syncthreads();
-  TB_TLOG();
-  ldpc_encp_phase(12, code, ej->Kb, c, L, nullptr, tid, nt);
-  __syncthreads();
-  TB_TLOG();
-  }
-  /* Bit selection + interleaving (nr_rate_matching.c:424-501, :240-303): f[i + jj*Qm] = e[i*E/Qm + jj],
-   * e[k] = d[position of rank (rank0 + k) mod V], d[p] = code word bit p + 2Z.  In two steps per chunk of TB_TX_SEL_SYMS
-   * modulation symbols: (1) the Qm sub-streams e[i*E/Qm + jj0 ..] are packed into LDS, 32 bits per item, gathered from
-   * the code word in runs (a run ends at the circular buffer's wrap, at the filler gap, at the end of a lifted column);
-   * (2) one thread per 8 symbols: a byte of every sub-stream in, 8 Qm output bytes out (tb_tx_store_syms).  (The first version stored one byte per thread and bit, strided by Qm: 1664 segments x 9450 one-byte
-   * stores were most of the kernel's 50 us.) */
+  /* ---- bit selection + interleaving, in two steps per chunk of TB_TX_SEL_SYMS modulation symbols: (1) the Qm sub-streams
+   * e[i*E/Qm + jj0 ..] are packed into LDS, 32 bits per item (tb_tx_sel_chunk); (2) the chunk's store: one thread per 8 symbols,
+   * a byte of every sub-stream in, 8 Qm output bytes out (tb_tx_store_syms), or the packed words, or the points.  (The first
+   * version stored one byte per thread and bit, strided by Qm: 1664 segments x 9450 one-byte stores were most of the
+   * kernel's 50 us.) */
   uint8_t *__restrict__ f = coded + j->out_off;
-  const uint32_t E = j->E, Qm = j->Qm, EQ = E / Qm, V = j->V, rank0 = j->rank0, Foffset = j->Foffset, Fin = j->Fin;
-  const uint32_t z_magic = 0xffffffffu / (uint32_t)Z + 1u, bs = (uint32_t)ldpc_encp_W(Z) + 1u, twoZ = 2u * (uint32_t)Z;
-  const uint32_t v_magic = V > 1u ? 0xffffffffu / V + 1u : 0u; /* (V = 1: every rank is 0) */
-  uint32_t *sel = reinterpret_cast<uint32_t *>(c + 1056 + 16); /* [Qm][TB_TX_SEL_SYMS / 32 + 1], behind the segment bytes */
-  const uint32_t sel_stride = TB_TX_SEL_SYMS / 32 + 1;
-  uint32_t *seq = sel + 8 * sel_stride, *carry = seq + TB_TX_SCR_WORDS; /* scrambled launch only: TB_TX_FUSED_SCR_LDS */
-  for (uint32_t jj0 = 0; jj0 < EQ; jj0 += TB_TX_SEL_SYMS) {
-    const uint32_t nsym = EQ - jj0 < TB_TX_SEL_SYMS ? EQ - jj0 : TB_TX_SEL_SYMS, nw = (nsym + 31) >> 5;
-    if constexpr (SCR) { /* the chunk's sequence words, generated while the sub-streams are gathered */
-      const uint32_t b_lo = j->bit_off + jj0 * Qm, b_hi = b_lo + nsym * Qm;
+  const tb_tx_sel_geom sg = tb_tx_sel_geometry(j, Z);
+  const uint32_t Qm = sg.Qm;
+  uint32_t *const sel = T.sel, *const seq = T.seq;
+  const uint32_t sel_stride = TB_TX_SEL_STRIDE;
+  for (uint32_t jj0 = 0; jj0 < sg.EQ; jj0 += TB_TX_SEL_SYMS) {
+    const uint32_t nsym = sg.EQ - jj0 < TB_TX_SEL_SYMS ? sg.EQ - jj0 : TB_TX_SEL_SYMS;
+    const uint32_t b_lo = j->bit_off + jj0 * Qm, b_hi = b_lo + nsym * Qm; /* the chunk's codeword bits (SCR) */
+    if constexpr (SCR) /* the chunk's sequence words, generated while the sub-streams are gathered */
       tb_rx_scr_fill(seq, j->c_init, b_lo >> 5, ((b_hi + 31u) >> 5) - (b_lo >> 5));
-    }
-    for (uint32_t it = tid; it < Qm * nw; it += nt) {
-      const uint32_t i = it / nw, w = it - i * nw;
-      const uint32_t k = i * EQ + jj0 + 32u * w;
-      uint32_t nbits = nsym - 32u * w;
-      nbits = nbits > 32u ? 32u : nbits;
-      /* (rank0 + k) mod V without a division: quotient from the reciprocal, off by one at most either way */
-      const uint32_t x = rank0 + k, q = __umulhi(x, v_magic);
-      uint32_t r = x - q * V, v = 0, filled = 0;
-      r += (int32_t)r < 0 ? V : 0u;
-      r -= r >= V ? V : 0u;
-      r = V == 1u ? 0u : r;
-      while (filled < nbits) {
-        const uint32_t p = (r < Foffset ? r : r + Fin) + twoZ;
-        const uint32_t col = __umulhi(p, z_magic), t = p - col * (uint32_t)Z;
-        uint32_t n = nbits - filled;
-        n = n < V - r ? n : V - r;
-        if (r < Foffset)
-          n = n < Foffset - r ? n : Foffset - r;
-        n = n < (uint32_t)Z - t ? n : (uint32_t)Z - t;
-        uint32_t chunk = ldpc_bits_at(L.B + col * bs, t);
-        if (n < 32u)
-          chunk &= (1u << n) - 1u;
-        v |= chunk << filled;
-        filled += n;
-        r += n;
-        r = r >= V ? r - V : r;
-      }
-      sel[i * sel_stride + w] = v;
-    }
+    tb_tx_sel_chunk(sg, L.B, jj0, nsym, sel, sel_stride, tid, nt);
 #ifndef TB_TX_SYM_TAB_CONST /* (defined: the A/B variant that looks the points up in constant memory) */
     if constexpr (SYM) {
       if (jj0 == 0) /* the constellation behind the sequence words, once (published by the barrier below) */
         for (uint32_t x = tid; x < (1u << Qm); x += nt)
-          seq[TB_TX_SCR_WORDS + x] = nr_qam_tab_tx.pt[nr_qam_table_off(Qm) + x];
+          T.behind[x] = nr_qam_tab_tx.pt[nr_qam_table_off(Qm) + x];
     }
 #endif
     __syncthreads();
     TB_TLOG();
     if constexpr (SYM) { /* one thread per symbol: plane s mod Nl, entry s div Nl of the TB's record */
-      const uint32_t b_lo = j->bit_off + jj0 * Qm;
       const tb_tx_sym_chunk ch{sel, sel_stride, seq, b_lo & 31u, j->bit_off / Qm + jj0, j->Nl, j->plane};
-      uint32_t *out32 = reinterpret_cast<uint32_t *>(f);
 #ifdef TB_TX_SYM_TAB_CONST
-      const uint32_t *tab = nr_qam_tab_tx.pt + nr_qam_table_off(Qm);
+      const uint32_t *pts = nr_qam_tab_tx.pt + nr_qam_table_off(Qm);
 #else
-      const uint32_t *tab = seq + TB_TX_SCR_WORDS;
+      const uint32_t *pts = T.behind;
 #endif
-      switch (Qm) {
-        case 2: tb_tx_sym_store<2>(ch, tab, nsym, out32, tid, nt); break;
-        case 4: tb_tx_sym_store<4>(ch, tab, nsym, out32, tid, nt); break;
-        case 6: tb_tx_sym_store<6>(ch, tab, nsym, out32, tid, nt); break;
-        default: tb_tx_sym_store<8>(ch, tab, nsym, out32, tid, nt); break;
-      }
-      __syncthreads();
-      TB_TLOG();
-      continue;
-    }
-    if constexpr (SCR) {
-      const uint32_t b_lo = j->bit_off + jj0 * Qm, b_hi = b_lo + nsym * Qm, k = jj0 / TB_TX_SEL_SYMS;
-      const bool last_chunk = jj0 + nsym == EQ;
-      uint32_t *out32 = reinterpret_cast<uint32_t *>(f);
-      switch (Qm) {
-        case 1: tb_tx_store_scr<1>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
-        case 2: tb_tx_store_scr<2>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
-        case 4: tb_tx_store_scr<4>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
-        case 6: tb_tx_store_scr<6>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
-        default: tb_tx_store_scr<8>(j, sel, sel_stride, seq, carry, k, b_lo, b_hi, last_chunk, out32, tickets, parts, tid, nt); break;
-      }
-      __syncthreads();
-      TB_TLOG();
-      continue;
-    }
-    /* output bytes [jj0 Qm, (jj0 + nsym) Qm) of the segment */
-    uint8_t *dst = f + (size_t)jj0 * Qm;
-    switch (Qm) {
-      case 1: tb_tx_store_syms<1>(sel, sel_stride, nsym, dst, tid, nt); break;
-      case 2: tb_tx_store_syms<2>(sel, sel_stride, nsym, dst, tid, nt); break;
-      case 4: tb_tx_store_syms<4>(sel, sel_stride, nsym, dst, tid, nt); break;
-      case 6: tb_tx_store_syms<6>(sel, sel_stride, nsym, dst, tid, nt); break;
-      case 8: tb_tx_store_syms<8>(sel, sel_stride, nsym, dst, tid, nt); break;
-      default: /* (no such modulation in NR; kept correct) */
-        for (uint32_t m = tid; m < nsym * Qm; m += nt) {
-          const uint32_t sy = m / Qm, i = m - sy * Qm;
-          dst[m] = (uint8_t)((sel[i * sel_stride + (sy >> 5)] >> (sy & 31u)) & 1u);
-        }
+      auto store = [&](auto qm) { tb_tx_sym_store<decltype(qm)::value>(ch, pts, nsym, reinterpret_cast<uint32_t *>(f), tid, nt); };
+      if (!tb_tx_for_qm<2, 4, 6>(Qm, store))
+        store(tb_tx_qm<8>{});
+    } else if constexpr (SCR) {
+      const uint32_t k = jj0 / TB_TX_SEL_SYMS;
+      const bool last_chunk = jj0 + nsym == sg.EQ;
+      auto store = [&](auto qm) {
+        tb_tx_store_scr<decltype(qm)::value>(j, sel, sel_stride, seq, T.behind, k, b_lo, b_hi, last_chunk, reinterpret_cast<uint32_t *>(f),
+                                             tickets, parts, tid, nt);
+      };
+      if (!tb_tx_for_qm<1, 2, 4, 6>(Qm, store))
+        store(tb_tx_qm<8>{});
+    } else {
+      uint8_t *dst = f + (size_t)jj0 * Qm; /* output bytes [jj0 Qm, (jj0 + nsym) Qm) of the segment */
+      auto store = [&](auto qm) { tb_tx_store_syms<decltype(qm)::value>(sel, sel_stride, nsym, dst, tid, nt); };
+      if (!tb_tx_for_qm<1, 2, 4, 6, 8>(Qm, store))
+        tb_tx_store_syms_any(Qm, sel, sel_stride, nsym, dst, tid, nt);
     }
     __syncthreads();
     TB_TLOG();
@@ -800,29 +618,20 @@ hipError_t tb_launch_tx_ratematch(const tb_tx_seg_job *jobs, uint32_t n, const u
 {
   TB_LAUNCH(tb_tx_ratematch_kernel, n, s, jobs, scratch, coded);
 }
-hipError_t tb_launch_tx_fused(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
-                              const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, hipStream_t s)
+hipError_t tb_launch_tx_fused(tb_tx_out mode, const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, uint32_t n, int n_threads, int enc_lds,
+                              const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets,
+                              uint32_t *parts, hipStream_t s)
 {
   if (n == 0)
     return hipSuccess;
-  hipLaunchKernelGGL(tb_tx_fused_kernel, dim3(n), dim3(n_threads), lds_bytes, s, jobs, ejobs, scratch, coded, pow24b, acc);
-  return hipGetLastError();
-}
-hipError_t tb_launch_tx_fused_scr(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
-                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, uint32_t *tickets,
-                                  uint32_t *parts, hipStream_t s)
-{
-  if (n == 0)
-    return hipSuccess;
-  hipLaunchKernelGGL(tb_tx_fused_scr_kernel, dim3(n), dim3(n_threads), lds_bytes, s, jobs, ejobs, scratch, coded, pow24b, acc, tickets, parts);
-  return hipGetLastError();
-}
-hipError_t tb_launch_tx_fused_sym(const tb_tx_seg_job *jobs, const ldpc_enc_job *ejobs, uint32_t n, int n_threads, int lds_bytes,
-                                  const uint8_t *scratch, uint8_t *coded, const uint32_t *pow24b, uint32_t *acc, hipStream_t s)
-{
-  if (n == 0)
-    return hipSuccess;
-  hipLaunchKernelGGL(tb_tx_fused_sym_kernel, dim3(n), dim3(n_threads), lds_bytes, s, jobs, ejobs, scratch, coded, pow24b, acc);
+  const dim3 grid(n), block(n_threads);
+  const size_t lds = (size_t)enc_lds + TB_TX_FUSED_EXTRA_LDS;
+  if (mode == TB_TX_OUT_SYMBOLS)
+    hipLaunchKernelGGL(tb_tx_fused_sym_kernel, grid, block, lds + TB_TX_FUSED_SYM_LDS, s, jobs, ejobs, scratch, coded, pow24b, acc);
+  else if (mode == TB_TX_OUT_PACKED)
+    hipLaunchKernelGGL(tb_tx_fused_scr_kernel, grid, block, lds + TB_TX_FUSED_SCR_LDS, s, jobs, ejobs, scratch, coded, pow24b, acc, tickets, parts);
+  else
+    hipLaunchKernelGGL(tb_tx_fused_kernel, grid, block, lds, s, jobs, ejobs, scratch, coded, pow24b, acc);
   return hipGetLastError();
 }
 hipError_t tb_launch_rx_dematch(const tb_rx_seg_job *jobs, uint32_t n, uint32_t lds_elems, const int16_t *llr, int16_t *harq,

@@ -188,10 +188,9 @@ int offload_encode(const uint8_t *in, uint8_t *out, const encoder_implemparams_t
     return -1;
   int nthr, nlds;
   ldpc_enc_launch_shape(hc, &nthr, &nlds);
-  HIP_TRY(tb_launch_tx_fused(reinterpret_cast<const tb_tx_seg_job *>(c.jobs_d.p + o_seg),
-                             reinterpret_cast<const ldpc_enc_job *>(c.jobs_d.p + o_enc), 1, 512, nlds + TB_TX_FUSED_EXTRA_LDS,
-                             c.jobs_d.p + o_in, c.io_coded.p, G().crc_pow[NR_HIP_CRC24_B],
-                             reinterpret_cast<uint32_t *>(c.jobs_d.p + o_acc), s));
+  HIP_TRY(tb_launch_tx_fused(TB_TX_OUT_BYTES, reinterpret_cast<const tb_tx_seg_job *>(c.jobs_d.p + o_seg),
+                             reinterpret_cast<const ldpc_enc_job *>(c.jobs_d.p + o_enc), 1, 512, nlds, c.jobs_d.p + o_in, c.io_coded.p,
+                             G().crc_pow[NR_HIP_CRC24_B], reinterpret_cast<uint32_t *>(c.jobs_d.p + o_acc), nullptr, nullptr, s));
   /* (the caller's array never meets the runtime's copy functions: TbCtx::fin_copies) */
   if (c.coded_h.ensure(ip->E) != 0)
     return -1;

@@ -9,6 +9,7 @@
  * proves nothing about barriers, LDS sizes or wave intrinsics -- the `-m gpu` tests do that.
  */
 #include <cstdint>
+#include <algorithm>
 #include <cstring>
 #include <vector>
 #include "../../openairinterface5g_amd/csrc/ldpc_enc_core.h"
@@ -158,20 +159,9 @@ extern "C" int ldpc_emul_encode_packed(int BG, int Zc, int Kb, const uint8_t *in
  * are loops here.  -2: the code does not take this path. */
 #include "../../openairinterface5g_amd/csrc/ldpc_enc_packed32.h"
 
-extern "C" int ldpc_emul_encode_packed32(int BG, int Zc, int Kb, const uint8_t *in, uint8_t *out, int nt)
+/* the code word's packed columns L.B from the block's input bytes, nt threads */
+static void emul_encp32_solve(const ldpc_code_desc_t *code, const ldpc_encp_lds &L, const ldpc_encp32 &g, const uint8_t *in, int nt)
 {
-  ldpc_code_desc_t code_s;
-  if (ldpc_build_code_desc(BG, Zc, BG == 1 ? 13 : 15, &code_s) != 0)
-    return -1;
-  const ldpc_code_desc_t *code = &code_s;
-  if (!ldpc_encp32_applies(code))
-    return -2;
-  std::vector<uint32_t> lds(ldpc_encp_lds_words(code->ncols, code->kb_full, Zc, code->nrows, code->nedges), 0x5a5a5a5au);
-  ldpc_encp_lds L;
-  ldpc_encp_carve(lds.data(), code, L);
-  if (nt <= 0)
-    nt = ldpc_encp_threads(code->nrows, Zc);
-  const ldpc_encp32 g = ldpc_encp32_make(code, Kb);
   const uint32_t nd = (uint32_t)(g.kbf * g.W);
   std::vector<uint32_t> in32(nd);
   memcpy(in32.data(), in, (size_t)nd * 4);
@@ -196,6 +186,23 @@ extern "C" int ldpc_emul_encode_packed32(int BG, int Zc, int Kb, const uint8_t *
     ldpc_encp32_core_step_rest(code, L, g, lane);
   for (int tid = 0; tid < nt; tid++)
     ldpc_encp32_extension(code, L, g, tid, nt);
+}
+
+extern "C" int ldpc_emul_encode_packed32(int BG, int Zc, int Kb, const uint8_t *in, uint8_t *out, int nt)
+{
+  ldpc_code_desc_t code_s;
+  if (ldpc_build_code_desc(BG, Zc, BG == 1 ? 13 : 15, &code_s) != 0)
+    return -1;
+  const ldpc_code_desc_t *code = &code_s;
+  if (!ldpc_encp32_applies(code))
+    return -2;
+  std::vector<uint32_t> lds(ldpc_encp_lds_words(code->ncols, code->kb_full, Zc, code->nrows, code->nedges), 0x5a5a5a5au);
+  ldpc_encp_lds L;
+  ldpc_encp_carve(lds.data(), code, L);
+  if (nt <= 0)
+    nt = ldpc_encp_threads(code->nrows, Zc);
+  const ldpc_encp32 g = ldpc_encp32_make(code, Kb);
+  emul_encp32_solve(code, L, g, in, nt);
   std::vector<uint8_t> o2((size_t)(code->ncols - 2) * Zc + 32); /* (the stores are 16 bytes wide and want alignment) */
   uint8_t *oa = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(o2.data()) + 15) & ~(uintptr_t)15);
   for (int tid = 0; tid < nt; tid++)
@@ -453,4 +460,54 @@ extern "C" int tb_emul_first_tx_columns(uint32_t Tbslbrm, int BG, uint32_t Zc, u
   if (nr_hip_rate_match_geometry(Tbslbrm, BG, Zc, C, F, K, rv, E, &rm) != 0)
     return -1;
   return (int)nr_hip_first_tx_columns(&rm, E, Zc);
+}
+
+/* ---- DL: bit selection + interleaving of one segment (tb_tx_core.h: the fused TX kernel's gather and its byte store) ---------
+ * The code word's packed columns come from the encoder phases above (the kernel's own per Zc), then every selection chunk of
+ * `chunk` modulation symbols (the kernel: TB_TX_SEL_SYMS; a multiple of 32) is gathered and stored, the workgroup's nt threads
+ * walked one after another; the sub-stream area is poisoned before every chunk.  seg = the segment's K/8 bytes (fillers zero),
+ * f = its E output bytes.  Returns the chunks run, -1 on invalid parameters. */
+#include "../../openairinterface5g_amd/csrc/tb_tx_core.h"
+
+extern "C" int tb_emul_tx_select(uint32_t Tbslbrm, int BG, uint32_t Zc, uint32_t C, uint32_t F, int Kb, int rv, uint32_t E, uint32_t Qm,
+                                 uint32_t chunk, int nt, const uint8_t *seg, uint8_t *f)
+{
+  ldpc_code_desc_t code_s;
+  nr_hip_rm_t rm;
+  const uint32_t K = (BG == 1 ? 22u : 10u) * Zc;
+  if (chunk == 0 || chunk % 32 || nt < 1 || (Qm != 2 && Qm != 4 && Qm != 6 && Qm != 8) || E == 0 || E % Qm ||
+      nr_hip_rate_match_geometry(Tbslbrm, BG, Zc, C, F, K, rv, E, &rm) != 0 || ldpc_build_code_desc(BG, (int)Zc, BG == 1 ? 13 : 15, &code_s) != 0)
+    return -1;
+  const ldpc_code_desc_t *code = &code_s;
+  std::vector<uint32_t> lds(ldpc_encp_lds_words(code->ncols, code->kb_full, (int)Zc, code->nrows, code->nedges), 0x5a5a5a5au);
+  ldpc_encp_lds L;
+  ldpc_encp_carve(lds.data(), code, L);
+  if (ldpc_encp32_applies(code)) {
+    for (int col = 0; col < code->ncols; col++) /* (the kernel's LDS image stage: the word behind every column) */
+      L.B[col * (ldpc_encp_W((int)Zc) + 1) + ldpc_encp_W((int)Zc)] = 0u;
+    emul_encp32_solve(code, L, ldpc_encp32_make(code, Kb), seg, nt);
+  } else {
+    for (int ph = 0; ph < LDPC_ENCP_SOLVE_PHASES; ph++)
+      for (int tid = 0; tid < nt; tid++)
+        ldpc_encp_phase(ph, code, Kb, seg, L, nullptr, tid, nt);
+  }
+  tb_tx_seg_job j;
+  memset(&j, 0, sizeof(j));
+  j.E = E; j.Qm = Qm; j.Foffset = rm.Foffset; j.Fin = rm.Fin; j.V = rm.V; j.rank0 = rm.rank0;
+  const tb_tx_sel_geom g = tb_tx_sel_geometry(&j, (int)Zc);
+  const uint32_t sel_stride = chunk / 32 + 1;
+  std::vector<uint32_t> sel(8 * sel_stride);
+  int chunks = 0;
+  for (uint32_t jj0 = 0; jj0 < g.EQ; jj0 += chunk, chunks++) {
+    const uint32_t nsym = g.EQ - jj0 < chunk ? g.EQ - jj0 : chunk;
+    std::fill(sel.begin(), sel.end(), 0x5a5a5a5au);
+    for (int tid = 0; tid < nt; tid++)
+      tb_tx_sel_chunk(g, L.B, jj0, nsym, sel.data(), sel_stride, tid, nt);
+    uint8_t *dst = f + (size_t)jj0 * Qm;
+    for (int tid = 0; tid < nt; tid++) {
+      auto store = [=](auto qm) { tb_tx_store_syms<decltype(qm)::value>(sel.data(), sel_stride, nsym, dst, tid, nt); };
+      tb_tx_for_qm<2, 4, 6, 8>(Qm, store);
+    }
+  }
+  return chunks;
 }

@@ -215,3 +215,56 @@ def test_rx_dematch_first_round_clear_does_not_follow_the_cut(emul):
                         beyond += clear and max(Ncb, nc * Z - 2 * Z) < np_mode
     assert cases > 700 and cut > 50 and beyond > 50, (cases, cut, beyond)
 
+
+
+def test_tx_select_phases_against_the_oracle(emul):
+    """tb_tx_core.h (the fused DL segment kernel's bit selection and its byte store), a workgroup's threads walked chunk by
+    chunk over the code word the emulated encoder phases leave packed in LDS: the segment's E output bytes equal the oracle's
+    encode -> nr_rate_matching_ldpc -> nr_interleaving_ldpc bit for bit, and nothing around them is written.  Zc = 6 (one word
+    per column), 36 (two, the second partial), 32 and 64 (the word-aligned encoder path); both base graphs, Kb < 10; fillers
+    (the gap falls inside a 32-bit item); rv 0-3; LBRM (Ncb < N); E below Ncb, a little above it and above 2 V (several laps,
+    the wrap inside an item); every Qm; E/Qm = 1, 31, 32, 33, 65 against chunks of 32 and 64 symbols (a partial last word,
+    three chunks); all four alignments of the output.  A combination the reference refuses (Foffset > E) must be refused."""
+    emul.tb_emul_tx_select.argtypes = [C.c_uint32, C.c_int] + [C.c_uint32] * 3 + [C.c_int, C.c_int] + [C.c_uint32] * 3 + [C.c_int] + [C.c_void_p] * 2
+    rng = np.random.default_rng(2024)
+    seen = dict(ok=0, refused=0, lbrm=0, below=0, above=0, laps=0, one=0, three=0, partial=0)
+    for BG, Z, Kb, F in ((1, 6, 22, 0), (1, 6, 22, 8), (1, 36, 22, 0), (1, 36, 22, 40), (1, 32, 22, 24), (1, 64, 22, 0), (1, 64, 22, 56),
+                         (2, 6, 10, 0), (2, 6, 6, 46), (2, 36, 8, 88), (2, 32, 10, 8), (2, 32, 9, 48), (2, 64, 6, 296), (2, 64, 10, 0)):
+        K, N = kbits(BG, Z), (66 if BG == 1 else 50) * Z
+        assert F >= K - Kb * Z
+        bits = rng.integers(0, 2, K, dtype=np.uint8)
+        bits[K - F:] = 0
+        seg = np.packbits(np.concatenate([bits, np.zeros((-K) % 8, np.uint8)]))
+        d = O.encode(BG, Z, seg, Kb).copy()
+        Foffset = K - F - 2 * Z
+        d[Foffset:Foffset + F] = 2                                   # NR_NULL (nr_dlsch_coding.c:177-180)
+        for lbrm in (0, (2 * (K + Z + 5) + 2) // 3):                 # Ncb = N; Ncb = K + Z + 5 or so, inside a column
+            Ncb = N if not lbrm else min(N, 3 * lbrm // 2)
+            V = Ncb - F
+            for Qm in (2, 4, 6, 8):
+                sizes = [Qm * n for n in (1, 31, 32, 33, 65)] + [int(0.6 * V) // Qm * Qm, (Ncb + 3 * Qm) // Qm * Qm, (2 * V + 37 + Qm) // Qm * Qm]
+                for E in sizes:
+                    for rv in range(4):
+                        rc, e = O.rate_match(lbrm, BG, Z, d, 1, F, Foffset, rv, E)
+                        for chunk, nt in ((32, 5), (64, 64)):
+                            out = np.full(E + 16, 0x77, np.uint8)
+                            got = out[4 + rv:4 + rv + E]              # the output's alignment decides the store width
+                            n = emul.tb_emul_tx_select(lbrm, BG, Z, 1, F, Kb, rv, E, Qm, chunk, nt, seg.ctypes.data, got.ctypes.data)
+                            key = (BG, Z, Kb, F, lbrm, Qm, E, rv, chunk)
+                            if rc != 0:
+                                assert n == -1 and (out == 0x77).all(), key
+                                seen["refused"] += 1
+                                continue
+                            assert n == -(-(E // Qm) // chunk), key
+                            assert np.array_equal(got, O.interleave(E, Qm, e)), key
+                            assert (out[:4 + rv] == 0x77).all() and (out[4 + rv + E:] == 0x77).all(), key
+                            seen["ok"] += 1
+                            seen["lbrm"] += Ncb < N
+                            seen["below"] += E < Ncb
+                            seen["above"] += Ncb < E < 2 * V
+                            seen["laps"] += E > 2 * V
+                            seen["one"] += E == Qm
+                            seen["three"] += n == 3
+                            seen["partial"] += (E // Qm) % 32 != 0
+    assert all(v > 0 for v in seen.values()), seen
+    assert seen["ok"] > 3000, seen
