@@ -240,6 +240,12 @@ struct TbCtx {
   bool pending = false;
   void drain() /* nothing of this thread's stays in flight (error paths, thread exit) */
   {
+    /* A DEVICE mem call's upload is queued on the caller's stream (`last`), which nothing below waits for: the page-locked job
+     * area must not change hands -- this thread's next call after an error, or the next thread that takes the context from the
+     * pool and calls on the same stream -- while a queued copy has yet to read it.  An event wait, not a stream wait: the
+     * caller may have destroyed its stream since. */
+    if (pending && uploaded)
+      (void)hipEventSynchronize(uploaded);
     if (aux)
       (void)hipStreamSynchronize(aux);
     for (hipStream_t q : side)
