@@ -295,6 +295,13 @@ static const CodeEntry *get_code_impl(int BG, int Z, int R, int ri)
     set_error("invalid (BG, Z, R)");
     return nullptr;
   }
+  /* Every caller asks the THROUGHPUT descriptor whether the fast kernel serves the code and then launches whichever shape the
+   * call size picks; the latency shape's users (the resident server above all) count on what that shape always has, staged
+   * extension LLRs among it.  The builder may give up one shape alone -- a forced knob value whose LDS no longer fits:
+   * NRLDPC_HIP_BN_SHORT=30 pads BG1 Zc = 384 R = 1/3 past 160 KiB with the extension LLRs staged -- and a shape it gave up must
+   * never be launched, nor may the other one stand in for it: the fast section is then off for the code (generic kernel). */
+  if (!ce->host.f_ok || !ce->host_lat.f_ok)
+    ce->host.f_ok = ce->host_lat.f_ok = 0;
   static const int multi_env = [] { const char *v = getenv("NRLDPC_HIP_MULTI"); return v ? atoi(v) : -1; }(); /* 0: off, n: force n per workgroup */
   ce->host_multi.f_ok = 0;
   if (multi_env != 0) {
@@ -874,9 +881,11 @@ int32_t nrLDPC_hip_lds_bytes(int BG, int Z, int R)
 
 int32_t nrLDPC_hip_code_info(int BG, int Z, int R, int32_t info[8])
 {
-  static thread_local ldpc_code_desc_t d;
-  if (!info || ldpc_build_code_desc(BG, Z, R, &d) != 0)
+  static thread_local ldpc_code_desc_t d, dl;
+  if (!info || ldpc_build_code_desc(BG, Z, R, &d) != 0 || ldpc_build_code_desc_shape(BG, Z, R, LDPC_SHAPE_LATENCY, &dl) != 0)
     return -1;
+  if (!dl.f_ok)
+    d.f_ok = 0; /* (get_code_impl: a code is served by the fast kernel in both shapes or not at all) */
   info[0] = d.nrows; info[1] = d.ncols; info[2] = d.nedges; info[3] = d.f_ok;
   info[4] = d.f_ok ? d.f_n_threads : d.n_threads;
   info[5] = d.f_ok ? d.f_lds_total : d.lds_total;

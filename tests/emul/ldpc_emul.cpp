@@ -212,6 +212,23 @@ extern "C" int ldpc_emul_encode_packed32(int BG, int Zc, int Kb, const uint8_t *
 }
 
 extern "C" int ldpc_emul_desc(int BG, int Z, int R, ldpc_code_desc_t *d) { return ldpc_build_code_desc(BG, Z, R, d); }
+/* the descriptor of either workgroup shape (ldpc_graph.h LDPC_SHAPE_*) and its size, for byte-wise comparisons
+ * (tests/switch_knobs.py) */
+extern "C" int ldpc_emul_desc_shape(int BG, int Z, int R, int shape, ldpc_code_desc_t *d)
+{
+  return ldpc_build_code_desc_shape(BG, Z, R, shape, d);
+}
+extern "C" int ldpc_emul_desc_size(void) { return (int)sizeof(ldpc_code_desc_t); }
+/* what the schedule knobs move: {f_ok, threads, LDS bytes, check-node tasks, bit-node tickets, ext_global, pair19, workgroups per CU} */
+extern "C" int ldpc_emul_fast_info(int BG, int Z, int R, int shape, int *info)
+{
+  ldpc_code_desc_t d;
+  if (ldpc_build_code_desc_shape(BG, Z, R, shape, &d) != 0)
+    return -1;
+  info[0] = d.f_ok; info[1] = d.f_n_threads; info[2] = d.f_lds_total; info[3] = d.f_n_cn_tasks; info[4] = d.f_n_bn_tickets;
+  info[5] = d.f_ext_global; info[6] = d.f_pair19; info[7] = d.f_wg_per_cu;
+  return 0;
+}
 
 /* ---- fast kernel (ldpc_decoder_fast.hip) ---------------------------------------------------------------- */
 #include "../../openairinterface5g_amd/csrc/ldpc_dec_fast_core.h"
