@@ -96,8 +96,10 @@ EXPORTS = ["LDPCinit", "LDPCshutdown", "LDPCdecoder", "LDPCencoder", "ldpc_check
 _lib = None
 
 
-def load_library(path=None):
-    """dlopen libldpc_hip.so (the analogue of load_LDPClib, nrLDPC_load.c:45-75). Raises if it is missing."""
+def load_library(path=None, mode=None):
+    """dlopen libldpc_hip.so (the analogue of load_LDPClib, nrLDPC_load.c:45-75). Raises if it is missing.
+    mode: dlopen flags of the first load (default RTLD_NOW | RTLD_GLOBAL; the reference's loader uses
+    RTLD_LAZY | RTLD_NODELETE | RTLD_GLOBAL, load_module_shlib.c:160)."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -105,7 +107,7 @@ def load_library(path=None):
     if not p.exists():
         raise RuntimeError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C {_PKG / 'csrc'}` -- there is no CPU fallback")
-    L = C.CDLL(str(p), mode=os.RTLD_NOW | os.RTLD_GLOBAL)
+    L = C.CDLL(str(p), mode=os.RTLD_NOW | os.RTLD_GLOBAL if mode is None else mode)
     L.LDPCinit.restype = C.c_int32
     L.LDPCshutdown.restype = C.c_int32
     L.LDPCdecoder.restype = C.c_int32
@@ -252,16 +254,19 @@ T2_EXPORTS = ["LDPCinit", "LDPCshutdown", "LDPCdecoder", "LDPCencoder", "ldpc_ch
 _t2 = None
 
 
-def load_offload_library():
+def load_offload_library(mode=None, alone=False):
     """dlopen libldpc_hip_t2.so the way load_LDPClib("_t2", &ldpc_interface_offload) does (nr_init.c:138-139,
-    nrLDPC_load.c:45-75) and run its LDPCinit.  Raises if the library is missing or no GPU is usable."""
+    nrLDPC_load.c:45-75) and run its LDPCinit.  Raises if the library is missing or no GPU is usable.
+    mode: dlopen flags of the first load (default: ctypes' own); alone: do not load libldpc_hip.so first -- it then comes
+    in through the offload library's DT_NEEDED entry and $ORIGIN, as in a process that uses the offload slot only."""
     global _t2
     if _t2 is None:
-        load_library()
+        if not alone:
+            load_library()
         path = Path(os.environ.get("NRLDPC_HIP_T2_LIB", Path(LIB_PATH).parent / "libldpc_hip_t2.so"))
         if not path.exists():
             raise RuntimeError(f"{path} not found: run `python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
-        L = C.CDLL(str(path))
+        L = C.CDLL(str(path)) if mode is None else C.CDLL(str(path), mode=mode)
         for name in T2_EXPORTS:
             getattr(L, name)
         L.LDPCdecoder.restype = C.c_int32

@@ -6,6 +6,8 @@
  *
  *   gcc -O2 -I include tests/abi_threads.c -o abi_threads -ldl -lpthread
  *   ./abi_threads <path/libldpc_hip.so> <threads> <calls per thread> [case]
+ * ABI_DUMP=<file>: the single-threaded answers the threads are held against go into <file> (abi_cases.h), where the tests
+ * compare them with the oracle.
  * With a case index every call uses that one case (1 = BG1 Zc=384 R=1/3 at high SNR, 2 passes: the per-call latency
  * figure that corresponds to `ldpctest -l 8448 -s10`'s "Decoding time mean").
  */
@@ -17,19 +19,12 @@
 #include <string.h>
 #include <sys/resource.h>
 #include <time.h>
-#include "nrLDPC_hip.h"
+#include "abi_cases.h" /* the case table, ncols(), the LLR generator, the dump file */
 
 typedef int32_t (*init_t)(void);
 typedef int32_t (*stats_t)(int64_t *);
-typedef int32_t (*batch_t)(const nrLDPC_hip_dec_batch_t *);
 typedef int32_t (*dec_t)(t_nrLDPC_dec_params *, uint8_t, uint8_t, uint8_t, int8_t *, int8_t *, t_nrLDPC_time_stats *, decode_abort_t *);
 
-#define NCASE 12
-static const int cases[NCASE][4] = { /* BG, Z, R, numMaxIter */
-  {1, 384, 13, 8}, {1, 384, 13, 8}, {1, 384, 23, 8}, {1, 352, 89, 5}, {2, 64, 15, 8}, {2, 208, 13, 8},
-  {1, 96, 13, 8},  {1, 384, 13, 2}, {2, 6, 15, 8},   {1, 18, 13, 8},  {2, 384, 23, 8}, {1, 384, 13, 8}};
-static int ncols(int BG, int R) { return BG == 1 ? (R == 13 ? 68 : R == 23 ? 35 : 27) : (R == 15 ? 52 : R == 13 ? 32 : 17); }
-typedef int (*crc_t)(uint8_t *, uint32_t, uint8_t);
 static crc_t crc_cb; /* the library's nrLDPC_hip_check_crc: the CRC stop that is evaluated on the GPU (a caller's own predicate would be called on the host) */
 
 static dec_t dec;
@@ -86,37 +81,24 @@ int main(int argc, char **argv)
   const int T = atoi(argv[2]);
   calls_per_thread = atoi(argv[3]);
   if (argc > 4) only_case = atoi(argv[4]) % NCASE;
-  unsigned s = 12345;
-  if (getenv("ABI_WARM")) { /* build every code's descriptor before the first per-segment call */
-    batch_t batch = (batch_t)dlsym(h, "LDPCdecoder_batch");
-    for (int c = 0; c < NCASE; c++) {
-      nrLDPC_hip_dec_batch_t b;
-      int8_t dummy[16];
-      int32_t it;
-      memset(&b, 0, sizeof(b));
-      b.params.BG = cases[c][0]; b.params.Z = cases[c][1]; b.params.R = cases[c][2]; b.params.numMaxIter = 1;
-      b.llr = dummy; b.out = dummy; b.n_iter = &it; b.llr_stride = 68 * 384; b.out_stride = 68 * 384;
-      batch(&b);
-    }
-  }
+  unsigned s = ABI_LLR_SEED;
+  if (getenv("ABI_WARM")) /* build every code's descriptor before the first per-segment call */
+    abi_warm_cases((abi_batch_t)dlsym(h, "LDPCdecoder_batch"));
+  /* ABI_DUMP=<file>: the single-threaded calls every concurrent call is compared with, for the oracle (abi_cases.h) */
+  FILE *dump = getenv("ABI_DUMP") ? fopen(getenv("ABI_DUMP"), "wb") : NULL;
   for (int c = 0; c < NCASE; c++) {
-    const int BG = cases[c][0], Z = cases[c][1], R = cases[c][2], n = ncols(BG, R) * Z;
-    llr[c] = aligned_alloc(64, (n + 63) / 64 * 64);
-    for (int i = 0; i < n; i++) {
-      s = s * 1664525u + 1013904223u;
-      const int r = (int)((s >> 16) % 41) - 20;            /* -20..20 */
-      llr[c][i] = (int8_t)(i < 2 * Z ? 0 : (c & 1) ? 14 + r / 2 : r); /* odd cases: noisy all-zero code word, even: noise */
-    }
-    memset(&prm[c], 0, sizeof(prm[c]));
-    prm[c].BG = BG; prm[c].Z = Z; prm[c].R = R; prm[c].numMaxIter = cases[c][3]; prm[c].outMode = nrLDPC_outMode_BIT;
-    if (c == 11) { prm[c].check_crc = crc_cb; prm[c].E = 22 * 384; prm[c].crc_type = 1; } /* CRC-stop mode in the mix */
-    out_len[c] = (n + 31) / 32 * 4;
+    abi_case_llr(c, &s, &llr[c]);
+    abi_case_params(c, crc_cb, &prm[c]);
+    out_len[c] = abi_case_out_len(c);
     expect[c] = malloc(out_len[c]);
     memset(expect[c], 0xA5, out_len[c]);
     t_nrLDPC_dec_params p = prm[c];
     expect_iter[c] = dec(&p, 0, 0, 0, llr[c], (int8_t *)expect[c], NULL, NULL);
     if (expect_iter[c] < 0) { fprintf(stderr, "case %d failed single-threaded\n", c); return 1; }
+    abi_dump_dec(dump, c, &prm[c], 0xA5, expect_iter[c], llr[c], expect[c]);
   }
+  if (dump)
+    fclose(dump);
   if (getenv("ABI_FAIL_LAUNCHES_FROM_NOW")) /* fault injection: the resident server cannot be (re)launched any more */
     setenv("NRLDPC_HIP_SRV_TEST_FAIL_LAUNCH", "1", 1);
   pthread_t th[256];

@@ -608,14 +608,18 @@ def test_concurrent_callers_of_the_reference_entry_point(hip, tmp_path):
     exe = tmp_path / "abi_threads"
     subprocess.run(["gcc", "-O2", "-I", str(root / "include"), str(root / "tests" / "abi_threads.c"), "-o", str(exe),
                     "-ldl", "-lpthread"], check=True)
+    import abi_dump
     for extra in ({}, {"NRLDPC_HIP_SRV_SLOTS": "4", "NRLDPC_HIP_SRV_IDLE_US": "150"}, {"NRLDPC_HIP_SERVER": "0"}):
-        env = dict(os.environ, **extra)
+        dump = tmp_path / "abi_threads.dump"
+        env = dict(os.environ, ABI_DUMP=str(dump), **extra)
         r = subprocess.run([str(exe), str(hip.ldpc.LIB_PATH), "16", "150"], capture_output=True, text=True, env=env,
                            timeout=300)
         assert r.returncode == 0, (extra, r.stderr[-2000:])
         d = json.loads(r.stdout.strip().splitlines()[-1])
         assert d["failures"] == 0 and d["calls"] == 2400, extra
         assert d["served"] == (0 if extra.get("NRLDPC_HIP_SERVER") == "0" else 2400 + 12), (extra, d)
+        # ... and what they all returned is what the oracle returns for the same inputs (the C caller's view of the entry point)
+        assert abi_dump.check_against_oracle(dump, 12) == d["iters"], extra
 
 
 def test_server_generations_wait_modes_and_a_server_that_cannot_be_relaunched(hip, tmp_path):
