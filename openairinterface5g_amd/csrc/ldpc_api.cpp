@@ -60,6 +60,14 @@ int set_error(const char *what, hipError_t e = hipSuccess)
       return set_error(#expr, e_);                      \
   } while (0)
 
+} // namespace
+
+/* the slot-level calls' plain arithmetic on descriptors (it reports through set_error); the plans themselves come in with the
+ * *_api.inc.cpp files at the end */
+#include "slot_plan.h"
+
+namespace {
+
 struct CodeEntry {
   ldpc_code_desc_t host;            /* throughput shape (ldpc_graph.h); everything shape independent is read from here */
   ldpc_code_desc_t *dev = nullptr;
@@ -468,8 +476,6 @@ template <typename T> struct CtxHolder { /* thread_local, one per logical device
 inline int cur_dev_index() { return (int)(&G() - g.dev); }
 thread_local CtxHolder<ThreadCtx> tls_ctx_holder[NRLDPC_HIP_MAX_DEVICES];
 #define tls_ctx (tls_ctx_holder[cur_dev_index()].get(cur_dev_index()))
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 /* is [p, p + bytes) page-locked host memory the GPU can address?  Both ends are asked about: a caller may have registered
  * only part of an array, and a range that was registered once and given back to the allocator must not be taken for

@@ -8,13 +8,6 @@
 
 namespace {
 
-int qam_check_qm(uint32_t Qm)
-{
-  if (Qm != 2 && Qm != 4 && Qm != 6 && Qm != 8)
-    return set_error("modulation: Qm must be 2, 4, 6 or 8");
-  return 0;
-}
-
 /* decode_symbols: what decode_scrambled checks, and a record that starts on a symbol and on a 4-byte boundary */
 int sym_check_batch(const nrLDPC_hip_tb_batch_t *b, const nrLDPC_hip_tb_scr_t *scr)
 {

@@ -1,107 +1,12 @@
 /*
  * rx_front_api.inc.cpp -- the UL receive front's entry points: channel level and channel compensation of the single-layer PUSCH
- * receiver (included into ldpc_api.cpp; uses qam_check_qm of qam_api.inc.cpp and the call scopes, the table layout and the overlap
- * check of slot_call.inc.cpp).  The arithmetic: nr_rx_front.h; the kernels: tb_rx_front.hip.  Everything the kernels index with is
- * checked here, before anything is enqueued.
+ * receiver (included into ldpc_api.cpp; uses the call scopes of slot_call.inc.cpp).  The arithmetic: nr_rx_front.h; the kernels:
+ * tb_rx_front.hip.  Everything the kernels index with is checked before anything is enqueued: the checks, the plan and the
+ * workgroup table are rx_plan.h's, which the CPU emulation of the kernels shares.
  */
+#include "rx_plan.h"
 
 namespace {
-
-/* what a call's descriptors come to: the job lists and the c16 ranges of the caller's arrays they reach */
-struct RxFrontPlan {
-  std::vector<rx_front_seg_job> jobs;
-  std::vector<rx_front_wg> wgs;
-  std::vector<rx_front_lvl_job> lvl;
-  uint64_t rx_lo = UINT64_MAX, rx_hi = 0, ch_lo = UINT64_MAX, ch_hi = 0, out_lo = UINT64_MAX, out_hi = 0;
-  uint32_t n_shift = 0; /* 1 + the largest tb */
-};
-
-int rxf_check_common(const char *who, uint32_t n_rx, int32_t mem)
-{
-  if (n_rx < 1 || n_rx > NR_RXF_MAX_RX)
-    return set_error((std::string(who) + ": n_rx must be 1..8").c_str());
-  return check_mem(who, mem);
-}
-
-/* the segments of a compensation call, without the workgroup table (that needs the address the records are written at) */
-int rxf_plan_compensation(const nrLDPC_hip_rx_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t ant_stride, RxFrontPlan &p)
-{
-  std::vector<Range64> out;
-  p.jobs.reserve(n_seg);
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_rx_seg_t &g = seg[i];
-    if (qam_check_qm(g.Qm) != 0)
-      return set_error("channel_compensation: Qm must be 2, 4, 6 or 8");
-    if (g.rec_off & 1u)
-      return set_error("channel_compensation: rec_off must be even");
-    if ((uint64_t)g.sym_off + g.nb_re > g.plane)
-      return set_error("channel_compensation: sym_off + nb_re above plane");
-    if ((uint64_t)g.nb_re * g.Qm > NR_SCR_MAX_BITS)
-      return set_error("channel_compensation: nb_re * Qm above 2^21");
-    p.n_shift = std::max(p.n_shift, g.tb + 1u);
-    if (g.nb_re == 0)
-      continue;
-    const uint64_t first = g.rec_off / 2u + g.sym_off, reach = (uint64_t)(n_rx - 1) * ant_stride + g.nb_re;
-    for (uint32_t k = 0; k < g.Qm / 2u; k++)
-      out.push_back(Range64{first + (uint64_t)k * g.plane, first + (uint64_t)k * g.plane + g.nb_re});
-    p.rx_lo = std::min(p.rx_lo, g.rx_off);
-    p.rx_hi = std::max(p.rx_hi, g.rx_off + reach);
-    p.ch_lo = std::min(p.ch_lo, g.ch_off);
-    p.ch_hi = std::max(p.ch_hi, g.ch_off + reach);
-    rx_front_seg_job j{};
-    j.rx_off = g.rx_off;
-    j.ch_off = g.ch_off;
-    j.out_off = first;
-    j.plane = g.plane;
-    j.nb_re = g.nb_re;
-    j.tb = g.tb;
-    j.Qm = g.Qm;
-    p.jobs.push_back(j);
-  }
-  if (ranges_overlap(out, p.out_lo, p.out_hi))
-    return set_error("channel_compensation: the output ranges of two segments overlap");
-  return 0;
-}
-
-/* offsets relative to the copies' starts (staged) and the workgroup table for records written at word address rec_word */
-void rxf_place(RxFrontPlan &p, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias, uint64_t rec_word)
-{
-  for (size_t i = 0; i < p.jobs.size(); i++) {
-    rx_front_seg_job &j = p.jobs[i];
-    j.rx_off -= rx_bias;
-    j.ch_off -= ch_bias;
-    j.out_off -= out_bias;
-    j.phase = (uint32_t)((rec_word + j.out_off) & 3u);
-    const uint32_t groups = (j.nb_re + j.phase + NR_RXF_GROUP - 1u) / NR_RXF_GROUP;
-    for (uint32_t q = 0; q * NR_RXF_THREADS < groups; q++)
-      p.wgs.push_back(rx_front_wg{(uint32_t)i, q});
-  }
-}
-
-int rxf_plan_level(const nrLDPC_hip_rx_seg_t *fs, uint32_t n_tb, uint32_t n_rx, uint64_t ant_stride, RxFrontPlan &p)
-{
-  std::vector<uint8_t> seen(n_tb, 0);
-  p.lvl.resize(n_tb);
-  for (uint32_t i = 0; i < n_tb; i++) {
-    if (fs[i].tb >= n_tb || seen[fs[i].tb])
-      return set_error("channel_level: every tb below n_tb must be named once");
-    seen[fs[i].tb] = 1;
-    if (fs[i].nb_re == 0)
-      return set_error("channel_level: the measurement symbol has no REs");
-    if ((uint64_t)fs[i].nb_re * 2u > NR_SCR_MAX_BITS)
-      return set_error("channel_level: nb_re above 2^20");
-    p.lvl[i] = rx_front_lvl_job{fs[i].ch_off, fs[i].nb_re, fs[i].tb};
-    p.ch_lo = std::min(p.ch_lo, fs[i].ch_off);
-    p.ch_hi = std::max(p.ch_hi, fs[i].ch_off + (uint64_t)(n_rx - 1) * ant_stride + fs[i].nb_re);
-  }
-  return 0;
-}
-
-/* a level call's blocks, then their zeroed state (maxima, counters: two words a block) */
-template <typename Job> Table2<Job, int32_t> rxf_level_tables(const std::vector<Job> &lvl)
-{
-  return Table2<Job, int32_t>{lvl.data(), lvl.size(), nullptr, 2u * lvl.size()};
-}
 
 /* only the segments' entries of the bounce that begins at c16 `bias` of the record array go to the caller's array */
 void rxf_scatter(const RxFrontPlan &p, const uint8_t *bounce, uint64_t bias, int16_t *records)

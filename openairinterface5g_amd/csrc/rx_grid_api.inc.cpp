@@ -1,122 +1,9 @@
 /*
  * rx_grid_api.inc.cpp -- the UL receive front read from the OFDM grid: the _grid forms of the two calls of
- * rx_front_api.inc.cpp (they use its checks, its plan and its scatter, and the call scopes of slot_call.inc.cpp), the CPU extraction
- * for checking, and the descriptors of a PUSCH allocation.  Where the REs lie: nr_rx_grid.h; the kernels: tb_rx_front.hip.
- * Everything the kernels index with is checked here, before anything is enqueued.
+ * rx_front_api.inc.cpp (they use its scatter and the call scopes of slot_call.inc.cpp), the CPU extraction for checking, and the
+ * descriptors of a PUSCH allocation.  Where the REs lie: nr_rx_grid.h; the kernels: tb_rx_front.hip.  Everything the kernels
+ * index with is checked before anything is enqueued: the grid checks, ranges and plan are rx_plan.h's.
  */
-
-namespace {
-
-int rxg_check_seg(const char *who, uint32_t pattern, uint32_t fft_size, uint32_t start_re, uint32_t nb_re)
-{
-  if (pattern >= NR_RXG_PATTERNS)
-    return set_error((std::string(who) + ": pattern must be FULL, DMRS1 or DMRS2").c_str());
-  if (fft_size > NR_SCR_MAX_BITS)
-    return set_error((std::string(who) + ": fft_size above 2^21").c_str());
-  if (fft_size == 0 || start_re >= fft_size)
-    return set_error((std::string(who) + ": start_re must be below fft_size").c_str());
-  /* the same as p(nb_re - 1) >= fft_size */
-  if (nb_re > nr_rxg_count(pattern, fft_size))
-    return set_error((std::string(who) + ": nb_re above the pattern's count within fft_size subcarriers (p(nb_re - 1) >= fft_size)").c_str());
-  return 0;
-}
-
-/* the c16 range [lo, hi) of one antenna's grid that a segment reaches: one piece, or the whole OFDM symbol when it wraps */
-void rxg_rx_range(const nrLDPC_hip_rx_grid_seg_t &g, uint64_t &lo, uint64_t &hi)
-{
-  const uint32_t first = g.start_re + nr_rxg_p(g.pattern, 0), last = g.start_re + nr_rxg_p(g.pattern, g.nb_re - 1u);
-  if (last < g.fft_size) {
-    lo = g.rx_off + first;
-    hi = g.rx_off + last + 1u;
-  } else if (first >= g.fft_size) {
-    lo = g.rx_off + first - g.fft_size;
-    hi = g.rx_off + last - g.fft_size + 1u;
-  } else {
-    lo = g.rx_off;
-    hi = g.rx_off + g.fft_size;
-  }
-}
-
-/* the grid checks, then the plan of the extracted form (its checks, output ranges and jobs) with the input ranges of the grid */
-int rxg_plan_compensation(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
-                          std::vector<rx_front_grid_job> &gj)
-{
-  std::vector<nrLDPC_hip_rx_seg_t> plain(n_seg);
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
-    if (rxg_check_seg("channel_compensation_grid", g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
-      return -1;
-    nrLDPC_hip_rx_seg_t &q = plain[i];
-    memset(&q, 0, sizeof q);
-    q.tb = g.tb;
-    q.Qm = g.Qm;
-    q.nb_re = g.nb_re;
-    q.plane = g.plane;
-    q.sym_off = g.sym_off;
-    q.rx_off = g.rx_off;
-    q.ch_off = g.ch_off;
-    q.rec_off = g.rec_off;
-  }
-  if (rxf_plan_compensation(plain.data(), n_seg, 1, 0, p) != 0)
-    return -1;
-  p.rx_lo = p.ch_lo = UINT64_MAX;
-  p.rx_hi = p.ch_hi = 0;
-  gj.reserve(p.jobs.size());
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
-    if (g.nb_re == 0)
-      continue;
-    uint64_t lo, hi;
-    rxg_rx_range(g, lo, hi);
-    p.rx_lo = std::min(p.rx_lo, lo);
-    p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
-    p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
-    p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(n_rx - 1) * ch_stride);
-    rx_front_grid_job j{};
-    j.pattern = g.pattern;
-    j.fft_size = g.fft_size;
-    j.start_re = g.start_re;
-    gj.push_back(j);
-  }
-  return 0;
-}
-
-/* rxf_place, then the placed segments into the grid jobs (p.jobs and gj run in step: the segments with REs).  A staged copy
- * starts at the first c16 that is reached, which lies behind subcarrier 0: rx_off / ch_off minus the bias may wrap below zero,
- * and the kernels' 64-bit address sums bring it back. */
-void rxg_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias, uint64_t rec_word)
-{
-  rxf_place(p, rx_bias, ch_bias, out_bias, rec_word);
-  for (size_t i = 0; i < gj.size(); i++)
-    gj[i].s = p.jobs[i];
-}
-
-int rxg_plan_level(const nrLDPC_hip_rx_grid_seg_t *fs, uint32_t n_tb, uint32_t n_rx, uint64_t ch_stride, std::vector<rx_front_grid_lvl_job> &lvl,
-                   uint64_t &ch_lo, uint64_t &ch_hi)
-{
-  std::vector<uint8_t> seen(n_tb, 0);
-  lvl.resize(n_tb);
-  ch_lo = UINT64_MAX;
-  ch_hi = 0;
-  for (uint32_t i = 0; i < n_tb; i++) {
-    if (fs[i].tb >= n_tb || seen[fs[i].tb])
-      return set_error("channel_level_grid: every tb below n_tb must be named once");
-    seen[fs[i].tb] = 1;
-    if (fs[i].nb_re == 0)
-      return set_error("channel_level_grid: the measurement symbol has no REs");
-    if ((uint64_t)fs[i].nb_re * 2u > NR_SCR_MAX_BITS)
-      return set_error("channel_level_grid: nb_re above 2^20");
-    /* the level reads the estimates alone, but the descriptor is the segment's: its grid fields are held to the same rules */
-    if (rxg_check_seg("channel_level_grid", fs[i].pattern, fs[i].fft_size, fs[i].start_re, fs[i].nb_re) != 0)
-      return -1;
-    lvl[i] = rx_front_grid_lvl_job{fs[i].ch_off, fs[i].nb_re, fs[i].tb, fs[i].pattern, 0};
-    ch_lo = std::min(ch_lo, fs[i].ch_off + nr_rxg_p(fs[i].pattern, 0));
-    ch_hi = std::max(ch_hi, fs[i].ch_off + nr_rxg_p(fs[i].pattern, fs[i].nb_re - 1u) + 1u + (uint64_t)(n_rx - 1) * ch_stride);
-  }
-  return 0;
-}
-
-} // namespace
 
 extern "C" {
 

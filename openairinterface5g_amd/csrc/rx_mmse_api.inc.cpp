@@ -1,83 +1,12 @@
 /*
  * rx_mmse_api.inc.cpp -- the two-layer PUSCH MMSE receiver's entry points: the channel level over the 2 n_rx (layer, antenna)
  * pairs, the receiver itself from the OFDM grid, and their CPU forms on extracted arrays (included into ldpc_api.cpp behind
- * rx_grid_api.inc.cpp: it uses its grid checks and ranges, the plan and placing of rx_front_api.inc.cpp and the call scopes of
- * slot_call.inc.cpp).  The arithmetic: nr_rx_mmse.h; the kernels: tb_rx_mmse.hip.  Everything the kernels index with is checked
- * here, before anything is enqueued.
+ * rx_grid_api.inc.cpp; uses the call scopes of slot_call.inc.cpp).  The arithmetic: nr_rx_mmse.h; the kernels: tb_rx_mmse.hip.
+ * Everything the kernels index with is checked before anything is enqueued: the checks, the plan and the workgroup table are
+ * rx_plan.h's (rxm_*), which the CPU emulation of the kernels shares.
  */
 
 namespace {
-
-int rxm_check_common(const char *who, uint32_t n_rx, int32_t mem)
-{
-  if (n_rx != 2 && n_rx != 4)
-    return set_error((std::string(who) + ": n_rx must be 2 or 4").c_str());
-  return check_mem(who, mem);
-}
-
-/* the checks, the jobs, the doubled output ranges (a segment fills codeword symbols 2 sym_off .. 2 (sym_off + nb_re) - 1 of
- * each plane) and the input ranges: n_rx antennas of the grid, 2 n_rx pairs of the estimates */
-int rxm_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
-             std::vector<rx_front_grid_job> &gj)
-{
-  std::vector<Range64> out;
-  gj.reserve(n_seg);
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
-    if (rxg_check_seg("mmse_2layers_grid", g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
-      return -1;
-    if (g.Qm != 6 && g.Qm != 8)
-      return set_error("mmse_2layers_grid: Qm must be 6 or 8 (two layers of QPSK / 16QAM take the ML receiver, which is not built)");
-    if (g.rec_off & 1u)
-      return set_error("mmse_2layers_grid: rec_off must be even");
-    if (2u * ((uint64_t)g.sym_off + g.nb_re) > g.plane)
-      return set_error("mmse_2layers_grid: 2 (sym_off + nb_re) above plane");
-    if (2u * (uint64_t)g.nb_re * g.Qm > NR_SCR_MAX_BITS)
-      return set_error("mmse_2layers_grid: 2 nb_re * Qm above 2^21");
-    p.n_shift = std::max(p.n_shift, g.tb + 1u);
-    if (g.nb_re == 0)
-      continue;
-    const uint64_t first = g.rec_off / 2u + 2u * (uint64_t)g.sym_off;
-    for (uint32_t k = 0; k < g.Qm / 2u; k++)
-      out.push_back(Range64{first + (uint64_t)k * g.plane, first + (uint64_t)k * g.plane + 2u * (uint64_t)g.nb_re});
-    uint64_t lo, hi;
-    rxg_rx_range(g, lo, hi);
-    p.rx_lo = std::min(p.rx_lo, lo);
-    p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
-    p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
-    p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(2u * n_rx - 1u) * ch_stride);
-    rx_front_grid_job j{};
-    j.s.rx_off = g.rx_off;
-    j.s.ch_off = g.ch_off;
-    j.s.out_off = first;
-    j.s.plane = g.plane;
-    j.s.nb_re = g.nb_re;
-    j.s.tb = g.tb;
-    j.s.Qm = g.Qm;
-    j.pattern = g.pattern;
-    j.fft_size = g.fft_size;
-    j.start_re = g.start_re;
-    gj.push_back(j);
-  }
-  if (ranges_overlap(out, p.out_lo, p.out_hi))
-    return set_error("mmse_2layers_grid: the output ranges of two segments overlap");
-  return 0;
-}
-
-/* offsets relative to the copies' starts (staged; see rxg_place for the wrap below zero) and the workgroup table: a workgroup
- * takes NR_RXF_THREADS quads of a segment, counted from its RE 0 */
-void rxm_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias)
-{
-  for (size_t i = 0; i < gj.size(); i++) {
-    rx_front_seg_job &j = gj[i].s;
-    j.rx_off -= rx_bias;
-    j.ch_off -= ch_bias;
-    j.out_off -= out_bias;
-    const uint32_t quads = (j.nb_re + NR_RXM_QUAD - 1u) / NR_RXM_QUAD;
-    for (uint32_t q = 0; q * NR_RXF_THREADS < quads; q++)
-      p.wgs.push_back(rx_front_wg{(uint32_t)i, q});
-  }
-}
 
 /* only the segments' entries of the bounce that begins at c16 `bias` of the record array go to the caller's array */
 void rxm_scatter(const std::vector<rx_front_grid_job> &gj, const uint8_t *bounce, uint64_t bias, int16_t *records)

@@ -6,8 +6,6 @@
 
 namespace {
 
-#define NR_SCR_MAX_BITS (1u << 21) /* one codeword: G <= 1.5 Mbit (the sequence's jump tables reach 2^17 - 50 words) */
-
 /* 38.211 7.3.1.1 / 6.3.1.1: n_RNTI < 2^16, n_ID < 1024, q = codeword 0 / 1 */
 int scr_validate(uint32_t n_rnti, uint32_t q, uint32_t n_id)
 {

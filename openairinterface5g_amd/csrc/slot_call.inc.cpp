@@ -1,18 +1,12 @@
 /*
  * slot_call.inc.cpp -- what the slot-level entry points share (included into ldpc_api.cpp behind tb_api.inc.cpp, whose TbCtx it
  * uploads descriptor tables through, and ahead of the *_api.inc.cpp files that use it): the scope of a DEVICE mem call and of a
- * HOST mem call, the layout of a call's descriptor tables, and the small checks and derivations that more than one of them needs.
+ * HOST mem call, and the small derivations that more than one of them needs.  The layout of a call's descriptor tables, the
+ * overlap check and the checks that need no HIP call are in slot_plan.h, which the CPU emulation of the kernels shares.
  * An entry point reads top to bottom: checks, plan, one of the two scopes, launch, scatter.
  */
 
 namespace {
-
-int check_mem(const char *who, int32_t mem)
-{
-  if (mem != NRLDPC_HIP_MEM_HOST && mem != NRLDPC_HIP_MEM_DEVICE)
-    return set_error((std::string(who) + ": mem must be NRLDPC_HIP_MEM_HOST or NRLDPC_HIP_MEM_DEVICE").c_str());
-  return 0;
-}
 
 /* DEVICE mem: the HIP ordinal of the GPU whose memory holds p (hipMalloc or managed), -1 for anything else */
 int scr_device_ordinal(const void *p)
@@ -22,32 +16,6 @@ int scr_device_ordinal(const void *p)
     return at.device;
   (void)hipGetLastError();
   return -1;
-}
-
-/* ---- two arrays back to back, each padded to 16 bytes: a call's descriptor tables (the workgroup table, then the job table) or
- * its jobs and their state (b == nullptr: nb zeroed elements) ---- */
-template <typename A, typename B> struct Table2 {
-  const A *a;
-  size_t na;
-  const B *b;
-  size_t nb;
-  static size_t bytes(size_t na, size_t nb) { return align_up(na * sizeof(A), 16) + align_up(nb * sizeof(B), 16); }
-  size_t bytes() const { return bytes(na, nb); }
-  void write(uint8_t *dst) const
-  {
-    memcpy(dst, a, na * sizeof(A));
-    if (b)
-      memcpy(dst + align_up(na * sizeof(A), 16), b, nb * sizeof(B));
-    else
-      memset(dst + align_up(na * sizeof(A), 16), 0, align_up(nb * sizeof(B), 16));
-  }
-  /* the two parts of a copy at base */
-  const A *first(const uint8_t *base) const { return reinterpret_cast<const A *>(base); }
-  B *second(uint8_t *base) const { return reinterpret_cast<B *>(base + align_up(na * sizeof(A), 16)); }
-};
-template <typename A, typename B> Table2<A, const B> table2(const std::vector<A> &a, const std::vector<B> &b)
-{
-  return Table2<A, const B>{a.data(), a.size(), b.data(), b.size()};
 }
 
 /* ---- DEVICE mem: the call works in place on the caller's arrays, on the GPU that holds them and on the caller's stream ---- */
@@ -144,47 +112,6 @@ struct StagedCall {
     return 0;
   }
 };
-
-/* ---- the write set of a call: [lo, hi) ranges that must not overlap ---- */
-struct Range64 {
-  uint64_t lo, hi;
-};
-/* true when two of the ranges overlap (r comes back sorted); lo, hi: the span of all of them, UINT64_MAX and 0 when there are none */
-bool ranges_overlap(std::vector<Range64> &r, uint64_t &lo, uint64_t &hi)
-{
-  lo = UINT64_MAX;
-  hi = 0;
-  for (const Range64 &x : r) {
-    lo = std::min(lo, x.lo);
-    hi = std::max(hi, x.hi);
-  }
-  std::sort(r.begin(), r.end(), [](const Range64 &a, const Range64 &b) { return a.lo < b.lo; });
-  for (size_t i = 1; i < r.size(); i++)
-    if (r[i].lo < r[i - 1].hi)
-      return true;
-  return false;
-}
-
-/* ---- DMRS sequences ---- */
-/* c_init of the DMRS of one OFDM symbol, PUSCH and PDSCH alike (nr_gold.c:87-88, 107-108) */
-uint32_t dmrs_c_init(uint32_t slot, uint32_t symbol, uint32_t scrambling_id, uint32_t scid)
-{
-  return (uint32_t)(((1ull << 17) * (NR_RXG_SYMBOLS * slot + symbol + 1u) * (2ull * scrambling_id + 1u) + 2ull * scrambling_id + scid) & 0x7fffffffull);
-}
-/* the sequence from symbol k on, two bits a symbol (the low two: the DMRS value of k itself), out of Gold words w0, w0 + 1, ...;
- * gold holds one word beyond the one k's bits lie in */
-uint64_t dmrs_bits(const std::vector<uint32_t> &gold, uint32_t w0, uint32_t k)
-{
-  const uint32_t w = (k >> 4) - w0;
-  return ((uint64_t)gold[w] | ((uint64_t)gold[w + 1] << 32)) >> ((2u * k) & 31u);
-}
-/* the words that hold symbols k0 .. k0 + n - 1 (n >= 1) and one more, for dmrs_bits; false when they cannot be generated */
-bool dmrs_gold_words(uint32_t c_init, uint32_t k0, uint32_t n, std::vector<uint32_t> &gold, uint32_t &w0)
-{
-  w0 = k0 >> 4;
-  gold.resize(((k0 + n - 1u) >> 4) - w0 + 2u);
-  return nr_hip_gold_words(c_init, w0, (uint32_t)gold.size(), gold.data()) == 0;
-}
 
 /* ---- the builders of descriptors from an allocation ---- */
 int alloc_check_symbols(const char *who, uint32_t start_symbol, uint32_t nr_of_symbols)

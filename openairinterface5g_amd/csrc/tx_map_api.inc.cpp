@@ -1,54 +1,13 @@
 /*
  * tx_map_api.inc.cpp -- PDSCH resource mapping with DMRS onto the transmit grid: the GPU call, its CPU check forms and the
- * descriptors of a PDSCH allocation (included into ldpc_api.cpp; uses che_fft_ok and che_gold_tables of rx_chest_api.inc.cpp and
- * the call scopes, the table layout, the overlap check and the DMRS helpers of slot_call.inc.cpp).  The arithmetic:
- * nr_pdsch_map.h; the kernel: tb_tx_map.hip.  Everything the kernel indexes with is checked here, before anything is enqueued.
+ * descriptors of a PDSCH allocation (included into ldpc_api.cpp; uses the call scopes and the DMRS helpers of slot_call.inc.cpp).
+ * The arithmetic: nr_pdsch_map.h; the kernel: tb_tx_map.hip.  Everything the kernel indexes with is checked before anything is
+ * enqueued: the descriptor check, the plan and the workgroup table are tx_map_plan.h's, which the CPU emulation of the kernels
+ * shares.
  */
+#include "tx_map_plan.h"
 
 namespace {
-
-int txm_check_seg(const char *who, const nrLDPC_hip_pdsch_map_seg_t &g)
-{
-  const std::string w(who);
-  if (g.pattern >= NR_PDM_PATTERNS)
-    return set_error((w + ": pattern must be FULL, DMRS1 or DMRS2").c_str());
-  if (g.Nl < 1 || g.Nl > NR_PDM_MAX_LAYERS)
-    return set_error((w + ": Nl must be 1..4").c_str());
-  if (g.amp <= 0)
-    return set_error((w + ": amp must be positive").c_str());
-  if (!che_fft_ok(g.fft_size))
-    return set_error((w + ": fft_size must be 128, 256, 512, 1024, 1536, 2048, 4096, 6144 or 8192").c_str());
-  if (g.rb_size == 0)
-    return set_error((w + ": rb_size is 0").c_str());
-  if ((uint64_t)g.rb_size * 12u > g.fft_size)
-    return set_error((w + ": the allocation is wider than fft_size").c_str());
-  if (g.start_re >= g.fft_size)
-    return set_error((w + ": start_re must be below fft_size").c_str());
-  if (g.lay_off & 1u)
-    return set_error((w + ": lay_off must be even").c_str());
-  if (g.pattern != NR_PDM_FULL) {
-    if (g.ncdm < 1 || g.ncdm > nr_pdm_max_ncdm(g.pattern))
-      return set_error((w + ": ncdm must be 1..2 for type 1 and 1..3 for type 2").c_str());
-    if (g.l_prime > 1)
-      return set_error((w + ": l_prime must be 0 or 1").c_str());
-    for (uint32_t l = 0; l < g.Nl; l++)
-      if (g.port[l] >= nr_pdm_ports(g.pattern))
-        return set_error((w + ": port must be 0..7 for type 1 and 0..11 for type 2").c_str());
-    if (g.c_init >> 31)
-      return set_error((w + ": c_init must be below 2^31").c_str());
-    if (g.dmrs_offset > (1u << 20))
-      return set_error((w + ": dmrs_offset above 2^20").c_str());
-  }
-  for (uint32_t l = 0; l < g.Nl; l++) {
-    uint32_t pm, dm;
-    nr_pdm_masks(g.pattern, g.ncdm, nr_pdm_delta(g.pattern, g.port[l]), &pm, &dm);
-    if (g.nb_re != g.rb_size * nr_pdm_popc(dm))
-      return set_error((w + ": nb_re is not the number of data REs of the pattern (for every layer's port)").c_str());
-  }
-  if ((uint64_t)g.sym_off + g.nb_re > g.plane)
-    return set_error((w + ": sym_off + nb_re is above plane").c_str());
-  return 0;
-}
 
 /* one descriptor, one antenna on the CPU: lay = the symbol's stretch of the layer's plane (NULL: zeros), sym = the symbol's
  * subcarrier 0 */
@@ -74,91 +33,6 @@ int txm_host_one(const nrLDPC_hip_pdsch_map_seg_t &g, const uint32_t *lay, uint3
     sym[nr_pdm_wrap(g.start_re, i, g.fft_size)] = nr_pdm_re(&s, lay, i, bits, jlo);
   }
   return 0;
-}
-
-struct TxMapPlan {
-  std::vector<tx_map_job> jobs;
-  std::vector<tx_map_wg> wgs; /* sorted by pattern */
-  uint32_t n_wg[NR_PDM_PATTERNS] = {0, 0, 0};
-  uint64_t lay_lo = UINT64_MAX, lay_hi = 0, out_lo = UINT64_MAX, out_hi = 0; /* c16 */
-};
-
-/* checks and ranges; the workgroup table needs the address the grid is written at (txm_plan_wgs) */
-int txm_plan(const char *who, const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, TxMapPlan &p)
-{
-  std::vector<Range64> out;
-  p.jobs.resize(n_seg);
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_pdsch_map_seg_t &g = seg[i];
-    if (txm_check_seg(who, g) != 0)
-      return -1;
-    if (n_tx < g.Nl)
-      return set_error((std::string(who) + ": n_tx is below a descriptor's Nl").c_str());
-    const uint64_t lay0 = g.lay_off / 2u + g.sym_off;
-    p.lay_lo = std::min(p.lay_lo, lay0);
-    p.lay_hi = std::max(p.lay_hi, lay0 + (uint64_t)(g.Nl - 1u) * g.plane + g.nb_re);
-    const uint32_t n_re = 12u * g.rb_size, first = std::min(n_re, g.fft_size - g.start_re);
-    for (uint32_t a = 0; a < n_tx; a++) {
-      const uint64_t base = g.tx_off + (uint64_t)a * tx_stride;
-      out.push_back(Range64{base + g.start_re, base + g.start_re + first});
-      if (first < n_re)
-        out.push_back(Range64{base, base + (n_re - first)});
-    }
-    tx_map_job &j = p.jobs[i];
-    memset(&j, 0, sizeof j);
-    j.tx_off = g.tx_off;
-    j.lay_off = lay0;
-    j.plane = g.plane;
-    j.fft_size = g.fft_size;
-    j.start_re = g.start_re;
-    j.n_re = n_re;
-    j.dmrs_offset = g.dmrs_offset;
-    j.Nl = g.Nl;
-    j.ncdm = g.ncdm;
-    j.l_prime = g.l_prime;
-    j.amp = g.amp;
-    for (uint32_t l = 0; l < g.Nl; l++)
-      j.ports |= (uint32_t)g.port[l] << (8u * l);
-  }
-  if (ranges_overlap(out, p.out_lo, p.out_hi))
-    return set_error((std::string(who) + ": the output ranges of two (descriptor, antenna) pairs overlap").c_str());
-  return 0;
-}
-
-/* the workgroup table, pattern by pattern; tx = the address the kernel is given, the jobs' tx_off as they will be launched.
- * precoded: every antenna needs the pilots of every layer, so its Gold registers stand where the port with the latest pilots is */
-void txm_plan_wgs(const nrLDPC_hip_pdsch_map_seg_t *seg, uint32_t n_seg, uint32_t n_tx, uint64_t tx_stride, const void *tx, TxMapPlan &p,
-                  bool precoded = false)
-{
-  const uint64_t word0 = (uint64_t)(reinterpret_cast<uintptr_t>(tx) >> 2);
-  for (uint32_t pattern = 0; pattern < NR_PDM_PATTERNS; pattern++)
-    for (uint32_t i = 0; i < n_seg; i++) {
-      const nrLDPC_hip_pdsch_map_seg_t &g = seg[i];
-      if (g.pattern != pattern)
-        continue;
-      const tx_map_job &j = p.jobs[i];
-      for (uint32_t a = 0; a < n_tx; a++) {
-        tx_map_wg w{};
-        w.job = i;
-        w.ant = a;
-        w.phase = (uint32_t)((word0 + j.tx_off + (uint64_t)a * tx_stride + j.start_re) & 3u);
-        uint32_t pm = 0, dm = 0;
-        if (precoded)
-          pm = nr_pdm_last_pmask(pattern);
-        else if (a < g.Nl)
-          nr_pdm_masks(pattern, g.ncdm, nr_pdm_delta(pattern, g.port[a]), &pm, &dm);
-        for (uint32_t q = 0; (uint64_t)q * NR_TXM_THREADS * NR_TXM_GROUP < (uint64_t)j.n_re + w.phase; q++) {
-          w.piece = q;
-          if (pm) {
-            const uint32_t i_first = q ? q * NR_TXM_THREADS * NR_TXM_GROUP - w.phase : 0u;
-            w.w0 = (2u * (g.dmrs_offset + nr_pdm_count(pm, i_first))) >> 5;
-            nr_gold_jump(&che_gold_tables(), g.c_init, w.w0, &w.x1, &w.x2);
-          }
-          p.wgs.push_back(w);
-          p.n_wg[pattern]++;
-        }
-      }
-    }
 }
 
 /* the launches over the tables' device copy */

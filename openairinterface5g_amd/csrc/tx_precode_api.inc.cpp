@@ -1,88 +1,12 @@
 /*
  * tx_precode_api.inc.cpp -- PDSCH resource mapping with precoding, layers to antenna ports through per-PRG matrices: the GPU
- * call, its CPU check form and the descriptor builder (included into ldpc_api.cpp behind tx_map_api.inc.cpp, whose descriptor
- * checks, plan, workgroup table and scatter it uses).  The arithmetic: nr_pdsch_map.h; the kernel: tb_tx_map.hip.  The caller's
- * PMI lists are resolved against the matrix table here, so the device searches nothing; the resolved lists and the matrices in
- * use travel with the descriptors in the call's one upload (job_layout.h).
+ * call, its CPU check form and the descriptor builder (included into ldpc_api.cpp behind tx_map_api.inc.cpp, whose scatter it
+ * uses).  The arithmetic: nr_pdsch_map.h; the kernel: tb_tx_map.hip.  The caller's PMI lists are resolved against the matrix
+ * table before the launch (txp_plan of tx_map_plan.h), so the device searches nothing; the resolved lists and the matrices in use
+ * travel with the descriptors in the call's one upload (job_layout.h).
  */
 
 namespace {
-
-struct TxPrecodePlan {
-  std::vector<tx_map_prg> prgs; /* parallel to the descriptors */
-  std::vector<uint16_t> pmx;    /* per PRG: 0 = unit, else 1 + index into mats */
-  std::vector<tx_map_pm> mats;  /* the matrices in use */
-};
-
-int txp_plan(const char *who, const nrLDPC_hip_pdsch_map_seg_t *seg, const nrLDPC_hip_pdsch_prg_t *prg, uint32_t n_seg, uint32_t n_tx,
-             const uint16_t *pmi_list, uint32_t n_pmi, const nrLDPC_hip_pm_pdu_t *pm, uint32_t n_pm, TxPrecodePlan &pp)
-{
-  const std::string w(who);
-  std::map<uint16_t, uint32_t> by_idx;
-  for (uint32_t t = 0; pm && t < n_pm; t++) {
-    if (pm[t].pm_idx == 0)
-      return set_error((w + ": pm_idx 0 in the precoding-matrix table (0 is the unit matrix)").c_str());
-    if (!by_idx.emplace(pm[t].pm_idx, t).second)
-      return set_error((w + ": a pm_idx appears twice in the precoding-matrix table").c_str());
-  }
-  std::vector<int32_t> slot_of(pm ? n_pm : 0u, -1); /* table entry -> index into mats */
-  pp.prgs.resize(n_seg);
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_pdsch_map_seg_t &g = seg[i];
-    const nrLDPC_hip_pdsch_prg_t &r = prg[i];
-    tx_map_prg &o = pp.prgs[i];
-    if (r.prg_size == 0) { /* unit precoding: one PRG as wide as the allocation */
-      o.prg_size = g.rb_size;
-      o.pmx_off = (uint32_t)pp.pmx.size();
-      pp.pmx.push_back(0);
-      continue;
-    }
-    const uint32_t need = (g.rb_size + r.prg_size - 1u) / r.prg_size;
-    if (r.pmi_count < need)
-      return set_error((w + ": a descriptor's PMI range is shorter than ceil(rb_size / prg_size)").c_str());
-    if (!pmi_list || (uint64_t)r.pmi_off + r.pmi_count > n_pmi)
-      return set_error((w + ": a descriptor's PMI range reaches outside the PMI list").c_str());
-    /* the symbols of an allocation share their range: resolved once */
-    if (i > 0 && prg[i - 1].prg_size == r.prg_size && prg[i - 1].pmi_off == r.pmi_off && prg[i - 1].pmi_count == r.pmi_count &&
-        seg[i - 1].rb_size == g.rb_size && seg[i - 1].Nl == g.Nl) {
-      o = pp.prgs[i - 1];
-      continue;
-    }
-    o.prg_size = r.prg_size;
-    o.pmx_off = (uint32_t)pp.pmx.size();
-    for (uint32_t q = 0; q < need; q++) {
-      const uint16_t pmi = pmi_list[r.pmi_off + q];
-      if (pmi == 0) {
-        pp.pmx.push_back(0);
-        continue;
-      }
-      if (n_tx < 2)
-        return set_error((w + ": n_tx must be at least 2 when a PMI is not 0 (no precoding with a single antenna port)").c_str());
-      if (!pm)
-        return set_error((w + ": a PMI that is not 0 needs the precoding-matrix table").c_str());
-      const auto it = by_idx.find(pmi);
-      if (it == by_idx.end())
-        return set_error((w + ": a PMI that no entry of the precoding-matrix table carries").c_str());
-      const nrLDPC_hip_pm_pdu_t &m = pm[it->second];
-      if (m.numLayers != g.Nl)
-        return set_error((w + ": numLayers of a precoding matrix is not the descriptor's Nl").c_str());
-      if (m.num_ant_ports < n_tx || m.num_ant_ports > NR_PDM_MAX_TX)
-        return set_error((w + ": num_ant_ports of a precoding matrix must be n_tx..8").c_str());
-      if (slot_of[it->second] < 0) {
-        if (pp.mats.size() >= 0xffffu)
-          return set_error((w + ": more than 65534 precoding matrices in use").c_str());
-        slot_of[it->second] = (int32_t)pp.mats.size();
-        tx_map_pm d;
-        for (uint32_t l = 0; l < NR_PDM_MAX_LAYERS; l++)
-          for (uint32_t a = 0; a < NR_PDM_MAX_TX; a++)
-            d.w[l][a] = nr_pdm_pack(m.weights[l][a][0], m.weights[l][a][1]);
-        pp.mats.push_back(d);
-      }
-      pp.pmx.push_back((uint16_t)(slot_of[it->second] + 1));
-    }
-  }
-  return 0;
-}
 
 /* one descriptor, one antenna on the CPU: lay = the symbol's stretch of layer 0's plane, sym = the symbol's subcarrier 0 */
 int txp_host_one(const nrLDPC_hip_pdsch_map_seg_t &g, const tx_map_prg &pg, const TxPrecodePlan &pp, const uint32_t *lay, uint32_t ant, uint32_t *sym)
@@ -111,22 +35,6 @@ int txp_host_one(const nrLDPC_hip_pdsch_map_seg_t &g, const tx_map_prg &pg, cons
   }
   return 0;
 }
-
-/* the call's tables in one job buffer: the workgroup table, the jobs, their PRG records, the resolved PMIs, the matrices */
-struct TxPrecodeTables {
-  JobLayout lay;
-  size_t wgs, jobs, prgs, pmx, mats;
-  TxPrecodeTables(const TxMapPlan &p, const TxPrecodePlan &pp)
-      : wgs(lay.add(p.wgs)), jobs(lay.add(p.jobs)), prgs(lay.add(pp.prgs)), pmx(lay.add(pp.pmx)), mats(lay.add(pp.mats))
-  {
-  }
-  /* what a table of n_wg workgroups takes at the most */
-  static size_t bytes(size_t n_wg, const TxMapPlan &p, const TxPrecodePlan &pp)
-  {
-    return align_up(n_wg * sizeof(tx_map_wg), 16) + align_up(p.jobs.size() * sizeof(tx_map_job), 16) + align_up(pp.prgs.size() * sizeof(tx_map_prg), 16) +
-           align_up(pp.pmx.size() * sizeof(uint16_t), 16) + align_up(pp.mats.size() * sizeof(tx_map_pm), 16);
-  }
-};
 
 /* the launches over the tables' device copy at base */
 int txp_launch(const TxMapPlan &p, const TxPrecodeTables &t, const uint8_t *base, const uint32_t *lay, uint32_t *tx, uint64_t tx_stride, hipStream_t s)

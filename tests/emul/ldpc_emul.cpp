@@ -125,7 +125,9 @@ extern "C" int ldpc_emul_encode(int BG, int Zc, int Kb, const uint8_t *in, uint8
   if (ldpc_build_code_desc(BG, Zc, BG == 1 ? 13 : 15, &code_s) != 0)
     return -1;
   const ldpc_code_desc_t *code = &code_s;
-  std::vector<uint8_t> x(((code->ncols * Zc + 15) & ~15), 0x5a), lam(4 * Zc + 16, 0x5a);
+  /* exactly what ldpc_enc_core.h documents: ncols Zc bytes of code word, 4 Zc bytes of lambda (the kernel rounds the first up to
+   * 16 only to place the second in LDS) */
+  std::vector<uint8_t> x((size_t)code->ncols * Zc, 0x5a), lam(4 * (size_t)Zc, 0x5a);
   int waves = (Zc + 63) / 64 * 2;
   if (waves > 16) waves = 16;
   const int nt = waves * 64;
@@ -203,7 +205,9 @@ extern "C" int ldpc_emul_encode_packed32(int BG, int Zc, int Kb, const uint8_t *
     nt = ldpc_encp_threads(code->nrows, Zc);
   const ldpc_encp32 g = ldpc_encp32_make(code, Kb);
   emul_encp32_solve(code, L, g, in, nt);
-  std::vector<uint8_t> o2((size_t)(code->ncols - 2) * Zc + 32); /* (the stores are 16 bytes wide and want alignment) */
+  /* the stores are 16 bytes wide and want a 16-byte aligned output, which the product has (the chain's scratch and the caller's
+   * hipMalloc'ed array are 256-byte aligned): up to 15 bytes in front to get there, nothing behind the (ncols - 2) Zc bytes */
+  std::vector<uint8_t> o2((size_t)(code->ncols - 2) * Zc + 15);
   uint8_t *oa = reinterpret_cast<uint8_t *>((reinterpret_cast<uintptr_t>(o2.data()) + 15) & ~(uintptr_t)15);
   for (int tid = 0; tid < nt; tid++)
     ldpc_encp32_store_bytes(L, g, oa, 2, code->ncols, tid, nt);
@@ -245,7 +249,7 @@ extern "C" int ldpc_emul_decode_fast(int BG, int Z, int R, int numMaxIter, int o
   const ldpc_code_desc_t *code = &code_s;
   if (!code->f_ok)
     return -2;
-  std::vector<uint32_t> smem32((code->f_lds_total + 3) / 4 + 4, 0x5a5a5a5au);
+  std::vector<uint32_t> smem32((code->f_lds_total + 3) / 4, 0x5a5a5a5au); /* exactly the LDS the kernel is launched with */
   uint8_t *fsm = reinterpret_cast<uint8_t *>(smem32.data());
   const int zq = code->f_zq, rstride = code->f_rstride, astride = code->f_astride;
   const uint32_t zq_magic = code->f_zq_magic, z_magic = 0xffffffffu / (uint32_t)Z + 1u;
@@ -261,7 +265,7 @@ extern "C" int ldpc_emul_decode_fast(int BG, int Z, int R, int numMaxIter, int o
   L.etbl = etbl; L.ctbl = ctbl; L.rowtbl = rowtbl; L.coltbl = coltbl;
   int flags[4] = {0, 0, 0, 0};
   const int nt = code->f_n_threads, ncore = code->ncore, num_llr = code->num_llr, ncz = ncore * Z, nedges = code->nedges;
-  std::vector<uint32_t> src_copy((num_llr + 3) / 4 + 1);
+  std::vector<uint32_t> src_copy((num_llr + 3) / 4); /* num_llr bytes in whole words, as hipMalloc rounds a block's input */
   memcpy(src_copy.data(), llr_in, num_llr);
   const uint32_t *src32 = src_copy.data();
   static const uint32_t polys[4] = {0x864cfb00u, 0x80006300u, 0x10210000u, 0x9B000000u};
@@ -449,7 +453,7 @@ extern "C" int tb_emul_rx_dematch_cut(uint32_t Tbslbrm, int BG, uint32_t Zc, uin
   j.clear = clear ? 1u : 0u;
   j.K = K; j.F = F; j.Z = Zc; j.num_llr = num_llr; j.np_mode = np_mode;
   const tb_rx_geom g = tb_rx_geometry(&j);
-  std::vector<tb_u32x4> lds(g.span / 8 + 1);
+  std::vector<tb_u32x4> lds(g.span / 8); /* span int16 slots, a multiple of 8: exactly the LDS the kernel asks for */
   memset(lds.data(), 0x5a, lds.size() * sizeof(tb_u32x4)); /* poison: phase Z must initialise what is read */
   int16_t *e_lds = reinterpret_cast<int16_t *>(lds.data());
   switch (Qm) {

@@ -83,7 +83,7 @@ extern "C" int tb_emul_rx_dematch_sym(uint32_t Tbslbrm, int BG, uint32_t Zc, uin
   j.K = K; j.F = F; j.Z = Zc; j.num_llr = num_llr;
   j.c_init = c_init; j.bit_off = bit_off; j.plane = plane;
   const tb_rx_geom g = tb_rx_geometry(&j);
-  std::vector<tb_u32x4> lds((g.span * 2 + TB_RX_SCR_LDS) / 16 + 1);
+  std::vector<tb_u32x4> lds((g.span * 2 + TB_RX_SCR_LDS) / 16); /* the image (span a multiple of 8) and the sequence words behind it, no more */
   memset(lds.data(), 0x5a, lds.size() * sizeof(tb_u32x4)); /* poison: phase Z and the staging must initialise what is read */
   int16_t *e_lds = reinterpret_cast<int16_t *>(lds.data());
   const uint32_t *r32 = reinterpret_cast<const uint32_t *>(rec);

@@ -128,16 +128,24 @@ def test_encode_symbols_other_tx_paths(hip, env):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+LAYER_PER = (1, 3, 4, 5, 64, 1001, 4096 + 7)        # points per layer
+LAYER_OFFS = ((0, 0), (2, 2), (1, 2), (0, 1))       # int16 offsets of in and out: 16-byte, 4-byte, 2-byte aligned arrays
+
+
+def layer_strides(per):
+    return (per, per + 3, per + 4)
+
+
 @pytest.mark.parametrize("Nl", [1, 2, 3, 4])
 def test_layer_mapping_host_and_device_against_numpy(hip, Nl):
     import torch
     m = hip.ldpc
     rng = np.random.default_rng(500 + Nl)
-    for per in (1, 3, 4, 5, 64, 1001, 4096 + 7):
+    for per in LAYER_PER:
         n = per * Nl
         pts = rng.integers(-32768, 32768, (n, 2)).astype(np.int16)
         want = layer_map_np(pts, Nl)
-        for stride in (per, per + 3, per + 4):
+        for stride in layer_strides(per):
             got = m.layer_mapping(pts, Nl, layer_stride=stride)
             assert np.array_equal(got[:, :per], want), (Nl, per, stride)
             assert (got[:, per:] == 0).all()
@@ -147,7 +155,7 @@ def test_layer_mapping_host_and_device_against_numpy(hip, Nl):
             assert L.nrLDPC_hip_layer_mapping(pts.ctypes.data, n, Nl, out.ctypes.data, stride, m.MEM_HOST, None) == 0
             o = out[:Nl * stride * 2].reshape(Nl, stride, 2)
             assert np.array_equal(o[:, :per], want) and (o[:, per:] == 0x5a5a).all() and (out[Nl * stride * 2:] == 0x5a5a).all()
-            for off_in, off_out in ((0, 0), (2, 2), (1, 2), (0, 1)):   # int16 offsets: 16-byte, 4-byte, 2-byte aligned arrays
+            for off_in, off_out in LAYER_OFFS:
                 src = torch.zeros(2 * n + 8, dtype=torch.int16, device="cuda")
                 x = src[off_in:off_in + 2 * n]
                 x.copy_(torch.from_numpy(pts.reshape(-1)).cuda())

@@ -41,6 +41,11 @@ MOD_LENGTHS = {2: [2, 6, 30, 34, 190, 1000, 2 * 12345], 4: [4, 12, 28, 36, 188, 
                6: [6, 18, 42, 66, 186, 198, 6 * 13, 6 * 1001, SLOT_G], 8: [8, 24, 56, 72, 184, 200, 8 * 999]}
 
 
+MOD_OFFS = (0, 1, 2)                                # int16 offsets: 16-byte, 4-byte and 2-byte aligned outputs
+LLR_NB_RE = (1, 3, 4, 7, 8, 9, 100, 1001, 4096 + 3)
+LLR_OFFS = (0, 2)                                   # 16-byte aligned planes and output / only 4-byte aligned ones
+
+
 @pytest.mark.parametrize("Qm", [2, 4, 6, 8])
 def test_modulation_host_and_device_against_numpy(hip, Qm):
     import torch
@@ -52,7 +57,7 @@ def test_modulation_host_and_device_against_numpy(hip, Qm):
         want = modulate_np(words, length, Qm)
         got = m.modulation(words[:nw], length, Qm)
         assert np.array_equal(got, want), (Qm, length)
-        for off in (0, 1, 2):                       # 16-byte, 4-byte and 2-byte aligned outputs
+        for off in MOD_OFFS:
             out = torch.full((2 * (length // Qm) + off + 8,), 0x5a5a, dtype=torch.int16, device="cuda")
             m.modulation(torch.from_numpy(words[:nw].view(np.int32)).cuda(), length, Qm, out=out[off:])
             torch.cuda.synchronize()
@@ -67,11 +72,11 @@ def test_ulsch_llr_host_and_device_against_numpy(hip, Qm):
     import torch
     m = hip.ldpc
     rng = np.random.default_rng(200 + Qm)
-    for nb_re in (1, 3, 4, 7, 8, 9, 100, 1001, 4096 + 3):
+    for nb_re in LLR_NB_RE:
         y, mags = edge_symbols(rng, nb_re, Qm)
         want = demap_np(y, mags, Qm)
         assert np.array_equal(m.ulsch_llr(y, mags, Qm), want), (Qm, nb_re)
-        for off in (0, 2):                          # 16-byte aligned planes and output / only 4-byte aligned ones
+        for off in LLR_OFFS:
             dev = []
             for a in [y] + mags:
                 t = torch.zeros(2 * nb_re + off, dtype=torch.int16, device="cuda")

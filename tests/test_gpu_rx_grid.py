@@ -86,16 +86,23 @@ def grid_case(rng, Qm, n_rx):
     return segs, ext_segs, rx, ch, rx_stride, ch_stride, rx_e, ch_e, shift, want
 
 
-@pytest.mark.parametrize("n_rx,Qm", [(1, 6), (2, 6), (3, 6), (4, 6), (8, 6), (2, 2), (2, 4), (2, 8)])
+def measurement_symbols(segs, n_rx):
+    """indices into grid_case's segments: a DMRS1 / DMRS2 / FULL segment of 3 RBs per block, rotating; any order"""
+    pick = lambda tb, pat: next(i for i, s in enumerate(segs) if s["tb"] == tb and s["pattern"] == pat and s["nb_re"] == PER_RB[pat] * 3)
+    return [pick(1, (n_rx + 1) % 3), pick(0, n_rx % 3)]
+
+
+GRID_PARAMS = [(1, 6), (2, 6), (3, 6), (4, 6), (8, 6), (2, 2), (2, 4), (2, 8)]
+
+
+@pytest.mark.parametrize("n_rx,Qm", GRID_PARAMS)
 def test_grid_compensation_and_level(hip, n_rx, Qm):
     import torch
     m = hip.ldpc
     rng = np.random.default_rng(2000 * Qm + n_rx)
     segs, ext_segs, rx, ch, rx_stride, ch_stride, rx_e, ch_e, shift, want = grid_case(rng, Qm, n_rx)
     n_ext = rx_e.shape[1]
-    # measurement symbols: a DMRS1 / DMRS2 / FULL segment of 3 RBs per block, rotating; any order
-    pick = lambda tb, pat: next(i for i, s in enumerate(segs) if s["tb"] == tb and s["pattern"] == pat and s["nb_re"] == PER_RB[pat] * 3)
-    fi = [pick(1, (n_rx + 1) % 3), pick(0, n_rx % 3)]
+    fi = measurement_symbols(segs, n_rx)
     first, ext_first = [segs[i] for i in fi], [ext_segs[i] for i in fi]
     lv_want = np.array([level_np(extract_np(rx, ch, segs[i])[1])[0] for i in fi[::-1]], np.int32)
     rx0, ch0 = rx.copy(), ch.copy()

@@ -107,10 +107,8 @@ def test_mmse_grid_equals_numpy(hip, n_rx, Qm):
     assert np.array_equal(rx_d.cpu().numpy(), rx0.reshape(-1)) and np.array_equal(ch_d.cpu().numpy(), ch0.reshape(-1))
 
 
-@pytest.mark.parametrize("n_rx", [2, 4])
-def test_level_grid_mmse_equals_numpy(hip, n_rx):
-    import torch
-    m = hip.ldpc
+def level_case(n_rx):
+    """three blocks' measurement symbols, one of each pattern, named in any order; estimates of three sizes"""
     rng = np.random.default_rng(70 + n_rx)
     N, cs = 512, 3 * 512 + 40
     ch = (rng.integers(-32768, 32768, (2 * n_rx, cs, 2)) >> np.array([0, 4, 6])[rng.integers(0, 3, (2 * n_rx, 1, 1))]).astype(np.int16)
@@ -118,6 +116,14 @@ def test_level_grid_mmse_equals_numpy(hip, n_rx):
              dict(tb=0, Qm=8, pattern=FULL, nb_re=300, plane=800, sym_off=0, fft_size=N, start_re=3, rx_off=0, ch_off=N + 1, rec_off=0),
              dict(tb=1, Qm=6, pattern=DMRS2, nb_re=8 * 13, plane=400, sym_off=0, fft_size=N, start_re=0, rx_off=0, ch_off=2 * N + 9, rec_off=0)]
     max_ch = np.array([1500, 2048, 32767], np.int32)                              # shift_ch_ext 0, 1, 4: both branches of the scale
+    return ch, cs, first, max_ch
+
+
+@pytest.mark.parametrize("n_rx", [2, 4])
+def test_level_grid_mmse_equals_numpy(hip, n_rx):
+    import torch
+    m = hip.ldpc
+    ch, cs, first, max_ch = level_case(n_rx)
     want = np.zeros(3, np.int32)
     for f in first:
         pairs = extract_np(ch[:1], ch, f)[1].reshape(2, n_rx, f["nb_re"], 2)
