@@ -39,7 +39,11 @@
 #else
 #define LDPC_HD static inline
 #define LDPC_CONST_AS
+/* (x) is right where one host thread walks the lanes one after the other (tests/emul/ldpc_emul.cpp); an emulation with a thread
+ * per lane supplies a broadcast of lane 0's value */
+#ifndef LDPC_UNIFORM
 #define LDPC_UNIFORM(x) (x)
+#endif
 #endif
 typedef const ldpc_code_desc_t LDPC_CONST_AS *ldpc_code_ptr_t;
 typedef const uint32_t LDPC_CONST_AS *ldpc_u32c_ptr_t;

@@ -357,6 +357,14 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
          * on, the eager check from pass 2 on), so it is not accumulated and the bodies drop it as dead code */
         uint32_t m = 0;
         (void)half;
+#if !defined(__HIP_DEVICE_COMPILE__)
+        /* host build (the CPU emulation with a thread per lane, tests/emul/): ldpc_fast_cn19_pair is device code, so the even
+         * lane of a pair runs the whole item below and the odd one does nothing -- two in-place updates of one row otherwise.
+         * The `continue` goes to the loop's increment on purpose: the odd lane must still take part in its wave's ldpc_draw
+         * there, or the wave hangs */
+        if (pair && half)
+          continue;
+#endif
         bool mute = false;
         if constexpr (!IO::syndrome && IO::mute_items)
           mute = mute_check && ext && ldpc_fast_item_is_mute(L, e0, deg, j);

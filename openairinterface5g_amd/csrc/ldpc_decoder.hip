@@ -16,7 +16,7 @@
 
 __global__ void __launch_bounds__(1024) ldpc_dec_generic_kernel(const ldpc_dec_args a)
 {
-  extern __shared__ __attribute__((aligned(16))) int8_t smem[];
+  LDPC_DYNAMIC_LDS(int8_t, smem);
   /* job records and descriptors are read through the constant address space: uniform address -> scalar loads,
    * so everything derived from them stays in SGPRs */
   typedef const ldpc_dec_job LDPC_CONST_AS *job_ptr_t;
@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(1024) ldpc_dec_generic_kernel(const ldpc_dec_a
  * trace + (b * n_trace + p - 3) * trace_stride).  A kernel of its own so that the hot kernels' argument block stays as it is. */
 __global__ void __launch_bounds__(1024) ldpc_dec_generic_trace_kernel(const ldpc_dec_args a, int8_t *trace, uint32_t trace_stride, uint32_t n_trace)
 {
-  extern __shared__ __attribute__((aligned(16))) int8_t smem[];
+  LDPC_DYNAMIC_LDS(int8_t, smem);
   ldpc_code_ptr_t code = (ldpc_code_ptr_t)a.code;
   const uint32_t blk = blockIdx.x;
   ldpc_gblock_io io;

@@ -74,7 +74,7 @@ template <bool JOBS, bool CRC = false, bool TRACE = false> struct ldpc_batch_io 
 template <bool JOBS, bool CRC = false, bool TRACE = false, int ZC = 0>
 __global__ void __launch_bounds__(1024) ldpc_dec_fast_kernel(const ldpc_dec_args a)
 {
-  extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
+  LDPC_DYNAMIC_LDS(uint8_t, fsm);
   /* job records and descriptors are read through the constant address space: uniform address -> scalar loads,
    * so everything derived from them stays in SGPRs */
   const ldpc_job_ptr_t job = JOBS ? (ldpc_job_ptr_t)a.jobs + blockIdx.x : (ldpc_job_ptr_t) nullptr;
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(1024) ldpc_dec_fast_kernel(const ldpc_dec_args
 template <bool CRC>
 __global__ void __launch_bounds__(1024) ldpc_dec_fast_pull_kernel(const ldpc_dec_args a)
 {
-  extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
+  LDPC_DYNAMIC_LDS(uint8_t, fsm);
   ldpc_code_ptr_t code = (ldpc_code_ptr_t)a.code;
   const int nb = code->num_llr, tid = (int)threadIdx.x, nt = (int)blockDim.x; /* Zc % 4 == 0: a multiple of 4 bytes */
   const uint8_t *src = reinterpret_cast<const uint8_t *>(a.pull) + (size_t)blockIdx.x * a.pull_stride;
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(1024) ldpc_dec_fast_pull_kernel(const ldpc_dec
 template <int SUB, bool CRC>
 __global__ void __launch_bounds__(1024) ldpc_dec_fast_multi_kernel(const ldpc_dec_args a)
 {
-  extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
+  LDPC_DYNAMIC_LDS(uint8_t, fsm);
   ldpc_code_ptr_t code = (ldpc_code_ptr_t)a.code;
   const uint32_t per_wg = (uint32_t)code->f_mb * SUB;
   const uint32_t first = blockIdx.x * per_wg;
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(1024) ldpc_dec_fast_multi_kernel(const ldpc_de
 template <int SUB, bool CRC>
 __global__ void __launch_bounds__(1024) ldpc_dec_fast_multi_jobs_kernel(const ldpc_dec_args a)
 {
-  extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
+  LDPC_DYNAMIC_LDS(uint8_t, fsm);
   typedef const ldpc_dec_mgroup LDPC_CONST_AS *grp_ptr_t;
   const grp_ptr_t gr = (grp_ptr_t)a.mgroups + blockIdx.x;
   ldpc_code_ptr_t code = (ldpc_code_ptr_t)gr->code;

@@ -9,6 +9,12 @@
 
 #define LDPC_CRC_POW_LEN 8448 /* x^j mod g for j < 8448 = largest code block */
 
+/* a kernel's dynamic LDS (the launch's lds_bytes).  The CPU emulation of the kernels (tests/emul/) supplies a meaning of its own:
+ * a heap buffer of exactly that many bytes */
+#ifndef LDPC_DYNAMIC_LDS
+#define LDPC_DYNAMIC_LDS(type, name) extern __shared__ __attribute__((aligned(16))) type name[]
+#endif
+
 /* heterogeneous batches (transport-block chain): one job per workgroup overrides code / buffers / E / crc */
 #define LDPC_JOB_MUTE_CHECK 0x100
 struct ldpc_dec_job {
@@ -100,10 +106,12 @@ bool ldpc_fast_zc_enabled(int zc); /* is there an instantiation for this lifting
 #ifndef LDPC_FAST_ZC
 #define LDPC_FAST_ZC 1
 #endif
+#ifndef LDPC_FAST_ZC_LIST /* (the sanitized CPU build of the kernels, tests/emul/dec_emul_san.cpp, compiles one of them) */
 #if LDPC_FAST_ZC
 #define LDPC_FAST_ZC_LIST(X) X(384) X(352) X(320) X(288) X(256) X(208)
 #else
 #define LDPC_FAST_ZC_LIST(X)
+#endif
 #endif
 hipError_t ldpc_launch_enc_jobs(const ldpc_enc_args &a, int n_threads, int lds_bytes, uint32_t n_blocks, hipStream_t stream);
 /* fast decoder (Zc % 4 == 0, 4-byte aligned LLR rows, hc.f_ok): one workgroup per code block */

@@ -26,7 +26,9 @@
 #include <stdint.h>
 #include "tb_jobs.h"
 #include "nr_qam.h"
-#if defined(__HIPCC__)
+/* TB_RX_BLOCK_PHASES: a host build that has meanings for threadIdx, __syncthreads() and the wave votes (the CPU emulation with a
+ * thread per work-item, tests/emul/rx_fused_emul.cpp) takes the block-level functions at the end of this file too */
+#if defined(__HIPCC__) || defined(TB_RX_BLOCK_PHASES)
 #include "nr_gold_dev.h"
 #endif
 
@@ -371,7 +373,7 @@ TB_RX_HD void tb_rx_phase_stream(const tb_rx_geom &g, const int16_t *e_lds, int1
   }
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) || defined(TB_RX_BLOCK_PHASES)
 /* the phases with their barriers, executed by every thread of the workgroup (wave-uniform arguments).  Only the loads and
  * the scatter are compiled per modulation order; the clearing and the streaming phase exist once. */
 __device__ __forceinline__ void tb_rx_dematch_block(const tb_rx_geom &g, uint32_t Qm, const int16_t *__restrict__ f, int16_t *__restrict__ w,

@@ -35,7 +35,12 @@ typedef const tb_rx_tb_job LDPC_CONST_AS *tb_tb_ptr_t;
 
 /* stores / loads that other workgroups (other XCDs: other L2s) or the host may look at while the kernel runs */
 template <class T> __device__ __forceinline__ void tb_store_out(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-__device__ __forceinline__ void tb_wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void tb_wait_stores()
+{
+#if defined(__HIP_DEVICE_COMPILE__) /* (a host build -- the CPU emulation of this file, tests/emul/ -- has nothing to wait for) */
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+}
 
 /* LROW: the decoder input lives in the workgroup's LDS (tb_rx_fused_args.lrow_off) -- a compile-time property, so that the
  * block body's reads of the channel LLRs are LDS instructions and not flat ones */
@@ -223,7 +228,7 @@ template <bool LROW, bool MUTE = false> struct tb_rx_fused_io {
 template <bool LROW, bool MUTE, int ZC = 0, bool SCR = false, bool SYM = false>
 __global__ void __launch_bounds__(1024) tb_rx_fused_kernel(const ldpc_dec_args a, const tb_rx_fused_args x)
 {
-  extern __shared__ __attribute__((aligned(16))) uint8_t fsm[];
+  LDPC_DYNAMIC_LDS(uint8_t, fsm);
   const ldpc_job_ptr_t job = (ldpc_job_ptr_t)a.jobs + blockIdx.x;
   ldpc_code_ptr_t code = (ldpc_code_ptr_t)job->code;
   tb_rx_fused_io<LROW, MUTE> io{a, x, job, fsm};
