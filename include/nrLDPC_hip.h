@@ -512,7 +512,7 @@ int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, ui
  * max_ch and nvar come out of the reference's channel estimator (nr_ul_channel_estimation.c:187, :468-469); the estimator
  * here does not produce them, so they are inputs, one value per tb like shift, read from device memory in DEVICE mode.
  * mem modes, staging and refusals are those of the _grid calls; further refusals: Qm other than 6 or 8 (two layers of QPSK /
- * 16QAM take the ML receiver, which writes LLRs and is not built), n_rx other than 2 or 4, 2 (sym_off + nb_re) > plane, a NULL
+ * 16QAM take the ML receiver, which writes LLRs: the _ml calls below), n_rx other than 2 or 4, 2 (sym_off + nb_re) > plane, a NULL
  * nvar / max_ch or (DEVICE) one that is not device memory of that GPU, two segments whose doubled output ranges overlap.
  * One deviation: where the reference aborts (AssertFatal :1181, a determinant lane <= 0) the arithmetic goes on with what the
  * instructions give (a quad of zero determinants: b = -8); such a block fails its CRC.
@@ -529,6 +529,46 @@ int32_t nrLDPC_hip_ulsch_mmse_2layers_host(const int16_t *rxFext, const int16_t 
                                            uint8_t Qm, int32_t shift, uint32_t nvar, int16_t *out);
 int32_t nrLDPC_hip_ulsch_level_mmse_host(const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re, int32_t max_ch,
                                          int32_t *avg, int32_t *log2_maxh);
+/* Two layers, QPSK and 16QAM: the reference's max-log ML receiver (inner_rx, nr_ulsch_demodulation.c:1348-1389: Qm < 6 goes
+ * through nr_ulsch_compute_ML_llr, nr_ulsch_llr_computation.c:2100-2129) from the OFDM grid and the per-layer channel estimates
+ * to LLRs in codeword order, the array nrLDPC_hip_ulsch_decode_scrambled reads; csrc/nr_rx_ml.h has the arithmetic, in the
+ * 256-bit variants an x86 build of the reference takes.  The descriptors, the pairs and their layout are those of the _mmse
+ * calls above (pusch_grid_segments derives them: plane = G/Qm = twice the allocation's REs, sym_off counted per layer, rec_off =
+ * the block's coded_off in int16, even); n_rx = 1..8 (2 and 4 have kernels of their own, the rest take a loop).  nvar is not an
+ * input: the ML path does not use it.
+ *   ml_2layers_grid: per RE the two layers' matched filters and ul_ch_maga over the antennas (:505-548), rho[0][1] and rho[1][0],
+ *     each the saturating sum over the antennas in order of pack(conj(h_l) h_l' >> s) (:550-570; formed separately, as written:
+ *     the arithmetic shift makes them differ from each other's conjugate by rounding), s = shift[tb] clamped to 0..31; then per
+ *     layer nr_ulsch_qpsk_qpsk (:528-682) with nr_ulsch_shift_llr's >> 4 (:2076-2098), or nr_ulsch_qam16_qam16 (:1124-1350) --
+ *     layer 1 is the same function with the streams, magnitudes and rho swapped (:2115-2121).  QPSK forms num - den, 16QAM
+ *     den - num, as written.  Layer de-mapping (nr_ulsch_demodulation.c:1431-1438) is in the store: bit m of layer l of the
+ *     segment's RE r is int16 rec_off + Qm (2 (sym_off + r) + l) + m.  The write set per segment is exactly int16 rec_off + 2 Qm
+ *     sym_off .. rec_off + 2 Qm (sym_off + nb_re) - 1, overwritten.  Qm is per segment; one call may mix 2 and 4.
+ *   channel_level_grid_ml: log2_maxh[tb] = max(0, log2_approx(avgs) >> 1) (:1639-1647: neither the MMSE's - 3 nor the single
+ *     layer's term), avgs and the scaling by max_ch[tb] as in channel_level_grid_mmse.
+ * Three deviations, all in which REs are computed, none in an RE's value.  The reference's loops run `for (i = 0; i <
+ * length >> 3; i += 2)` over 16 REs each, so (1) when nb_re >> 3 is even and nb_re % 8 != 0 (18, 20, 36 REs; 3 or 11 PRBs) its
+ * last nb_re % 8 REs are never computed and their LLRs are whatever the buffer held, and (2) when nb_re >> 3 is odd it computes
+ * and stores up to 8 REs behind nb_re; (3) nr_ulsch_shift_llr shifts 4 (nb_re >> 2) REs from an address-dependent start, so some
+ * QPSK REs are shifted never or twice.  Here exactly nb_re REs per segment are computed, each by the per-RE definition, QPSK
+ * LLRs are shifted exactly once, and nothing behind nb_re is written.
+ * mem modes and staging are those of the _grid calls (HOST stages only the ranges the descriptors reach and copies back only
+ * the segments' entries).  Refused before anything is enqueued or written: everything channel_compensation_grid refuses; Qm
+ * other than 2 or 4 (64QAM / 256QAM take mmse_2layers_grid); n_rx outside 1..8; 2 (sym_off + nb_re) > plane; two segments whose
+ * output ranges overlap; a NULL max_ch or (DEVICE) one that is not device memory of that GPU; a capturing stream.
+ * ml_2layers_host / level_ml_host: the same arithmetic on the CPU, no GPU involved, for checking: one segment from extracted
+ * arrays (chFext: the 2 n_rx pairs ant_stride apart, rxFext: the n_rx antennas ant_stride apart; out = 2 nb_re Qm int16, bit m
+ * of layer l of RE r at Qm (2 r + l) + m) / one block (avg, when not NULL, receives the 2 n_rx averages).  0 / -1. */
+int32_t nrLDPC_hip_ulsch_channel_level_grid_ml(const int16_t *ul_ch, uint32_t n_rx, uint64_t ch_ant_stride,
+                                               const nrLDPC_hip_rx_grid_seg_t *first_sym, uint32_t n_tb, const int32_t *max_ch,
+                                               int32_t *log2_maxh, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_ml_2layers_grid(const int16_t *rxdataF, const int16_t *ul_ch, uint32_t n_rx, uint64_t rx_ant_stride,
+                                         uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, const int32_t *shift,
+                                         int16_t *llr, int32_t mem, void *stream);
+int32_t nrLDPC_hip_ulsch_ml_2layers_host(const int16_t *rxFext, const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re,
+                                         uint8_t Qm, int32_t shift, int16_t *out);
+int32_t nrLDPC_hip_ulsch_level_ml_host(const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re, int32_t max_ch,
+                                       int32_t *avg, int32_t *log2_maxh);
 /* ---------------------------------------------------------------------------------------------------
  * PUSCH DMRS channel estimation from the OFDM grid: nr_pusch_channel_estimation (openair1/PHY/NR_ESTIMATION/
  * nr_ul_channel_estimation.c:67-473) for one list of descriptors, one per (allocation, DMRS symbol), times n_rx antennas.  It

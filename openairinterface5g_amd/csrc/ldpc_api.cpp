@@ -39,6 +39,8 @@
 #include "tb_rx_front.h"
 #include "nr_rx_mmse.h"
 #include "tb_rx_mmse.h"
+#include "nr_rx_ml.h"
+#include "tb_rx_ml.h"
 #include "ldpc_enc_packed_core.h"
 
 namespace {
@@ -1529,6 +1531,7 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "rx_front_api.inc.cpp"
 #include "rx_grid_api.inc.cpp"
 #include "rx_mmse_api.inc.cpp"
+#include "rx_ml_api.inc.cpp"
 #include "rx_chest_api.inc.cpp"
 #include "tx_map_api.inc.cpp"
 #include "tx_precode_api.inc.cpp"

@@ -1,8 +1,8 @@
 /*
  * rx_plan.h -- what the UL receive front's calls derive from their descriptors before anything is enqueued: the descriptor
- * checks, the job lists, the c16 ranges of the caller's arrays they reach, and the workgroup tables of tb_rx_front.hip and
- * tb_rx_mmse.hip.  Plain arithmetic (slot_plan.h): rx_front_api.inc.cpp, rx_grid_api.inc.cpp and rx_mmse_api.inc.cpp run it in
- * front of their DEVICE and HOST scopes, and the CPU emulation of the kernels (tests/emul/) runs the same code.
+ * checks, the job lists, the c16 ranges of the caller's arrays they reach, and the workgroup tables of tb_rx_front.hip,
+ * tb_rx_mmse.hip and tb_rx_ml.hip.  Plain arithmetic (slot_plan.h): rx_front_api.inc.cpp, rx_grid_api.inc.cpp, rx_mmse_api.inc.cpp
+ * and rx_ml_api.inc.cpp run it in front of their DEVICE and HOST scopes, and the CPU emulation of the kernels (tests/emul/) runs the same code.
  */
 #ifndef RX_PLAN_H
 #define RX_PLAN_H
@@ -11,6 +11,7 @@
 #include "nr_rx_grid.h"
 #include "nr_rx_mmse.h"
 #include "tb_rx_front.h"
+#include "tb_rx_ml.h"
 
 namespace {
 
@@ -241,7 +242,7 @@ int rxm_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx,
     if (rxg_check_seg("mmse_2layers_grid", g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
       return -1;
     if (g.Qm != 6 && g.Qm != 8)
-      return set_error("mmse_2layers_grid: Qm must be 6 or 8 (two layers of QPSK / 16QAM take the ML receiver, which is not built)");
+      return set_error("mmse_2layers_grid: Qm must be 6 or 8 (two layers of QPSK / 16QAM take the ML receiver, ml_2layers_grid)");
     if (g.rec_off & 1u)
       return set_error("mmse_2layers_grid: rec_off must be even");
     if (2u * ((uint64_t)g.sym_off + g.nb_re) > g.plane)
@@ -289,6 +290,71 @@ void rxm_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_b
     j.out_off -= out_bias;
     const uint32_t quads = (j.nb_re + NR_RXM_QUAD - 1u) / NR_RXM_QUAD;
     for (uint32_t q = 0; q * NR_RXF_THREADS < quads; q++)
+      p.wgs.push_back(rx_front_wg{(uint32_t)i, q});
+  }
+}
+
+/* ---- the two-layer max-log ML receiver (rx_ml_api.inc.cpp) ---- */
+/* the checks, the jobs, the output ranges in 32-bit words of the LLR array (a segment fills words rec_off / 2 + Qm sym_off ..
+ * + Qm nb_re - 1: Qm / 2 words per layer and RE, the two layers of an RE side by side) and the input ranges: n_rx antennas of the
+ * grid, 2 n_rx pairs of the estimates */
+int rxl_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
+             std::vector<rx_front_grid_job> &gj)
+{
+  std::vector<Range64> out;
+  gj.reserve(n_seg);
+  for (uint32_t i = 0; i < n_seg; i++) {
+    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
+    if (rxg_check_seg("ml_2layers_grid", g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
+      return -1;
+    if (g.Qm != 2 && g.Qm != 4)
+      return set_error("ml_2layers_grid: Qm must be 2 or 4 (two layers of 64QAM / 256QAM take the MMSE receiver, mmse_2layers_grid)");
+    if (g.rec_off & 1u)
+      return set_error("ml_2layers_grid: rec_off must be even");
+    if (2u * ((uint64_t)g.sym_off + g.nb_re) > g.plane)
+      return set_error("ml_2layers_grid: 2 (sym_off + nb_re) above plane");
+    if (2u * (uint64_t)g.nb_re * g.Qm > NR_SCR_MAX_BITS)
+      return set_error("ml_2layers_grid: 2 nb_re * Qm above 2^21");
+    p.n_shift = std::max(p.n_shift, g.tb + 1u);
+    if (g.nb_re == 0)
+      continue;
+    const uint64_t first = g.rec_off / 2u + (uint64_t)g.Qm * g.sym_off;
+    out.push_back(Range64{first, first + (uint64_t)g.Qm * g.nb_re});
+    uint64_t lo, hi;
+    rxg_rx_range(g, lo, hi);
+    p.rx_lo = std::min(p.rx_lo, lo);
+    p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
+    p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
+    p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(2u * n_rx - 1u) * ch_stride);
+    rx_front_grid_job j{};
+    j.s.rx_off = g.rx_off;
+    j.s.ch_off = g.ch_off;
+    j.s.out_off = first;
+    j.s.plane = g.plane;
+    j.s.nb_re = g.nb_re;
+    j.s.tb = g.tb;
+    j.s.Qm = g.Qm;
+    j.pattern = g.pattern;
+    j.fft_size = g.fft_size;
+    j.start_re = g.start_re;
+    gj.push_back(j);
+  }
+  if (ranges_overlap(out, p.out_lo, p.out_hi))
+    return set_error("ml_2layers_grid: the output ranges of two segments overlap");
+  return 0;
+}
+
+/* offsets relative to the copies' starts (staged; see rxg_place for the wrap below zero) and the workgroup table: a workgroup
+ * takes NR_RXF_THREADS groups of NR_RXL_GROUP REs of a segment, counted from its RE 0 */
+void rxl_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias)
+{
+  for (size_t i = 0; i < gj.size(); i++) {
+    rx_front_seg_job &j = gj[i].s;
+    j.rx_off -= rx_bias;
+    j.ch_off -= ch_bias;
+    j.out_off -= out_bias;
+    const uint32_t groups = (j.nb_re + NR_RXL_GROUP - 1u) / NR_RXL_GROUP;
+    for (uint32_t q = 0; q * NR_RXF_THREADS < groups; q++)
       p.wgs.push_back(rx_front_wg{(uint32_t)i, q});
   }
 }

@@ -1439,6 +1439,92 @@ def ulsch_mmse_2layers_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, sh
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Two-layer max-log ML receiver for QPSK / 16QAM (include/nrLDPC_hip.h: the _ml calls; csrc/nr_rx_ml.h)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_ulsch_channel_level_grid_ml", "nrLDPC_hip_ulsch_ml_2layers_grid", "nrLDPC_hip_ulsch_ml_2layers_host",
+            "nrLDPC_hip_ulsch_level_ml_host"]
+
+
+def _rxl_lib():
+    L = _rxg_lib()
+    P = C.POINTER(nrLDPC_hip_rx_grid_seg_t)
+    L.nrLDPC_hip_ulsch_channel_level_grid_ml.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, P, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                         C.c_void_p]
+    L.nrLDPC_hip_ulsch_channel_level_grid_ml.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_ml_2layers_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, P, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_ml_2layers_grid.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_ml_2layers_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint8, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_ulsch_ml_2layers_host.restype = C.c_int32
+    L.nrLDPC_hip_ulsch_level_ml_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.nrLDPC_hip_ulsch_level_ml_host.restype = C.c_int32
+    return L
+
+
+def _rxl_check_llr(segs, llr_len):
+    """a segment's write set must lie inside `llr` (llr_len in int16)"""
+    for s in segs:
+        if s["nb_re"] and s["Qm"] in (2, 4) and s["rec_off"] + 2 * s["Qm"] * (s["sym_off"] + s["nb_re"]) > llr_len:
+            raise ValueError("a segment's LLRs leave the array")
+
+
+def ulsch_ml_2layers_host(rx, ch, n_rx, ant_stride, nb_re, Qm, shift):
+    """The two-layer max-log ML receiver for one segment on the CPU (csrc/nr_rx_ml.h, no GPU): rx = numpy int16 c16, antenna a's
+    RE r at c16 index a * ant_stride + r; ch the same for pair l * n_rx + a.  Returns int16[nb_re, 2, Qm]: per RE and layer the
+    Qm LLRs, the order of the codeword."""
+    rx, ch = np.ascontiguousarray(rx, np.int16).reshape(-1), np.ascontiguousarray(ch, np.int16).reshape(-1)
+    if 1 <= n_rx <= 8:
+        assert rx.size >= 2 * ((n_rx - 1) * ant_stride + nb_re) and ch.size >= 2 * ((2 * n_rx - 1) * ant_stride + nb_re)
+    q = Qm if Qm in (2, 4) else 2
+    out = np.zeros(max(nb_re, 1) * 2 * q, np.int16)
+    _check(_rxl_lib().nrLDPC_hip_ulsch_ml_2layers_host(rx.ctypes.data, ch.ctypes.data, n_rx, ant_stride, nb_re, Qm, shift, out.ctypes.data),
+           "nrLDPC_hip_ulsch_ml_2layers_host")
+    return out[:nb_re * 2 * q].reshape(nb_re, 2, q)
+
+
+def ulsch_level_ml_host(ch, n_rx, ant_stride, nb_re, max_ch):
+    """The channel level of one two-layer QPSK / 16QAM block's measurement symbol on the CPU (no GPU): (log2_maxh, int32[2 n_rx]
+    averages)."""
+    ch = np.ascontiguousarray(ch, np.int16).reshape(-1)
+    if 1 <= n_rx <= 8:
+        assert ch.size >= 2 * ((2 * n_rx - 1) * ant_stride + nb_re)
+    avg, out = np.zeros(16, np.int32), np.zeros(1, np.int32)
+    _check(_rxl_lib().nrLDPC_hip_ulsch_level_ml_host(ch.ctypes.data, n_rx, ant_stride, nb_re, max_ch, avg.ctypes.data, out.ctypes.data),
+           "nrLDPC_hip_ulsch_level_ml_host")
+    return int(out[0]), avg[:2 * n_rx]
+
+
+def ulsch_channel_level_grid_ml(ch, n_rx, ch_ant_stride, first_sym, max_ch, out=None, stream=None):
+    """nrLDPC_hip_ulsch_channel_level_grid_ml: the arguments of ulsch_channel_level_grid_mmse; n_rx = 1..8."""
+    n, res = len(first_sym), _level_out(ch, out, len(first_sym))
+    if isinstance(ch, np.ndarray) and max_ch is not None:
+        max_ch = np.ascontiguousarray(max_ch, np.int32)
+    ptr, numel, mem, s = _mem_of((ch,), stream, (res,) if max_ch is None else (res, max_ch))
+    assert max_ch is None or numel(max_ch) >= n
+    _rxg_check_extent(first_sym, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _check(_rxl_lib().nrLDPC_hip_ulsch_channel_level_grid_ml(ptr(ch), n_rx, ch_ant_stride, _rx_grid_seg_array(first_sym), n,
+                                                             None if max_ch is None else ptr(max_ch), ptr(res), mem, s),
+           "nrLDPC_hip_ulsch_channel_level_grid_ml")
+    return res[:n] if mem == MEM_HOST else res
+
+
+def ulsch_ml_2layers_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, shift, llr, stream=None):
+    """nrLDPC_hip_ulsch_ml_2layers_grid: rx = the OFDM grid (n_rx antennas), ch = the full-width channel estimates (2 n_rx pairs),
+    segs = the grid descriptors (pusch_grid_segments with plane = G/Qm, rec_off = the block's coded_off); shift = int32 per block
+    (the output of ulsch_channel_level_grid_ml); llr = the int16 array ulsch_decode_scrambled reads, written in place -- only the
+    segments' entries.  numpy arrays -> host call; torch CUDA tensors -> device call enqueued on `stream`.  Returns `llr`."""
+    if isinstance(rx, np.ndarray):
+        shift = np.ascontiguousarray(shift, np.int32)
+    ptr, numel, mem, s = _mem_of((rx, ch, llr), stream, (shift,))
+    _rxg_check_extent(segs, n_rx, rx_ant_stride, 0, numel(rx) // 2, None)
+    _rxg_check_extent(segs, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _rxl_check_llr(segs, numel(llr))
+    _check(_rxl_lib().nrLDPC_hip_ulsch_ml_2layers_grid(ptr(rx), ptr(ch), n_rx, rx_ant_stride, ch_ant_stride, _rx_grid_seg_array(segs), len(segs),
+                                                       ptr(shift), ptr(llr), mem, s), "nrLDPC_hip_ulsch_ml_2layers_grid")
+    return llr
+
+
+# ---------------------------------------------------------------------------------------------------------
 # PUSCH DMRS channel estimation (include/nrLDPC_hip.h: pusch_channel_estimation and its host forms; csrc/nr_chest.h)
 # ---------------------------------------------------------------------------------------------------------
 EXPORTS += ["nrLDPC_hip_pusch_channel_estimation", "nrLDPC_hip_pusch_chest_host", "nrLDPC_hip_pusch_dmrs_host", "nrLDPC_hip_delay_table_host",
