@@ -1,6 +1,6 @@
 /*
  * rx_grid_api.inc.cpp -- the UL receive front read from the OFDM grid: the _grid forms of the two calls of
- * rx_front_api.inc.cpp (they use its scatter and the call scopes of slot_call.inc.cpp), the CPU extraction for checking, and the
+ * rx_front_api.inc.cpp (they use its scatter and its two call bodies, rx_level_call and rx_receiver_call), the CPU extraction for checking, and the
  * descriptors of a PUSCH allocation.  Where the REs lie: nr_rx_grid.h; the kernels: tb_rx_front.hip.  Everything the kernels
  * index with is checked before anything is enqueued: the grid checks, ranges and plan are rx_plan.h's.
  */
@@ -98,53 +98,16 @@ int32_t nrLDPC_hip_ulsch_channel_compensation_grid(const int16_t *rxdataF, const
   std::vector<rx_front_grid_job> gj;
   if (rxg_plan_compensation(seg, n_seg, n_rx, rx_ant_stride, ch_ant_stride, p, gj) != 0)
     return -1;
-  if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    if (n_seg == 0)
-      return 0;
-    DeviceCall dc;
-    if (dc.open("channel_compensation_grid", {{records, 4}, {rxdataF, 4}, {ul_ch, 4}, {shift, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 ||
-        dc.refuse_capture("channel_compensation_grid") != 0)
-      return -1;
-    if (gj.empty())
-      return 0;
-    rxg_place(p, gj, 0, 0, 0, reinterpret_cast<uintptr_t>(records) >> 2);
-    const auto tab = table2(p.wgs, gj);
-    uint8_t *base = dc.upload(tab);
-    if (!base)
-      return -1;
-    HIP_TRY(nr_launch_rx_compensation_grid(tab.first(base), (uint32_t)p.wgs.size(), tab.second(base), reinterpret_cast<const uint32_t *>(rxdataF),
-                                           reinterpret_cast<const uint32_t *>(ul_ch), n_rx, rx_ant_stride, ch_ant_stride, shift,
-                                           reinterpret_cast<uint32_t *>(records), dc.s));
-    return 0;
-  }
-  if (gj.empty())
-    return 0;
-  StagedCall st;
-  if (st.open() != 0)
-    return -1;
-  /* the device works on copies of the c16 ranges the segments reach; the output keeps the caller's alignment phase */
-  const uint64_t out_pad = p.out_lo & 3u;
-  rxg_place(p, gj, p.rx_lo, p.ch_lo, p.out_lo - out_pad, 0);
-  const auto tab = table2(p.wgs, gj);
-  const size_t rx_n = (size_t)(p.rx_hi - p.rx_lo) * 4u, ch_n = (size_t)(p.ch_hi - p.ch_lo) * 4u, out_b = (size_t)(p.out_hi - p.out_lo + out_pad) * 4u;
-  const size_t tab_o = st.take(tab.bytes()), shift_o = st.take((size_t)p.n_shift * 4u), rx_o = st.take(rx_n), ch_o = st.take(ch_n);
-  if (st.ensure(out_b) != 0)
-    return -1;
-  tab.write(st.h(tab_o));
-  memcpy(st.h(shift_o), shift, (size_t)p.n_shift * 4u);
-  memcpy(st.h(rx_o), rxdataF + 2 * p.rx_lo, rx_n);
-  memcpy(st.h(ch_o), ul_ch + 2 * p.ch_lo, ch_n);
-  const auto launch = [&] {
-    HIP_TRY(nr_launch_rx_compensation_grid(tab.first(st.d(tab_o)), (uint32_t)p.wgs.size(), tab.second(st.d(tab_o)),
-                                           reinterpret_cast<const uint32_t *>(st.d(rx_o)), reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, rx_ant_stride,
-                                           ch_ant_stride, reinterpret_cast<const int32_t *>(st.d(shift_o)), reinterpret_cast<uint32_t *>(st.d_out()),
-                                           st.stream()));
-    return 0;
+  const auto place = [&](uint64_t rx_bias, uint64_t ch_bias, uint64_t out_lo, uint64_t rec_word) {
+    rxg_place(p, gj, rx_bias, ch_bias, rxf_aligned_bias(out_lo), rec_word);
+    return rxf_aligned_bias(out_lo);
   };
-  if (st.run(st.top, launch, out_b) != 0)
-    return -1;
-  rxf_scatter(p, st.h_out(), p.out_lo - out_pad, records);
-  return 0;
+  const auto launch = [&](const rx_front_wg *wgs, uint32_t n_wg, const rx_front_grid_job *jobs, const uint32_t *rx, const uint32_t *ch,
+                          const void *const *per_tb, uint32_t *rec, hipStream_t s) {
+    return nr_launch_rx_compensation_grid(wgs, n_wg, jobs, rx, ch, n_rx, rx_ant_stride, ch_ant_stride, static_cast<const int32_t *>(per_tb[0]), rec, s);
+  };
+  const auto scatter = [&](const uint8_t *bounce, uint64_t bias) { rxf_scatter(p, bounce, bias, records); };
+  return rx_receiver_call("channel_compensation_grid", p, gj, n_seg, rxdataF, ul_ch, {shift}, records, mem, stream, place, launch, scatter);
 }
 
 int32_t nrLDPC_hip_ulsch_channel_level_grid(const int16_t *ul_ch, uint32_t n_rx, uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *first_sym,
@@ -160,38 +123,10 @@ int32_t nrLDPC_hip_ulsch_channel_level_grid(const int16_t *ul_ch, uint32_t n_rx,
   uint64_t ch_lo, ch_hi;
   if (rxg_plan_level(first_sym, n_tb, n_rx, ch_ant_stride, lvl, ch_lo, ch_hi) != 0)
     return -1;
-  const auto tab = rxf_level_tables(lvl);
-  if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    DeviceCall dc;
-    if (dc.open("channel_level_grid", {{log2_maxh, 4}, {ul_ch, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 || dc.refuse_capture("channel_level_grid") != 0)
-      return -1;
-    uint8_t *base = dc.upload(tab);
-    if (!base)
-      return -1;
-    HIP_TRY(nr_launch_rx_level_grid(tab.first(base), n_tb, reinterpret_cast<const uint32_t *>(ul_ch), n_rx, ch_ant_stride, tab.second(base), log2_maxh,
-                                    dc.s));
-    return 0;
-  }
-  StagedCall st;
-  if (st.open() != 0)
-    return -1;
-  for (rx_front_grid_lvl_job &j : lvl)
-    j.ch_off -= ch_lo;
-  const size_t ch_n = (size_t)(ch_hi - ch_lo) * 4u, out_b = (size_t)n_tb * 4u;
-  const size_t tab_o = st.take(tab.bytes()), ch_o = st.take(ch_n);
-  if (st.ensure(out_b) != 0)
-    return -1;
-  tab.write(st.h(tab_o));
-  memcpy(st.h(ch_o), ul_ch + 2 * ch_lo, ch_n);
-  const auto launch = [&] {
-    HIP_TRY(nr_launch_rx_level_grid(tab.first(st.d(tab_o)), n_tb, reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, ch_ant_stride,
-                                    tab.second(st.d(tab_o)), reinterpret_cast<int32_t *>(st.d_out()), st.stream()));
-    return 0;
+  const auto launch = [&](const rx_front_grid_lvl_job *jobs, const uint32_t *ch, const void *const *, int32_t *state, int32_t *out, hipStream_t s) {
+    return nr_launch_rx_level_grid(jobs, n_tb, ch, n_rx, ch_ant_stride, state, out, s);
   };
-  if (st.run(ch_o + ch_n, launch, out_b) != 0)
-    return -1;
-  memcpy(log2_maxh, st.h_out(), out_b);
-  return 0;
+  return rx_level_call("channel_level_grid", lvl, ch_lo, ch_hi, ul_ch, {}, log2_maxh, mem, stream, launch);
 }
 
 } /* extern "C" */

@@ -1,9 +1,10 @@
 /*
  * rx_mmse_api.inc.cpp -- the two-layer PUSCH MMSE receiver's entry points: the channel level over the 2 n_rx (layer, antenna)
  * pairs, the receiver itself from the OFDM grid, and their CPU forms on extracted arrays (included into ldpc_api.cpp behind
- * rx_grid_api.inc.cpp; uses the call scopes of slot_call.inc.cpp).  The arithmetic: nr_rx_mmse.h; the kernels: tb_rx_mmse.hip.
+ * rx_grid_api.inc.cpp; uses the two call bodies of rx_front_api.inc.cpp).  The arithmetic: nr_rx_mmse.h; the kernels: tb_rx_mmse.hip.
  * Everything the kernels index with is checked before anything is enqueued: the checks, the plan and the workgroup table are
- * rx_plan.h's (rxm_*), which the CPU emulation of the kernels shares.
+ * rx_plan.h's (rxm_plan), which the CPU emulation of the kernels shares.  rx2_level_host, the CPU level of a two-layer
+ * block, serves this file and rx_ml_api.inc.cpp.
  */
 
 namespace {
@@ -19,6 +20,30 @@ void rxm_scatter(const std::vector<rx_front_grid_job> &gj, const uint8_t *bounce
 }
 
 uint32_t rxm_c16_at(const int16_t *p, size_t i) { return nr_rxf_c16(p[2 * i], p[2 * i + 1]); }
+
+/* the channel level of one two-layer block's measurement symbol on the CPU, behind the caller's n_rx rule: the MMSE level's term
+ * over the 2 n_rx pairs; final(avgs): the receiver's formula */
+int rx2_level_host(const char *who, const int16_t *chFext, uint32_t n_rx, uint64_t ant_stride, uint32_t nb_re, int32_t max_ch, int32_t *avg,
+                   int32_t *log2_maxh, int32_t (*final)(int32_t avgs))
+{
+  if (nb_re == 0 || (uint64_t)nb_re * 2u > NR_SCR_MAX_BITS)
+    return set_error((std::string(who) + ": nb_re must be 1..2^20").c_str());
+  if (!chFext || !log2_maxh)
+    return set_error("null argument");
+  const uint32_t len = nr_rxf_level_len(nb_re), x = (uint32_t)nr_rxf_factor2(len), sce = nr_rxm_shift_ch_ext(max_ch);
+  int32_t avgs = 0;
+  for (uint32_t a = 0; a < 2u * n_rx; a++) {
+    uint32_t sum = 0;
+    for (uint32_t r = 0; r < nb_re; r++)
+      sum += (uint32_t)nr_rxm_level_term(rxm_c16_at(chFext, (size_t)a * ant_stride + r), x, sce);
+    const int32_t v = nr_rxf_level_avg((int32_t)sum, len);
+    if (avg)
+      avg[a] = v;
+    avgs = std::max(avgs, v);
+  }
+  *log2_maxh = final(avgs);
+  return 0;
+}
 
 } // namespace
 
@@ -65,23 +90,7 @@ int32_t nrLDPC_hip_ulsch_level_mmse_host(const int16_t *chFext, uint32_t n_rx, u
 {
   if (n_rx != 2 && n_rx != 4)
     return set_error("level_mmse_host: n_rx must be 2 or 4");
-  if (nb_re == 0 || (uint64_t)nb_re * 2u > NR_SCR_MAX_BITS)
-    return set_error("level_mmse_host: nb_re must be 1..2^20");
-  if (!chFext || !log2_maxh)
-    return set_error("null argument");
-  const uint32_t len = nr_rxf_level_len(nb_re), x = (uint32_t)nr_rxf_factor2(len), sce = nr_rxm_shift_ch_ext(max_ch);
-  int32_t avgs = 0;
-  for (uint32_t a = 0; a < 2u * n_rx; a++) {
-    uint32_t sum = 0;
-    for (uint32_t r = 0; r < nb_re; r++)
-      sum += (uint32_t)nr_rxm_level_term(rxm_c16_at(chFext, (size_t)a * ant_stride + r), x, sce);
-    const int32_t v = nr_rxf_level_avg((int32_t)sum, len);
-    if (avg)
-      avg[a] = v;
-    avgs = std::max(avgs, v);
-  }
-  *log2_maxh = nr_rxm_log2_maxh(avgs);
-  return 0;
+  return rx2_level_host("level_mmse_host", chFext, n_rx, ant_stride, nb_re, max_ch, avg, log2_maxh, [](int32_t avgs) { return nr_rxm_log2_maxh(avgs); });
 }
 
 int32_t nrLDPC_hip_ulsch_mmse_2layers_grid(const int16_t *rxdataF, const int16_t *ul_ch, uint32_t n_rx, uint64_t rx_ant_stride, uint64_t ch_ant_stride,
@@ -96,54 +105,17 @@ int32_t nrLDPC_hip_ulsch_mmse_2layers_grid(const int16_t *rxdataF, const int16_t
   std::vector<rx_front_grid_job> gj;
   if (rxm_plan(seg, n_seg, n_rx, rx_ant_stride, ch_ant_stride, p, gj) != 0)
     return -1;
-  if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    if (n_seg == 0)
-      return 0;
-    DeviceCall dc;
-    if (dc.open("mmse_2layers_grid", {{records, 4}, {rxdataF, 4}, {ul_ch, 4}, {shift, 4}, {nvar, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 ||
-        dc.refuse_capture("mmse_2layers_grid") != 0)
-      return -1;
-    if (gj.empty())
-      return 0;
-    rxm_place(p, gj, 0, 0, 0);
-    const auto tab = table2(p.wgs, gj);
-    uint8_t *base = dc.upload(tab);
-    if (!base)
-      return -1;
-    HIP_TRY(nr_launch_rx_mmse_grid(tab.first(base), (uint32_t)p.wgs.size(), tab.second(base), reinterpret_cast<const uint32_t *>(rxdataF),
-                                   reinterpret_cast<const uint32_t *>(ul_ch), n_rx, rx_ant_stride, ch_ant_stride, shift, nvar,
-                                   reinterpret_cast<uint32_t *>(records), dc.s));
-    return 0;
-  }
-  if (gj.empty())
-    return 0;
-  StagedCall st;
-  if (st.open() != 0)
-    return -1;
-  /* the device works on copies of the c16 ranges the segments reach */
-  rxm_place(p, gj, p.rx_lo, p.ch_lo, p.out_lo);
-  const auto tab = table2(p.wgs, gj);
-  const size_t rx_n = (size_t)(p.rx_hi - p.rx_lo) * 4u, ch_n = (size_t)(p.ch_hi - p.ch_lo) * 4u, out_b = (size_t)(p.out_hi - p.out_lo) * 4u;
-  const size_t tab_o = st.take(tab.bytes()), shift_o = st.take((size_t)p.n_shift * 4u), nvar_o = st.take((size_t)p.n_shift * 4u), rx_o = st.take(rx_n),
-               ch_o = st.take(ch_n);
-  if (st.ensure(out_b) != 0)
-    return -1;
-  tab.write(st.h(tab_o));
-  memcpy(st.h(shift_o), shift, (size_t)p.n_shift * 4u);
-  memcpy(st.h(nvar_o), nvar, (size_t)p.n_shift * 4u);
-  memcpy(st.h(rx_o), rxdataF + 2 * p.rx_lo, rx_n);
-  memcpy(st.h(ch_o), ul_ch + 2 * p.ch_lo, ch_n);
-  const auto launch = [&] {
-    HIP_TRY(nr_launch_rx_mmse_grid(tab.first(st.d(tab_o)), (uint32_t)p.wgs.size(), tab.second(st.d(tab_o)), reinterpret_cast<const uint32_t *>(st.d(rx_o)),
-                                   reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, rx_ant_stride, ch_ant_stride,
-                                   reinterpret_cast<const int32_t *>(st.d(shift_o)), reinterpret_cast<const uint32_t *>(st.d(nvar_o)),
-                                   reinterpret_cast<uint32_t *>(st.d_out()), st.stream()));
-    return 0;
+  const auto place = [&](uint64_t rx_bias, uint64_t ch_bias, uint64_t out_lo, uint64_t) {
+    rxm_place(p, gj, rx_bias, ch_bias, out_lo);
+    return out_lo;
   };
-  if (st.run(st.top, launch, out_b) != 0)
-    return -1;
-  rxm_scatter(gj, st.h_out(), p.out_lo, records);
-  return 0;
+  const auto launch = [&](const rx_front_wg *wgs, uint32_t n_wg, const rx_front_grid_job *jobs, const uint32_t *rx, const uint32_t *ch,
+                          const void *const *per_tb, uint32_t *rec, hipStream_t s) {
+    return nr_launch_rx_mmse_grid(wgs, n_wg, jobs, rx, ch, n_rx, rx_ant_stride, ch_ant_stride, static_cast<const int32_t *>(per_tb[0]),
+                                  static_cast<const uint32_t *>(per_tb[1]), rec, s);
+  };
+  const auto scatter = [&](const uint8_t *bounce, uint64_t bias) { rxm_scatter(gj, bounce, bias, records); };
+  return rx_receiver_call("mmse_2layers_grid", p, gj, n_seg, rxdataF, ul_ch, {shift, nvar}, records, mem, stream, place, launch, scatter);
 }
 
 int32_t nrLDPC_hip_ulsch_channel_level_grid_mmse(const int16_t *ul_ch, uint32_t n_rx, uint64_t ch_ant_stride, const nrLDPC_hip_rx_grid_seg_t *first_sym,
@@ -160,41 +132,10 @@ int32_t nrLDPC_hip_ulsch_channel_level_grid_mmse(const int16_t *ul_ch, uint32_t 
   /* the estimates' range over 2 n_rx pairs */
   if (rxg_plan_level(first_sym, n_tb, 2u * n_rx, ch_ant_stride, lvl, ch_lo, ch_hi) != 0)
     return -1;
-  const auto tab = rxf_level_tables(lvl);
-  if (mem == NRLDPC_HIP_MEM_DEVICE) {
-    DeviceCall dc;
-    if (dc.open("channel_level_grid_mmse", {{log2_maxh, 4}, {ul_ch, 4}, {max_ch, 4}}, DEV_NEEDS_ALIGNED, stream) != 0 ||
-        dc.refuse_capture("channel_level_grid_mmse") != 0)
-      return -1;
-    uint8_t *base = dc.upload(tab);
-    if (!base)
-      return -1;
-    HIP_TRY(nr_launch_rx_level_grid_mmse(tab.first(base), n_tb, reinterpret_cast<const uint32_t *>(ul_ch), n_rx, ch_ant_stride, max_ch, tab.second(base),
-                                         log2_maxh, dc.s));
-    return 0;
-  }
-  StagedCall st;
-  if (st.open() != 0)
-    return -1;
-  for (rx_front_grid_lvl_job &j : lvl)
-    j.ch_off -= ch_lo;
-  const size_t ch_n = (size_t)(ch_hi - ch_lo) * 4u, out_b = (size_t)n_tb * 4u;
-  const size_t tab_o = st.take(tab.bytes()), max_o = st.take((size_t)n_tb * 4u), ch_o = st.take(ch_n);
-  if (st.ensure(out_b) != 0)
-    return -1;
-  tab.write(st.h(tab_o));
-  memcpy(st.h(max_o), max_ch, (size_t)n_tb * 4u);
-  memcpy(st.h(ch_o), ul_ch + 2 * ch_lo, ch_n);
-  const auto launch = [&] {
-    HIP_TRY(nr_launch_rx_level_grid_mmse(tab.first(st.d(tab_o)), n_tb, reinterpret_cast<const uint32_t *>(st.d(ch_o)), n_rx, ch_ant_stride,
-                                         reinterpret_cast<const int32_t *>(st.d(max_o)), tab.second(st.d(tab_o)),
-                                         reinterpret_cast<int32_t *>(st.d_out()), st.stream()));
-    return 0;
+  const auto launch = [&](const rx_front_grid_lvl_job *jobs, const uint32_t *ch, const void *const *per_tb, int32_t *state, int32_t *out, hipStream_t s) {
+    return nr_launch_rx_level_grid_mmse(jobs, n_tb, ch, n_rx, ch_ant_stride, static_cast<const int32_t *>(per_tb[0]), state, out, s);
   };
-  if (st.run(ch_o + ch_n, launch, out_b) != 0)
-    return -1;
-  memcpy(log2_maxh, st.h_out(), out_b);
-  return 0;
+  return rx_level_call("channel_level_grid_mmse", lvl, ch_lo, ch_hi, ul_ch, {max_ch}, log2_maxh, mem, stream, launch);
 }
 
 } /* extern "C" */

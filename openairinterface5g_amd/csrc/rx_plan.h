@@ -3,6 +3,8 @@
  * checks, the job lists, the c16 ranges of the caller's arrays they reach, and the workgroup tables of tb_rx_front.hip,
  * tb_rx_mmse.hip and tb_rx_ml.hip.  Plain arithmetic (slot_plan.h): rx_front_api.inc.cpp, rx_grid_api.inc.cpp, rx_mmse_api.inc.cpp
  * and rx_ml_api.inc.cpp run it in front of their DEVICE and HOST scopes, and the CPU emulation of the kernels (tests/emul/) runs the same code.
+ * There is one grid plan: rxg_job turns a grid segment into its job and input reach for the single-layer and the two-layer
+ * receivers alike, and the two two-layer receivers share one plan (rx2_plan) that takes what differs between them as data.
  */
 #ifndef RX_PLAN_H
 #define RX_PLAN_H
@@ -11,7 +13,6 @@
 #include "nr_rx_grid.h"
 #include "nr_rx_mmse.h"
 #include "tb_rx_front.h"
-#include "tb_rx_ml.h"
 
 namespace {
 
@@ -143,6 +144,24 @@ void rxg_rx_range(const nrLDPC_hip_rx_grid_seg_t &g, uint64_t &lo, uint64_t &hi)
   }
 }
 
+/* a grid segment with REs: its job (the grid fields; the segment's own part `s` is the caller's) and, into p, the c16 ranges of the
+ * caller's arrays it reaches -- n_rx antennas of the grid, n_ch arrays of the estimates (the antennas', or the 2 n_rx (layer,
+ * antenna) pairs') from the estimate of its first PUSCH subcarrier to that of its last */
+rx_front_grid_job rxg_job(const nrLDPC_hip_rx_grid_seg_t &g, uint32_t n_rx, uint32_t n_ch, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p)
+{
+  uint64_t lo, hi;
+  rxg_rx_range(g, lo, hi);
+  p.rx_lo = std::min(p.rx_lo, lo);
+  p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
+  p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
+  p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(n_ch - 1) * ch_stride);
+  rx_front_grid_job j{};
+  j.pattern = g.pattern;
+  j.fft_size = g.fft_size;
+  j.start_re = g.start_re;
+  return j;
+}
+
 /* the grid checks, then the plan of the extracted form (its checks, output ranges and jobs) with the input ranges of the grid */
 int rxg_plan_compensation(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
                           std::vector<rx_front_grid_job> &gj)
@@ -168,22 +187,9 @@ int rxg_plan_compensation(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, u
   p.rx_lo = p.ch_lo = UINT64_MAX;
   p.rx_hi = p.ch_hi = 0;
   gj.reserve(p.jobs.size());
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
-    if (g.nb_re == 0)
-      continue;
-    uint64_t lo, hi;
-    rxg_rx_range(g, lo, hi);
-    p.rx_lo = std::min(p.rx_lo, lo);
-    p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
-    p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
-    p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(n_rx - 1) * ch_stride);
-    rx_front_grid_job j{};
-    j.pattern = g.pattern;
-    j.fft_size = g.fft_size;
-    j.start_re = g.start_re;
-    gj.push_back(j);
-  }
+  for (uint32_t i = 0; i < n_seg; i++)
+    if (seg[i].nb_re != 0)
+      gj.push_back(rxg_job(seg[i], n_rx, n_rx, rx_stride, ch_stride, p));
   return 0;
 }
 
@@ -222,7 +228,7 @@ int rxg_plan_level(const nrLDPC_hip_rx_grid_seg_t *fs, uint32_t n_tb, uint32_t n
   return 0;
 }
 
-/* ---- the two-layer MMSE receiver (rx_mmse_api.inc.cpp) ---- */
+/* ---- the two-layer receivers (rx_mmse_api.inc.cpp, rx_ml_api.inc.cpp) ---- */
 int rxm_check_common(const char *who, uint32_t n_rx, int32_t mem)
 {
   if (n_rx != 2 && n_rx != 4)
@@ -230,38 +236,50 @@ int rxm_check_common(const char *who, uint32_t n_rx, int32_t mem)
   return check_mem(who, mem);
 }
 
-/* the checks, the jobs, the doubled output ranges (a segment fills codeword symbols 2 sym_off .. 2 (sym_off + nb_re) - 1 of
- * each plane) and the input ranges: n_rx antennas of the grid, 2 n_rx pairs of the estimates */
-int rxm_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
+/* what the plans of the two receivers differ in.  An RE's two layers come to Qm 32-bit words of output; run(Qm) of them lie side
+ * by side, and the Qm / run(Qm) runs of an RE are `plane` words apart:
+ *   MMSE  run = 2: the layers' entries of one plane; a segment fills codeword symbols 2 sym_off .. 2 (sym_off + nb_re) - 1 of each of
+ *         the Qm / 2 planes of the symbol record;
+ *   ML    run = Qm: Qm / 2 words of LLRs per layer, the two layers of an RE side by side; a segment fills words rec_off / 2 +
+ *         Qm sym_off .. + Qm nb_re - 1 of the LLR array */
+struct Rx2Layers {
+  const char *who;
+  uint8_t qm[2];         /* the modulation orders the receiver takes */
+  const char *qm_needed; /* the refusal of any other, with the receiver that takes it */
+  uint32_t (*run)(uint32_t Qm);
+};
+const Rx2Layers RX2_MMSE = {"mmse_2layers_grid", {6, 8}, "mmse_2layers_grid: Qm must be 6 or 8 (two layers of QPSK / 16QAM take the ML receiver, ml_2layers_grid)",
+                            [](uint32_t) { return 2u; }};
+const Rx2Layers RX2_ML = {"ml_2layers_grid", {2, 4}, "ml_2layers_grid: Qm must be 2 or 4 (two layers of 64QAM / 256QAM take the MMSE receiver, mmse_2layers_grid)",
+                          [](uint32_t Qm) { return Qm; }};
+
+/* the checks, the jobs (s.out_off = the word index of the segment's first output word), the output ranges and the input ranges:
+ * n_rx antennas of the grid, 2 n_rx pairs of the estimates */
+int rx2_plan(const Rx2Layers &rx, const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
              std::vector<rx_front_grid_job> &gj)
 {
+  const std::string who = std::string(rx.who) + ": ";
   std::vector<Range64> out;
   gj.reserve(n_seg);
   for (uint32_t i = 0; i < n_seg; i++) {
     const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
-    if (rxg_check_seg("mmse_2layers_grid", g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
+    if (rxg_check_seg(rx.who, g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
       return -1;
-    if (g.Qm != 6 && g.Qm != 8)
-      return set_error("mmse_2layers_grid: Qm must be 6 or 8 (two layers of QPSK / 16QAM take the ML receiver, ml_2layers_grid)");
+    if (g.Qm != rx.qm[0] && g.Qm != rx.qm[1])
+      return set_error(rx.qm_needed);
     if (g.rec_off & 1u)
-      return set_error("mmse_2layers_grid: rec_off must be even");
+      return set_error((who + "rec_off must be even").c_str());
     if (2u * ((uint64_t)g.sym_off + g.nb_re) > g.plane)
-      return set_error("mmse_2layers_grid: 2 (sym_off + nb_re) above plane");
+      return set_error((who + "2 (sym_off + nb_re) above plane").c_str());
     if (2u * (uint64_t)g.nb_re * g.Qm > NR_SCR_MAX_BITS)
-      return set_error("mmse_2layers_grid: 2 nb_re * Qm above 2^21");
+      return set_error((who + "2 nb_re * Qm above 2^21").c_str());
     p.n_shift = std::max(p.n_shift, g.tb + 1u);
     if (g.nb_re == 0)
       continue;
-    const uint64_t first = g.rec_off / 2u + 2u * (uint64_t)g.sym_off;
-    for (uint32_t k = 0; k < g.Qm / 2u; k++)
-      out.push_back(Range64{first + (uint64_t)k * g.plane, first + (uint64_t)k * g.plane + 2u * (uint64_t)g.nb_re});
-    uint64_t lo, hi;
-    rxg_rx_range(g, lo, hi);
-    p.rx_lo = std::min(p.rx_lo, lo);
-    p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
-    p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
-    p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(2u * n_rx - 1u) * ch_stride);
-    rx_front_grid_job j{};
+    const uint64_t run = rx.run(g.Qm), first = g.rec_off / 2u + run * g.sym_off;
+    for (uint32_t k = 0; k < g.Qm / run; k++)
+      out.push_back(Range64{first + (uint64_t)k * g.plane, first + (uint64_t)k * g.plane + run * g.nb_re});
+    rx_front_grid_job j = rxg_job(g, n_rx, 2u * n_rx, rx_stride, ch_stride, p);
     j.s.rx_off = g.rx_off;
     j.s.ch_off = g.ch_off;
     j.s.out_off = first;
@@ -269,95 +287,42 @@ int rxm_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx,
     j.s.nb_re = g.nb_re;
     j.s.tb = g.tb;
     j.s.Qm = g.Qm;
-    j.pattern = g.pattern;
-    j.fft_size = g.fft_size;
-    j.start_re = g.start_re;
     gj.push_back(j);
   }
   if (ranges_overlap(out, p.out_lo, p.out_hi))
-    return set_error("mmse_2layers_grid: the output ranges of two segments overlap");
+    return set_error((who + "the output ranges of two segments overlap").c_str());
   return 0;
 }
 
 /* offsets relative to the copies' starts (staged; see rxg_place for the wrap below zero) and the workgroup table: a workgroup
- * takes NR_RXF_THREADS quads of a segment, counted from its RE 0 */
-void rxm_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias)
+ * takes NR_RXF_THREADS groups of NR_RXF_GROUP REs of a segment, counted from its RE 0 (no `phase`: the MMSE quad shares its shift, so the
+ * groups cannot be moved against the segment) */
+void rx2_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias)
 {
   for (size_t i = 0; i < gj.size(); i++) {
     rx_front_seg_job &j = gj[i].s;
     j.rx_off -= rx_bias;
     j.ch_off -= ch_bias;
     j.out_off -= out_bias;
-    const uint32_t quads = (j.nb_re + NR_RXM_QUAD - 1u) / NR_RXM_QUAD;
-    for (uint32_t q = 0; q * NR_RXF_THREADS < quads; q++)
-      p.wgs.push_back(rx_front_wg{(uint32_t)i, q});
-  }
-}
-
-/* ---- the two-layer max-log ML receiver (rx_ml_api.inc.cpp) ---- */
-/* the checks, the jobs, the output ranges in 32-bit words of the LLR array (a segment fills words rec_off / 2 + Qm sym_off ..
- * + Qm nb_re - 1: Qm / 2 words per layer and RE, the two layers of an RE side by side) and the input ranges: n_rx antennas of the
- * grid, 2 n_rx pairs of the estimates */
-int rxl_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
-             std::vector<rx_front_grid_job> &gj)
-{
-  std::vector<Range64> out;
-  gj.reserve(n_seg);
-  for (uint32_t i = 0; i < n_seg; i++) {
-    const nrLDPC_hip_rx_grid_seg_t &g = seg[i];
-    if (rxg_check_seg("ml_2layers_grid", g.pattern, g.fft_size, g.start_re, g.nb_re) != 0)
-      return -1;
-    if (g.Qm != 2 && g.Qm != 4)
-      return set_error("ml_2layers_grid: Qm must be 2 or 4 (two layers of 64QAM / 256QAM take the MMSE receiver, mmse_2layers_grid)");
-    if (g.rec_off & 1u)
-      return set_error("ml_2layers_grid: rec_off must be even");
-    if (2u * ((uint64_t)g.sym_off + g.nb_re) > g.plane)
-      return set_error("ml_2layers_grid: 2 (sym_off + nb_re) above plane");
-    if (2u * (uint64_t)g.nb_re * g.Qm > NR_SCR_MAX_BITS)
-      return set_error("ml_2layers_grid: 2 nb_re * Qm above 2^21");
-    p.n_shift = std::max(p.n_shift, g.tb + 1u);
-    if (g.nb_re == 0)
-      continue;
-    const uint64_t first = g.rec_off / 2u + (uint64_t)g.Qm * g.sym_off;
-    out.push_back(Range64{first, first + (uint64_t)g.Qm * g.nb_re});
-    uint64_t lo, hi;
-    rxg_rx_range(g, lo, hi);
-    p.rx_lo = std::min(p.rx_lo, lo);
-    p.rx_hi = std::max(p.rx_hi, hi + (uint64_t)(n_rx - 1) * rx_stride);
-    p.ch_lo = std::min(p.ch_lo, g.ch_off + nr_rxg_p(g.pattern, 0));
-    p.ch_hi = std::max(p.ch_hi, g.ch_off + nr_rxg_p(g.pattern, g.nb_re - 1u) + 1u + (uint64_t)(2u * n_rx - 1u) * ch_stride);
-    rx_front_grid_job j{};
-    j.s.rx_off = g.rx_off;
-    j.s.ch_off = g.ch_off;
-    j.s.out_off = first;
-    j.s.plane = g.plane;
-    j.s.nb_re = g.nb_re;
-    j.s.tb = g.tb;
-    j.s.Qm = g.Qm;
-    j.pattern = g.pattern;
-    j.fft_size = g.fft_size;
-    j.start_re = g.start_re;
-    gj.push_back(j);
-  }
-  if (ranges_overlap(out, p.out_lo, p.out_hi))
-    return set_error("ml_2layers_grid: the output ranges of two segments overlap");
-  return 0;
-}
-
-/* offsets relative to the copies' starts (staged; see rxg_place for the wrap below zero) and the workgroup table: a workgroup
- * takes NR_RXF_THREADS groups of NR_RXL_GROUP REs of a segment, counted from its RE 0 */
-void rxl_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias)
-{
-  for (size_t i = 0; i < gj.size(); i++) {
-    rx_front_seg_job &j = gj[i].s;
-    j.rx_off -= rx_bias;
-    j.ch_off -= ch_bias;
-    j.out_off -= out_bias;
-    const uint32_t groups = (j.nb_re + NR_RXL_GROUP - 1u) / NR_RXL_GROUP;
+    const uint32_t groups = (j.nb_re + NR_RXF_GROUP - 1u) / NR_RXF_GROUP;
     for (uint32_t q = 0; q * NR_RXF_THREADS < groups; q++)
       p.wgs.push_back(rx_front_wg{(uint32_t)i, q});
   }
 }
+
+/* what a receiver's entry point and the CPU emulation of its kernel call: the one plan with the receiver's constants, the one place */
+int rxm_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
+             std::vector<rx_front_grid_job> &gj)
+{
+  return rx2_plan(RX2_MMSE, seg, n_seg, n_rx, rx_stride, ch_stride, p, gj);
+}
+int rxl_plan(const nrLDPC_hip_rx_grid_seg_t *seg, uint32_t n_seg, uint32_t n_rx, uint64_t rx_stride, uint64_t ch_stride, RxFrontPlan &p,
+             std::vector<rx_front_grid_job> &gj)
+{
+  return rx2_plan(RX2_ML, seg, n_seg, n_rx, rx_stride, ch_stride, p, gj);
+}
+void rxm_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias) { rx2_place(p, gj, rx_bias, ch_bias, out_bias); }
+void rxl_place(RxFrontPlan &p, std::vector<rx_front_grid_job> &gj, uint64_t rx_bias, uint64_t ch_bias, uint64_t out_bias) { rx2_place(p, gj, rx_bias, ch_bias, out_bias); }
 
 } // namespace
 #endif

@@ -29,7 +29,9 @@ struct DeviceCall {
   std::optional<UseDevice> use;
   /* every array in the memory of the GPU that holds the first one, at its alignment; then that GPU for the rest of the scope.
    * needs: how the call's refusal words it */
-  template <size_t N> int open(const char *who, const DevArray (&arrays)[N], const char *needs, void *stream)
+  template <size_t N> int open(const char *who, const DevArray (&arrays)[N], const char *needs, void *stream) { return open(who, arrays, N, needs, stream); }
+  /* ... for a call body that more than one entry point shares: the list is as long as its caller makes it */
+  int open(const char *who, const DevArray *arrays, size_t N, const char *needs, void *stream)
   {
     ord = scr_device_ordinal(arrays[0].p);
     bool ok = ord >= 0 && (reinterpret_cast<uintptr_t>(arrays[0].p) & (arrays[0].align - 1u)) == 0;

@@ -12,23 +12,8 @@
 #include "nr_rx_front.h"
 #include "nr_rx_grid.h"
 #include "tb_rx_front.h"
+#include "tb_rx_group.h"
 #include "tb_rx_level.h"
-
-typedef uint32_t rxf_u32x4 __attribute__((ext_vector_type(4)));
-
-/* 16 bytes at a 4-byte aligned address (the inputs' offsets and strides are the caller's; planes 1.. sit `plane` words behind
- * plane 0, any remainder mod 4) */
-__device__ __forceinline__ void rxf_load4(uint32_t (&w)[NR_RXF_GROUP], const uint32_t *p)
-{
-  rxf_u32x4 v;
-  __builtin_memcpy(&v, p, sizeof v);
-  w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-}
-__device__ __forceinline__ void rxf_store4(uint32_t *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-  const rxf_u32x4 v = {a, b, c, d};
-  __builtin_memcpy(p, &v, sizeof v);
-}
 
 /* ---- the grid source (nr_rx_grid.h): the segment's REs are read from the OFDM grid and the full-width channel estimates ----
  * A thread group's four REs r0 .. r0 + 3 are PUSCH subcarriers p(r0) .. p(r0 + 3): 4 consecutive c16 for FULL (and for DMRS2
@@ -110,10 +95,10 @@ __device__ __forceinline__ void rx_compensation_body(const rx_front_wg *__restri
           uint32_t hA[NRX][NR_RXF_GROUP], hB[NRX][NR_RXF_GROUP], yA[NRX][NR_RXF_GROUP], yB[NRX][NR_RXF_GROUP];
 #pragma unroll
           for (int a = 0; a < NRX; a++) {
-            rxf_load4(hA[a], h0 + (size_t)a * ch_stride + hoff);
-            rxf_load4(hB[a], h0 + (size_t)a * ch_stride + hoff + G.db);
-            rxf_load4(yA[a], y0 + (size_t)a * rx_stride + yoff);
-            rxf_load4(yB[a], y0 + (size_t)a * rx_stride + yoff + G.db);
+            rx_load4(hA[a], h0 + (size_t)a * ch_stride + hoff);
+            rx_load4(hB[a], h0 + (size_t)a * ch_stride + hoff + G.db);
+            rx_load4(yA[a], y0 + (size_t)a * rx_stride + yoff);
+            rx_load4(yB[a], y0 + (size_t)a * rx_stride + yoff + G.db);
           }
 #pragma unroll
           for (int a = 0; a < NRX; a++) {
@@ -127,10 +112,10 @@ __device__ __forceinline__ void rx_compensation_body(const rx_front_wg *__restri
         } else {
           for (uint32_t a = 0; a < nrx; a++) {
             uint32_t hA[NR_RXF_GROUP], hB[NR_RXF_GROUP], yA[NR_RXF_GROUP], yB[NR_RXF_GROUP], hv[NR_RXF_GROUP], yv[NR_RXF_GROUP];
-            rxf_load4(hA, h0 + (size_t)a * ch_stride + hoff);
-            rxf_load4(hB, h0 + (size_t)a * ch_stride + hoff + G.db);
-            rxf_load4(yA, y0 + (size_t)a * rx_stride + yoff);
-            rxf_load4(yB, y0 + (size_t)a * rx_stride + yoff + G.db);
+            rx_load4(hA, h0 + (size_t)a * ch_stride + hoff);
+            rx_load4(hB, h0 + (size_t)a * ch_stride + hoff + G.db);
+            rx_load4(yA, y0 + (size_t)a * rx_stride + yoff);
+            rx_load4(yB, y0 + (size_t)a * rx_stride + yoff + G.db);
             rxf_grid_pick(hv, hA, hB, G);
             rxf_grid_pick(yv, yA, yB, G);
 #pragma unroll
@@ -146,8 +131,8 @@ __device__ __forceinline__ void rx_compensation_body(const rx_front_wg *__restri
         uint32_t hv[NRX][NR_RXF_GROUP], yv[NRX][NR_RXF_GROUP];
 #pragma unroll
         for (int a = 0; a < NRX; a++) {
-          rxf_load4(hv[a], h0 + (size_t)a * ch_stride + hoff);
-          rxf_load4(yv[a], y0 + (size_t)a * rx_stride + yoff);
+          rx_load4(hv[a], h0 + (size_t)a * ch_stride + hoff);
+          rx_load4(yv[a], y0 + (size_t)a * rx_stride + yoff);
         }
 #pragma unroll
         for (int a = 0; a < NRX; a++)
@@ -157,8 +142,8 @@ __device__ __forceinline__ void rx_compensation_body(const rx_front_wg *__restri
       } else {
         for (uint32_t a = 0; a < nrx; a++) {
           uint32_t hv[NR_RXF_GROUP], yv[NR_RXF_GROUP];
-          rxf_load4(hv, h0 + (size_t)a * ch_stride + hoff);
-          rxf_load4(yv, y0 + (size_t)a * rx_stride + yoff);
+          rx_load4(hv, h0 + (size_t)a * ch_stride + hoff);
+          rx_load4(yv, y0 + (size_t)a * rx_stride + yoff);
 #pragma unroll
           for (int u = 0; u < NR_RXF_GROUP; u++)
             nr_rxf_mac(&acc[u], hv[u], yv[u], s, amp);
@@ -166,11 +151,11 @@ __device__ __forceinline__ void rx_compensation_body(const rx_front_wg *__restri
       }
     }
     /* plane 0 at r0 is 16-byte aligned: that is what `phase` was chosen for */
-    *reinterpret_cast<rxf_u32x4 *>(o + r0) = (rxf_u32x4){acc[0].w[0], acc[1].w[0], acc[2].w[0], acc[3].w[0]};
+    *reinterpret_cast<rx_u32x4 *>(o + r0) = (rx_u32x4){acc[0].w[0], acc[1].w[0], acc[2].w[0], acc[3].w[0]};
 #pragma unroll
     for (uint32_t k = 1; k < 4; k++)
       if (k < np)
-        rxf_store4(o + (size_t)k * j.plane + r0, acc[0].w[k], acc[1].w[k], acc[2].w[k], acc[3].w[k]);
+        rx_store4(o + (size_t)k * j.plane + r0, acc[0].w[k], acc[1].w[k], acc[2].w[k], acc[3].w[k]);
     return;
   }
   /* head (REs before the first aligned group) and tail; with the grid source also a group that straddles the wrap */

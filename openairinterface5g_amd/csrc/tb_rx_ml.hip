@@ -6,7 +6,8 @@
  * the LLR array nrLDPC_hip_ulsch_decode_scrambled reads; and the channel level of the blocks' measurement symbols over the 2 n_rx
  * (layer, antenna) pairs (:1612-1647).
  *
- * A thread takes a group of four REs counted from the segment's RE 0, so every array is read with 16-byte loads.  Bit m of layer
+ * A thread takes a group of four REs counted from the segment's RE 0, so every array is read with 16-byte loads (the group and
+ * its loader: tb_rx_group.h, shared with the MMSE receiver).  Bit m of layer
  * l of RE r is int16 rec_off + Qm (2 (sym_off + r) + l) + m: an RE's two layers are Qm 32-bit words side by side, a group's
  * four REs 32 (QPSK) or 64 (16QAM) contiguous bytes, stored as 16-byte stores at a 4-byte aligned address.  Per RE 4 n_rx bytes
  * of grid and 8 n_rx bytes of estimates come in and 4 Qm bytes go out; no LDS.  Qm is uniform per segment: the QPSK / 16QAM
@@ -16,89 +17,8 @@
 #include "nr_rx_ml.h"
 #include "nr_rx_grid.h"
 #include "tb_rx_ml.h"
+#include "tb_rx_group.h"
 #include "tb_rx_level.h"
-
-typedef uint32_t rxl_u32x4 __attribute__((ext_vector_type(4)));
-
-/* 16 bytes at a 4-byte aligned address */
-__device__ __forceinline__ void rxl_load4(uint32_t (&w)[4], const uint32_t *p)
-{
-  rxl_u32x4 v;
-  __builtin_memcpy(&v, p, sizeof v);
-  w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-}
-__device__ __forceinline__ void rxl_store4(uint32_t *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-  const rxl_u32x4 v = {a, b, c, d};
-  __builtin_memcpy(p, &v, sizeof v);
-}
-/* DMRS1: p(r0), + 2, + 4, + 6 = A[0], A[2], B[1], B[3] of load A at p(r0) and load B three c16 behind it (tb_rx_mmse.hip) */
-__device__ __forceinline__ void rxl_pick_dmrs1(uint32_t (&v)[4], const uint32_t (&A)[4], const uint32_t (&B)[4])
-{
-  v[0] = A[0]; v[1] = A[2]; v[2] = B[1]; v[3] = B[3];
-}
-
-/* where a thread's group lies */
-struct rxl_group {
-  uint32_t pattern, start_re, fft_size, r0, nb_re;
-  uint32_t pa, ga; /* PUSCH subcarrier of RE r0; its grid subcarrier (fast only) */
-  bool fast;       /* the group is whole and the grid does not wrap inside it */
-};
-
-/* The group's REs of N antennas (y, rx_stride apart) and of their 2 N pairs (h0 / h1 = layer 0's / layer 1's, ch_stride apart),
- * every load issued before the first use.  r0 % 4 == 0, so the four REs are PUSCH subcarriers p(r0) .. p(r0) + 3 for FULL and
- * DMRS2: one load.  The pattern is tested once around the loads of all arrays, not per array: a branch per array puts a wait
- * for the load in front of the next one.  A group that the grid's wrap cuts, and a partial last group, go RE by RE; the REs
- * behind nb_re read nothing and are zero. */
-template <int N>
-__device__ __forceinline__ void rxl_load(const rxl_group &G, const uint32_t *y, uint64_t rx_stride, const uint32_t *h0, const uint32_t *h1,
-                                         uint64_t ch_stride, uint32_t (&yv)[N][4], uint32_t (&h0v)[N][4], uint32_t (&h1v)[N][4])
-{
-  if (G.fast) {
-    if (G.pattern == NR_RXG_DMRS1) { /* wave-uniform */
-      uint32_t yA[N][4], yB[N][4], gA[N][4], gB[N][4], kA[N][4], kB[N][4];
-#pragma unroll
-      for (int a = 0; a < N; a++) {
-        rxl_load4(yA[a], y + (size_t)a * rx_stride + G.ga);
-        rxl_load4(yB[a], y + (size_t)a * rx_stride + G.ga + 3);
-      }
-#pragma unroll
-      for (int a = 0; a < N; a++) {
-        rxl_load4(gA[a], h0 + (size_t)a * ch_stride + G.pa);
-        rxl_load4(gB[a], h0 + (size_t)a * ch_stride + G.pa + 3);
-        rxl_load4(kA[a], h1 + (size_t)a * ch_stride + G.pa);
-        rxl_load4(kB[a], h1 + (size_t)a * ch_stride + G.pa + 3);
-      }
-#pragma unroll
-      for (int a = 0; a < N; a++) {
-        rxl_pick_dmrs1(yv[a], yA[a], yB[a]);
-        rxl_pick_dmrs1(h0v[a], gA[a], gB[a]);
-        rxl_pick_dmrs1(h1v[a], kA[a], kB[a]);
-      }
-    } else {
-#pragma unroll
-      for (int a = 0; a < N; a++)
-        rxl_load4(yv[a], y + (size_t)a * rx_stride + G.ga);
-#pragma unroll
-      for (int a = 0; a < N; a++) {
-        rxl_load4(h0v[a], h0 + (size_t)a * ch_stride + G.pa);
-        rxl_load4(h1v[a], h1 + (size_t)a * ch_stride + G.pa);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const bool in = G.r0 + u < G.nb_re;
-      const uint32_t p = nr_rxg_p(G.pattern, G.r0 + u), sc = nr_rxg_grid_sc(G.start_re, p, G.fft_size);
-#pragma unroll
-      for (int a = 0; a < N; a++) {
-        yv[a][u] = in ? y[(size_t)a * rx_stride + sc] : 0u;
-        h0v[a][u] = in ? h0[(size_t)a * ch_stride + p] : 0u;
-        h1v[a][u] = in ? h1[(size_t)a * ch_stride + p] : 0u;
-      }
-    }
-  }
-}
 
 /* NRX = 2, 4: the antennas unrolled; NRX = 0: any n_rx, one antenna's loads at a time */
 template <int NRX>
@@ -110,29 +30,18 @@ nr_rx_ml_grid_kernel(const rx_front_wg *__restrict__ wgs, const rx_front_grid_jo
   const rx_front_wg w = wgs[blockIdx.x];
   const rx_front_grid_job J = jobs[w.seg];
   const rx_front_seg_job &j = J.s;
-  const uint32_t r0 = (w.piece * NR_RXF_THREADS + threadIdx.x) * NR_RXL_GROUP;
+  const uint32_t r0 = (w.piece * NR_RXF_THREADS + threadIdx.x) * NR_RXF_GROUP;
   if (r0 >= j.nb_re)
     return;
   const uint32_t s = nr_rxf_shift(shift[j.tb]);
   const int32_t amp[3] = {nr_rxf_amp(j.Qm, 0), 0, 0};
   const uint32_t *y0 = rx + j.rx_off, *h0 = ch + j.ch_off, *h1 = h0 + (size_t)(NRX > 0 ? NRX : n_rx) * ch_stride;
-  const bool whole = r0 + NR_RXL_GROUP <= j.nb_re;
-
-  rxl_group G;
-  G.pattern = J.pattern;
-  G.start_re = J.start_re;
-  G.fft_size = J.fft_size;
-  G.r0 = r0;
-  G.nb_re = j.nb_re;
-  G.pa = nr_rxg_p(J.pattern, r0);
-  const uint32_t span = nr_rxg_p(J.pattern, r0 + 3u) - G.pa, g = J.start_re + G.pa;
-  G.fast = whole && !(g < J.fft_size && g + span >= J.fft_size);
-  G.ga = g >= J.fft_size ? g - J.fft_size : g;
+  const rx_group G = rx_group_locate(J, r0);
 
   nr_rxl_re_t R[4] = {};
   if constexpr (NRX > 0) {
     uint32_t yv[NRX][4], h0v[NRX][4], h1v[NRX][4];
-    rxl_load<NRX>(G, y0, rx_stride, h0, h1, ch_stride, yv, h0v, h1v);
+    rx_group_load<NRX>(G, y0, rx_stride, h0, h1, ch_stride, yv, h0v, h1v);
 #pragma unroll
     for (int u = 0; u < 4; u++)
 #pragma unroll
@@ -141,7 +50,7 @@ nr_rx_ml_grid_kernel(const rx_front_wg *__restrict__ wgs, const rx_front_grid_jo
   } else {
     for (uint32_t a = 0; a < n_rx; a++) { /* in order: the sums of rho saturate */
       uint32_t yv[1][4], h0v[1][4], h1v[1][4];
-      rxl_load<1>(G, y0 + (size_t)a * rx_stride, rx_stride, h0 + (size_t)a * ch_stride, h1 + (size_t)a * ch_stride, ch_stride, yv, h0v, h1v);
+      rx_group_load<1>(G, y0 + (size_t)a * rx_stride, rx_stride, h0 + (size_t)a * ch_stride, h1 + (size_t)a * ch_stride, ch_stride, yv, h0v, h1v);
 #pragma unroll
       for (int u = 0; u < 4; u++)
         nr_rxl_mac(&R[u], h0v[0][u], h1v[0][u], yv[0][u], s, amp);
@@ -160,9 +69,9 @@ nr_rx_ml_grid_kernel(const rx_front_wg *__restrict__ wgs, const rx_front_grid_jo
         nr_rxl_llr(&R[u], 2, l, L);
         v[2 * u + l] = nr_rxf_c16(L[0], L[1]);
       }
-    if (whole) {
-      rxl_store4(o, v[0], v[1], v[2], v[3]);
-      rxl_store4(o + 4, v[4], v[5], v[6], v[7]);
+    if (G.whole) {
+      rx_store4(o, v[0], v[1], v[2], v[3]);
+      rx_store4(o + 4, v[4], v[5], v[6], v[7]);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; u++)
@@ -182,8 +91,8 @@ nr_rx_ml_grid_kernel(const rx_front_wg *__restrict__ wgs, const rx_front_grid_jo
         v[2 * l] = nr_rxf_c16(L[0], L[1]);
         v[2 * l + 1] = nr_rxf_c16(L[2], L[3]);
       }
-      if (whole)
-        rxl_store4(o + 4 * u, v[0], v[1], v[2], v[3]);
+      if (G.whole)
+        rx_store4(o + 4 * u, v[0], v[1], v[2], v[3]);
       else if (r0 + u < j.nb_re) {
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -210,18 +119,12 @@ hipError_t nr_launch_rx_ml_grid(const rx_front_wg *wgs, uint32_t n_wg, const rx_
   return hipGetLastError();
 }
 
-/* ---- channel level: the shared body (tb_rx_level.h) over the 2 n_rx pairs, with the MMSE level's term (scaled by shift_ch_ext of
- * max_ch[tb]) and the ML branch's formula at the end ---- */
+/* ---- channel level: the two-layer body (tb_rx_level.h) with the ML branch's formula at the end ---- */
 __global__ void __launch_bounds__(NR_RXF_THREADS)
 nr_rx_level_grid_ml_kernel(const rx_front_grid_lvl_job *__restrict__ jobs, const uint32_t *__restrict__ ch, uint32_t n_pair, uint64_t ant_stride,
                            const int32_t *__restrict__ max_ch, int32_t *mx, int32_t *cnt, int32_t *__restrict__ log2_maxh)
 {
-  const uint32_t b = blockIdx.x / n_pair, a = blockIdx.x % n_pair;
-  const rx_front_grid_lvl_job j = jobs[b];
-  const uint32_t len = nr_rxf_level_len(j.nb_re), x = (uint32_t)nr_rxf_factor2(len), sce = nr_rxm_shift_ch_ext(max_ch[j.tb]);
-  const uint32_t *h = ch + j.ch_off + (size_t)a * ant_stride;
-  rx_level_sum(b, n_pair, j.nb_re, len, [&](uint32_t r) { return nr_rxm_level_term(h[nr_rxg_p(j.pattern, r)], x, sce); },
-               [](int32_t avgs) { return nr_rxl_log2_maxh(avgs); }, mx, cnt, &log2_maxh[j.tb]);
+  rx2_level_body(jobs, ch, n_pair, ant_stride, max_ch, [](int32_t avgs) { return nr_rxl_log2_maxh(avgs); }, mx, cnt, log2_maxh);
 }
 
 hipError_t nr_launch_rx_level_grid_ml(const rx_front_grid_lvl_job *jobs, uint32_t n_tb, const uint32_t *ch, uint32_t n_rx, uint64_t ch_ant_stride,

@@ -10,35 +10,20 @@
  * segment: the `phase` of the single-layer kernel, which lays its groups for 16-byte aligned stores, cannot be carried over.
  * The stores here are 16 bytes at a 4-byte aligned address.  Per RE 4 n_rx bytes of grid and 8 n_rx bytes of estimates come in
  * and 2 Qm bytes go out; no LDS.
+ *
+ * The 16-byte load and store and the DMRS1 pick are tb_rx_group.h's.  The loader of a quad is written out here and not taken
+ * from that header: with the shared one (the estimates as two arrays of n_rx, layer 0's and layer 1's loads interleaved) the
+ * n_rx = 4 kernel measured 0.5 .. 1 % slower than with this one (one array of 2 n_rx pairs, loaded in order), outside the spread of
+ * repeated runs.  What it does and why is said once, at rx_group_load.
  */
 #include <hip/hip_runtime.h>
 #include "nr_rx_mmse.h"
 #include "nr_rx_grid.h"
 #include "tb_rx_mmse.h"
+#include "tb_rx_group.h"
 #include "tb_rx_level.h"
 
-typedef uint32_t rxm_u32x4 __attribute__((ext_vector_type(4)));
-
-/* 16 bytes at a 4-byte aligned address */
-__device__ __forceinline__ void rxm_load4(uint32_t (&w)[4], const uint32_t *p)
-{
-  rxm_u32x4 v;
-  __builtin_memcpy(&v, p, sizeof v);
-  w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-}
-__device__ __forceinline__ void rxm_store4(uint32_t *p, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-  const rxm_u32x4 v = {a, b, c, d};
-  __builtin_memcpy(p, &v, sizeof v);
-}
-/* A quad's four REs out of one array.  4q % 4 == 0, so they are PUSCH subcarriers p(4q) .. p(4q) + 3 for FULL and DMRS2: one
- * load.  DMRS1: p(4q), + 2, + 4, + 6 = A[0], A[2], B[1], B[3] of load A at p(4q) and load B three c16 behind it; together they
- * cover exactly [p(4q), p(4q + 3)], nothing outside the segment's own range is read.  The pattern is tested once per quad, around
- * the loads of all arrays, not per array: a branch per array puts a wait for the load in front of the next one. */
-__device__ __forceinline__ void rxm_pick_dmrs1(uint32_t (&v)[4], const uint32_t (&A)[4], const uint32_t (&B)[4])
-{
-  v[0] = A[0]; v[1] = A[2]; v[2] = B[1]; v[3] = B[3];
-}
+static_assert(NR_RXM_QUAD == NR_RXF_GROUP, "a thread's group of four REs is the quad that shares the shift b");
 
 template <int NRX>
 __global__ void __launch_bounds__(NR_RXF_THREADS)
@@ -55,7 +40,8 @@ nr_rx_mmse_grid_kernel(const rx_front_wg *__restrict__ wgs, const rx_front_grid_
   const uint32_t s = nr_rxf_shift(shift[j.tb]), nv = nvar[j.tb], np = j.Qm >> 1;
   const uint32_t *y0 = rx + j.rx_off, *h0 = ch + j.ch_off;
 
-  /* the quad's REs of the n_rx antennas and of the 2 n_rx pairs, every load issued before the first use */
+  /* the quad's REs of the n_rx antennas and of the 2 n_rx pairs, every load issued before the first use (rx_group_load of
+   * tb_rx_group.h: the pattern tested once around all loads, DMRS1's two loads within the segment's own range) */
   uint32_t yv[NRX][4], hv[2 * NRX][4];
   const uint32_t pa = nr_rxg_p(J.pattern, r0), span = nr_rxg_p(J.pattern, r0 + 3u) - pa, g = J.start_re + pa;
   const bool whole = r0 + NR_RXM_QUAD <= j.nb_re;
@@ -65,27 +51,27 @@ nr_rx_mmse_grid_kernel(const rx_front_wg *__restrict__ wgs, const rx_front_grid_
       uint32_t yA[NRX][4], yB[NRX][4], hA[2 * NRX][4], hB[2 * NRX][4];
 #pragma unroll
       for (int a = 0; a < NRX; a++) {
-        rxm_load4(yA[a], y0 + (size_t)a * rx_stride + ga);
-        rxm_load4(yB[a], y0 + (size_t)a * rx_stride + ga + 3);
+        rx_load4(yA[a], y0 + (size_t)a * rx_stride + ga);
+        rx_load4(yB[a], y0 + (size_t)a * rx_stride + ga + 3);
       }
 #pragma unroll
       for (int a = 0; a < 2 * NRX; a++) {
-        rxm_load4(hA[a], h0 + (size_t)a * ch_stride + pa);
-        rxm_load4(hB[a], h0 + (size_t)a * ch_stride + pa + 3);
+        rx_load4(hA[a], h0 + (size_t)a * ch_stride + pa);
+        rx_load4(hB[a], h0 + (size_t)a * ch_stride + pa + 3);
       }
 #pragma unroll
       for (int a = 0; a < NRX; a++)
-        rxm_pick_dmrs1(yv[a], yA[a], yB[a]);
+        rx_pick_dmrs1(yv[a], yA[a], yB[a]);
 #pragma unroll
       for (int a = 0; a < 2 * NRX; a++)
-        rxm_pick_dmrs1(hv[a], hA[a], hB[a]);
+        rx_pick_dmrs1(hv[a], hA[a], hB[a]);
     } else {
 #pragma unroll
       for (int a = 0; a < NRX; a++)
-        rxm_load4(yv[a], y0 + (size_t)a * rx_stride + ga);
+        rx_load4(yv[a], y0 + (size_t)a * rx_stride + ga);
 #pragma unroll
       for (int a = 0; a < 2 * NRX; a++)
-        rxm_load4(hv[a], h0 + (size_t)a * ch_stride + pa);
+        rx_load4(hv[a], h0 + (size_t)a * ch_stride + pa);
     }
   } else {
     /* the grid wraps inside the quad, or the segment ends inside it: RE by RE; the lanes behind nb_re are the reference's zero
@@ -134,8 +120,8 @@ nr_rx_mmse_grid_kernel(const rx_front_wg *__restrict__ wgs, const rx_front_grid_
     }
     uint32_t *ok = o + (size_t)k * j.plane;
     if (whole) {
-      rxm_store4(ok, v[0], v[1], v[2], v[3]);
-      rxm_store4(ok + 4, v[4], v[5], v[6], v[7]);
+      rx_store4(ok, v[0], v[1], v[2], v[3]);
+      rx_store4(ok + 4, v[4], v[5], v[6], v[7]);
     } else {
 #pragma unroll
       for (int u = 0; u < 4; u++)
@@ -163,18 +149,12 @@ hipError_t nr_launch_rx_mmse_grid(const rx_front_wg *wgs, uint32_t n_wg, const r
   return hipGetLastError();
 }
 
-/* ---- channel level: the body of the single-layer front (tb_rx_level.h) over the 2 n_rx pairs, with the term scaled by
- * shift_ch_ext of max_ch[tb] and the MMSE formula at the end ---- */
+/* ---- channel level: the two-layer body (tb_rx_level.h) with the MMSE formula at the end ---- */
 __global__ void __launch_bounds__(NR_RXF_THREADS)
 nr_rx_level_grid_mmse_kernel(const rx_front_grid_lvl_job *__restrict__ jobs, const uint32_t *__restrict__ ch, uint32_t n_pair, uint64_t ant_stride,
                              const int32_t *__restrict__ max_ch, int32_t *mx, int32_t *cnt, int32_t *__restrict__ log2_maxh)
 {
-  const uint32_t b = blockIdx.x / n_pair, a = blockIdx.x % n_pair;
-  const rx_front_grid_lvl_job j = jobs[b];
-  const uint32_t len = nr_rxf_level_len(j.nb_re), x = (uint32_t)nr_rxf_factor2(len), sce = nr_rxm_shift_ch_ext(max_ch[j.tb]);
-  const uint32_t *h = ch + j.ch_off + (size_t)a * ant_stride;
-  rx_level_sum(b, n_pair, j.nb_re, len, [&](uint32_t r) { return nr_rxm_level_term(h[nr_rxg_p(j.pattern, r)], x, sce); },
-               [](int32_t avgs) { return nr_rxm_log2_maxh(avgs); }, mx, cnt, &log2_maxh[j.tb]);
+  rx2_level_body(jobs, ch, n_pair, ant_stride, max_ch, [](int32_t avgs) { return nr_rxm_log2_maxh(avgs); }, mx, cnt, log2_maxh);
 }
 
 hipError_t nr_launch_rx_level_grid_mmse(const rx_front_grid_lvl_job *jobs, uint32_t n_tb, const uint32_t *ch, uint32_t n_rx, uint64_t ch_ant_stride,

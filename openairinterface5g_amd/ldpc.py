@@ -1283,15 +1283,17 @@ def _rxg_p(pattern, j):
     return 2 * j + 1 if pattern == RXG_DMRS1 else (6 * (j // 4) + 2 + j % 4 if pattern == RXG_DMRS2 else j)
 
 
-def _rxg_check_extent(segs, n_rx, rx_stride, ch_stride, rx_len, ch_len):
-    """The calls do not know the arrays' extents; the wrappers do.  rx_len / ch_len in c16, None where an array is not read."""
+def _rxg_check_extent(segs, n_rx, rx_stride, ch_stride, rx_len, ch_len, n_ch=None):
+    """The calls do not know the arrays' extents; the wrappers do.  rx_len / ch_len in c16, None where an array is not read; n_ch =
+    the estimate arrays (n_rx by default; the two-layer receivers read the 2 n_rx (layer, antenna) pairs)."""
+    n_ch = n_rx if n_ch is None else n_ch
     for s in segs:
         if s["nb_re"] == 0 or s.get("pattern", 0) > 2 or not 0 <= s["start_re"] < s["fft_size"]:
             continue                                                   # the library names what is wrong with those
         last = _rxg_p(s["pattern"], s["nb_re"] - 1)
         if last >= s["fft_size"]:
             continue
-        if ch_len is not None and s["ch_off"] + (n_rx - 1) * ch_stride + last + 1 > ch_len:
+        if ch_len is not None and s["ch_off"] + (n_ch - 1) * ch_stride + last + 1 > ch_len:
             raise ValueError("a segment's channel estimates leave the array")
         if rx_len is not None:
             top = s["start_re"] + last + 1 if s["start_re"] + last < s["fft_size"] else s["fft_size"]
@@ -1372,6 +1374,20 @@ def _rxm_lib():
     return L
 
 
+def _level_grid_2layers(L, name, ch, n_rx, ch_ant_stride, first_sym, max_ch, out, stream):
+    """the level call `name` of a two-layer receiver: the estimates' extent over the 2 n_rx pairs, then the call (a max_ch that is
+    None is the library's to refuse)"""
+    n, res = len(first_sym), _level_out(ch, out, len(first_sym))
+    if isinstance(ch, np.ndarray) and max_ch is not None:
+        max_ch = np.ascontiguousarray(max_ch, np.int32)
+    ptr, numel, mem, s = _mem_of((ch,), stream, (res,) if max_ch is None else (res, max_ch))
+    assert max_ch is None or numel(max_ch) >= n
+    _rxg_check_extent(first_sym, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _check(getattr(L, name)(ptr(ch), n_rx, ch_ant_stride, _rx_grid_seg_array(first_sym), n, None if max_ch is None else ptr(max_ch), ptr(res), mem, s),
+           name)
+    return res[:n] if mem == MEM_HOST else res
+
+
 def _rxm_check_records(segs, rec_len):
     """a segment's doubled output range must lie inside `records` (rec_len in int16)"""
     for s in segs:
@@ -1409,15 +1425,7 @@ def ulsch_channel_level_grid_mmse(ch, n_rx, ch_ant_stride, first_sym, max_ch, ou
     ch_ant_stride apart; first_sym = one grid descriptor per block; max_ch = int32 per block.  numpy -> host call, returns
     int32[n_tb]; torch CUDA tensors -> device call enqueued on `stream` into `out` (torch int32 CUDA, >= n_tb elements); returns
     `out`."""
-    n, res = len(first_sym), _level_out(ch, out, len(first_sym))
-    if isinstance(ch, np.ndarray):
-        max_ch = np.ascontiguousarray(max_ch, np.int32)
-    ptr, numel, mem, s = _mem_of((ch,), stream, (res, max_ch))
-    assert numel(max_ch) >= n
-    _rxg_check_extent(first_sym, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
-    _check(_rxm_lib().nrLDPC_hip_ulsch_channel_level_grid_mmse(ptr(ch), n_rx, ch_ant_stride, _rx_grid_seg_array(first_sym), n, ptr(max_ch), ptr(res),
-                                                               mem, s), "nrLDPC_hip_ulsch_channel_level_grid_mmse")
-    return res[:n] if mem == MEM_HOST else res
+    return _level_grid_2layers(_rxm_lib(), "nrLDPC_hip_ulsch_channel_level_grid_mmse", ch, n_rx, ch_ant_stride, first_sym, max_ch, out, stream)
 
 
 def ulsch_mmse_2layers_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, shift, nvar, records, stream=None):
@@ -1430,8 +1438,7 @@ def ulsch_mmse_2layers_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, sh
         shift = np.ascontiguousarray(shift, np.int32)
         nvar = np.ascontiguousarray(np.asarray(nvar).astype(np.uint32).view(np.int32))
     ptr, numel, mem, s = _mem_of((rx, ch, records), stream, (shift, nvar))
-    _rxg_check_extent(segs, n_rx, rx_ant_stride, 0, numel(rx) // 2, None)
-    _rxg_check_extent(segs, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _rxg_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, numel(rx) // 2, numel(ch) // 2, n_ch=2 * n_rx)
     _rxm_check_records(segs, numel(records))
     _check(_rxm_lib().nrLDPC_hip_ulsch_mmse_2layers_grid(ptr(rx), ptr(ch), n_rx, rx_ant_stride, ch_ant_stride, _rx_grid_seg_array(segs), len(segs),
                                                          ptr(shift), ptr(nvar), ptr(records), mem, s), "nrLDPC_hip_ulsch_mmse_2layers_grid")
@@ -1496,16 +1503,7 @@ def ulsch_level_ml_host(ch, n_rx, ant_stride, nb_re, max_ch):
 
 def ulsch_channel_level_grid_ml(ch, n_rx, ch_ant_stride, first_sym, max_ch, out=None, stream=None):
     """nrLDPC_hip_ulsch_channel_level_grid_ml: the arguments of ulsch_channel_level_grid_mmse; n_rx = 1..8."""
-    n, res = len(first_sym), _level_out(ch, out, len(first_sym))
-    if isinstance(ch, np.ndarray) and max_ch is not None:
-        max_ch = np.ascontiguousarray(max_ch, np.int32)
-    ptr, numel, mem, s = _mem_of((ch,), stream, (res,) if max_ch is None else (res, max_ch))
-    assert max_ch is None or numel(max_ch) >= n
-    _rxg_check_extent(first_sym, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
-    _check(_rxl_lib().nrLDPC_hip_ulsch_channel_level_grid_ml(ptr(ch), n_rx, ch_ant_stride, _rx_grid_seg_array(first_sym), n,
-                                                             None if max_ch is None else ptr(max_ch), ptr(res), mem, s),
-           "nrLDPC_hip_ulsch_channel_level_grid_ml")
-    return res[:n] if mem == MEM_HOST else res
+    return _level_grid_2layers(_rxl_lib(), "nrLDPC_hip_ulsch_channel_level_grid_ml", ch, n_rx, ch_ant_stride, first_sym, max_ch, out, stream)
 
 
 def ulsch_ml_2layers_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, shift, llr, stream=None):
@@ -1516,8 +1514,7 @@ def ulsch_ml_2layers_grid(rx, ch, n_rx, rx_ant_stride, ch_ant_stride, segs, shif
     if isinstance(rx, np.ndarray):
         shift = np.ascontiguousarray(shift, np.int32)
     ptr, numel, mem, s = _mem_of((rx, ch, llr), stream, (shift,))
-    _rxg_check_extent(segs, n_rx, rx_ant_stride, 0, numel(rx) // 2, None)
-    _rxg_check_extent(segs, 2 * n_rx, 0, ch_ant_stride, None, numel(ch) // 2)
+    _rxg_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, numel(rx) // 2, numel(ch) // 2, n_ch=2 * n_rx)
     _rxl_check_llr(segs, numel(llr))
     _check(_rxl_lib().nrLDPC_hip_ulsch_ml_2layers_grid(ptr(rx), ptr(ch), n_rx, rx_ant_stride, ch_ant_stride, _rx_grid_seg_array(segs), len(segs),
                                                        ptr(shift), ptr(llr), mem, s), "nrLDPC_hip_ulsch_ml_2layers_grid")
