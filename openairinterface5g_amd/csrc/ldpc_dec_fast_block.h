@@ -40,6 +40,8 @@ typedef const ldpc_dec_job LDPC_CONST_AS *ldpc_job_ptr_t; /* job records are rea
  *   static bool pass_stamps   diagnostic instantiation: stamps() is a row of 54 words in memory (zeroed by the launcher) and
  *                             also takes [2p], [2p + 1] the clocks behind pass p's check-node / bit-node barrier, [20] the
  *                             passes that ran the eager parity sweep (bit p), [22 + p] the unsatisfied lanes counted by pass p
+ *                             (exact up to LDPC_EAGER_MAX_BAD_LANES, a lower bound above), [32 + p] the check-node tasks of
+ *                             pass p that ran without the parity
  *   int tid()                 threadIdx.x
  *   uint32_t ld_llr(p)        one dword of src32_prologue()'s row: a plain load, or one that bypasses the caches when the
  *                             row was written by the host while this kernel was running (resident server)
@@ -68,13 +70,47 @@ typedef const ldpc_dec_job LDPC_CONST_AS *ldpc_job_ptr_t; /* job records are rea
 #endif
 #define LDPC_EAGER_MAX_BAD_LANES 96
 #define LDPC_TIMING_SLOTS 28
+#ifndef LDPC_SYN_SKIP
+#define LDPC_SYN_SKIP 1 /* A/B and the tests' control: tools/build_variant.sh <name> -DLDPC_SYN_SKIP=0 evaluates the parity in every task */
+#endif
 
-/* next ticket of a task queue (wave-uniform) */
+/* The queue word of a pass: {unsatisfied lanes counted so far : 16 | tickets drawn : 16}.
+ *
+ * The parity of the previous pass' hard decisions, which the check-node phase of pass p >= 2 evaluates item by item, answers
+ * two questions only: "is the count 0?" (the block stops) and "is it <= LDPC_EAGER_MAX_BAD_LANES?" (the eager sweep runs).
+ * Both are settled once the running count has passed that bound, and every parity instruction issued behind that point of the
+ * pass produces nothing.  So the count travels in the high half of the word the tasks are drawn from: the draw that ends a
+ * check-node task -- the same single LDS atomic as before -- adds the number of the task's lanes that saw an unsatisfied check
+ * (one per thread and task) and returns the count of everything handed in before it; a task drawn with a count above the bound
+ * runs the bodies without the parity (SYN = false, ldpc_dec_fast_core.h).  Every wave's last check-node draw is its first
+ * bit-node ticket, so a wave has handed in its last task's count before it reaches the barrier, and behind the barrier the high
+ * half is the pass' count.  Bit-node draws and the draw in front of the barrier add 1 only; every reader of a ticket masks it
+ * out of the low half.
+ * Exactness: skipping starts only after the total has passed the bound.  A pass whose true total is <= the bound, zero included,
+ * is therefore counted in full; a pass whose true total is above it reports a number above it.  The stop decision and the
+ * eager decision are those of full evaluation, whatever order the waves run in.
+ * The halves cannot run into each other: ldpc_graph.c refuses the fast kernels unless tasks + tickets + 64 < 2^16 and
+ * 64 x tasks < 2^16. */
+#define LDPC_Q_TICKET(w) ((int)((uint32_t)(w) & 0xffffu))
+#define LDPC_Q_BAD(w) ((int)((uint32_t)(w) >> 16))
+
+/* next ticket of a task queue (wave-uniform); the word as drawn: LDPC_Q_TICKET / LDPC_Q_BAD */
 __device__ __forceinline__ int ldpc_draw(int *counter, int lane)
 {
   int t = 0;
   if (lane == 0)
     t = atomicAdd(counter, 1);
+  return LDPC_UNIFORM(t);
+}
+
+/* the draw behind a check-node task of a parity-stop launch: also hands in how many lanes of the task saw an unsatisfied check.
+ * The vote is in here so that EVERY lane of the wave takes part in it, whatever it did in the task */
+__device__ __forceinline__ int ldpc_draw_count(int *counter, int lane, uint32_t syn)
+{
+  const int cnt = (int)__popcll(__ballot(syn != 0));
+  int t = 0;
+  if (lane == 0)
+    t = atomicAdd(counter, 1 + (cnt << 16));
   return LDPC_UNIFORM(t);
 }
 
@@ -196,8 +232,8 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
     }
   }
   if (tid < 16)
-    flags[tid] = 0; /* [0], [1] syndrome flags of odd / even passes, [2] CRC register, [3] TB abort seen, [6] eager check,
-                       [8], [9] task queues of even / odd passes */
+    flags[tid] = 0; /* [2] CRC register, [3] TB abort seen, [6] eager check, [7] diagnostic instantiation: tasks of the pass that
+                       ran without the parity, [8], [9] queue words of even / odd passes (unsatisfied lanes | tickets, see above) */
   /* (the message array is not initialised: the first check-node phase takes r = 0 without reading it and writes every
    * message, wrap-around bytes included)
    * APP := channel LLR (both copies), so that with r = 0 the first check-node phase sees q = llr */
@@ -279,7 +315,8 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
   if (fair)
     prio_slot = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 4) & 15u) / fair; /* HW_REG_HW_ID.wave_id / waves per SIMD and workgroup */
   for (int p = 1; p <= max_pass; ++p) {
-    uint32_t syn = 0;
+    uint32_t tsyn = 0;  /* the task in hand: byte flags of this thread's unsatisfied lanes */
+    bool skip = false;  /* (wave-uniform) the task in hand was drawn with the pass' count already above the eager bound */
     if (fair) {
       if ((p + prio_slot) & 1)
         __builtin_amdgcn_s_setprio(1);
@@ -297,7 +334,9 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
      * ticket (a draw is an LDS atomic round trip on a busy CU: 250-300 clocks, profiles/r04/timeline_phase_switch.txt) */
     int *const pq = &flags[8 + (p & 1)];
 #ifdef LDPC_ABLATE_CN
-    syn = 1;
+    int task = cn_ticket;
+    if (IO::syndrome && lane == 0)
+      atomicAdd(pq, 64 << 16); /* (nothing ever stops) */
 #else
     /* The phase's tasks are drawn in id order (= most expensive first, ldpc_graph.c) from a queue -- an LDS counter --
      * by whichever wave is free: the SIMD issue arbiter favours a CU's older waves, so static equal shares leave the
@@ -307,10 +346,30 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
      * comes out of the barrier with its task in hand: the draw is an LDS atomic round trip, and right after a barrier
      * nobody has work to hide it behind (profiles/r03/timeline_*.txt: 1.3 k clocks between the phases). */
     if (p == 1)
-      cn_ticket = ldpc_draw(pq, lane);
+      cn_ticket = LDPC_Q_TICKET(ldpc_draw(pq, lane));
     int task = cn_ticket;
-    for (; task < n_cn_tasks; task = ldpc_draw(pq, lane)) {
+    /* the draw behind a task (see the queue word above); a parity-stop launch hands the finished task's count in and learns
+     * whether the next one still has to look at the parity */
+    auto next_task = [&]() -> int {
+      if constexpr (IO::syndrome) {
+        const int w = ldpc_draw_count(pq, lane, tsyn);
+        skip = LDPC_SYN_SKIP && LDPC_Q_BAD(w) > LDPC_EAGER_MAX_BAD_LANES;
+        if constexpr (IO::pass_stamps) {
+          if (skip && LDPC_Q_TICKET(w) < n_cn_tasks && lane == 0)
+            atomicAdd(&flags[7], 1);
+        }
+        return LDPC_Q_TICKET(w);
+      } else {
+        return LDPC_Q_TICKET(ldpc_draw(pq, lane));
+      }
+    };
+    for (; task < n_cn_tasks; task = next_task()) {
       LDPC_TLOG_BEGIN();
+      tsyn = 0;
+      /* does this task evaluate the parity?  Not in pass 1 (see below), not in a CRC-stop launch, not once the pass has failed */
+      bool with_syn = false;
+      if constexpr (IO::syndrome)
+        with_syn = p >= 2 && !skip;
       const int deg_f = code->f_cn_task[task][0], ext = code->f_cn_task[task][1];
       const int item = code->f_cn_task[task][2] + lane;
       const int gstart = code->f_cn_task[task][3], gend = code->f_cn_task[task][4], srow0 = code->f_cn_task[task][5];
@@ -325,8 +384,7 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
           const int rigb = (int)ldpc_umulhi((uint32_t)gib, zq_magic), jb = gib - rigb * zq;
           const uint32_t reca = rowtbl[srow0 + riga], recb = rowtbl[srow0 + rigb];
           const int e0a = (int)(reca & 0x1ffu), e0b = (int)(recb & 0x1ffu);
-          const int valida = (int)(reca >> 16) - 4 * ja, validb = (int)(recb >> 16) - 4 * jb;
-          uint32_t ma = 0, mb = 0;
+          uint32_t mb = 0;
           bool mute = false;
           if constexpr (!IO::syndrome && IO::mute_items)
             mute = mute_check && ldpc_fast_item_is_mute(L, e0a, deg, ja) && ldpc_fast_item_is_mute(L, e0b, deg, jb);
@@ -336,14 +394,15 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
               ldpc_fast_item_zero_messages(L, e0b, deg, jb, Z, rstride);
             }
           } else if (p == 1)
-            (void)ldpc_fast_cn2_dispatch<true>(deg, L, e0a, ja, e0b, jb, Z, rstride, mb);
-          else
-            ma = ldpc_fast_cn2_dispatch<false>(deg, L, e0a, ja, e0b, jb, Z, rstride, mb);
-          const uint32_t maska = ldpc_fast_valid_lanes(valida), maskb = ldpc_fast_valid_lanes(validb);
-          if constexpr (IO::syndrome)
-            syn |= (ma & maska) | (mb & maskb);
-          else
-            (void)ma, (void)mb, (void)maska, (void)maskb;
+            (void)ldpc_fast_cn2_dispatch<true, false>(deg, L, e0a, ja, e0b, jb, Z, rstride, mb);
+          else if (with_syn) {
+            if constexpr (IO::syndrome) {
+              const uint32_t ma = ldpc_fast_cn2_dispatch<false, true>(deg, L, e0a, ja, e0b, jb, Z, rstride, mb);
+              const int valida = (int)(reca >> 16) - 4 * ja, validb = (int)(recb >> 16) - 4 * jb;
+              tsyn = (ma & ldpc_fast_valid_lanes(valida)) | (mb & ldpc_fast_valid_lanes(validb));
+            }
+          } else
+            (void)ldpc_fast_cn2_dispatch<false, false>(deg, L, e0a, ja, e0b, jb, Z, rstride, mb);
         }
       } else if (item < gend) {
         /* degree-19 rows: an item is shared by two neighbouring lanes (ldpc_graph.h f_pair19) */
@@ -351,11 +410,10 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
         const int gi = pair ? (item - gstart) >> 1 : item - gstart, half = (item - gstart) & 1;
         const int rig = (int)ldpc_umulhi((uint32_t)gi, zq_magic), j = gi - rig * zq;
         const uint32_t rowrec = rowtbl[srow0 + rig];
-        const int e0 = (int)(rowrec & 0x1ffu), valid = (int)(rowrec >> 16) - 4 * j; /* lanes t+i < pc_lo are checked */
+        const int e0 = (int)(rowrec & 0x1ffu);
         /* pass 1: the messages are all 0 and are not read (nor initialised by the prologue); what its check-node phase
-         * returns -- the parity of the CHANNEL's hard decisions -- is looked at by nobody (stops are decided from pass 3
-         * on, the eager check from pass 2 on), so it is not accumulated and the bodies drop it as dead code */
-        uint32_t m = 0;
+         * would return -- the parity of the CHANNEL's hard decisions -- is looked at by nobody (stops are decided from pass 3
+         * on, the eager check from pass 2 on), so the bodies are asked for none (SYN = false) */
         (void)half;
 #if !defined(__HIP_DEVICE_COMPILE__)
         /* host build (the CPU emulation with a thread per lane, tests/emul/): ldpc_fast_cn19_pair is device code, so the even
@@ -374,37 +432,35 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
         } else if (p == 1) {
 #if defined(__HIP_DEVICE_COMPILE__)
           if (pair)
-            (void)ldpc_fast_cn19_pair<true>(L, e0, j, Z, rstride, half);
+            (void)ldpc_fast_cn19_pair<true, false>(L, e0, j, Z, rstride, half);
           else
 #endif
-            (void)ldpc_fast_cn_dispatch<true>(deg, ext, L, e0, j, Z, rstride);
+            (void)ldpc_fast_cn_dispatch<true, false>(deg, ext, L, e0, j, Z, rstride);
+        } else if (with_syn) {
+          if constexpr (IO::syndrome) {
+            uint32_t m;
+#if defined(__HIP_DEVICE_COMPILE__)
+            if (pair)
+              m = ldpc_fast_cn19_pair<false, true>(L, e0, j, Z, rstride, half);
+            else
+#endif
+              m = ldpc_fast_cn_dispatch<false, true>(deg, ext, L, e0, j, Z, rstride);
+            const int valid = (int)(rowrec >> 16) - 4 * j; /* lanes t+i < pc_lo are checked */
+            tsyn = m & ldpc_fast_valid_lanes(valid);
+          }
         } else {
 #if defined(__HIP_DEVICE_COMPILE__)
           if (pair)
-            m = ldpc_fast_cn19_pair<false>(L, e0, j, Z, rstride, half);
+            (void)ldpc_fast_cn19_pair<false, false>(L, e0, j, Z, rstride, half);
           else
 #endif
-            m = ldpc_fast_cn_dispatch<false>(deg, ext, L, e0, j, Z, rstride);
+            (void)ldpc_fast_cn_dispatch<false, false>(deg, ext, L, e0, j, Z, rstride);
         }
-        const uint32_t mask = ldpc_fast_valid_lanes(valid);
-        if constexpr (IO::syndrome)
-          syn |= m & mask;
-        else
-          (void)m, (void)mask;
       }
       LDPC_TLOG_END(0, deg);
     }
 #endif
-    const int bn_ticket = task - n_cn_tasks;
-    {
-      /* flags[p & 1] = how many lanes saw an unsatisfied check of the previous pass (0 = none: the stop criterion; the
-       * count itself only steers the eager check below) */
-      if constexpr (IO::syndrome) {
-        const unsigned long long bad_lanes = __ballot(syn != 0);
-        if (bad_lanes && lane == 0)
-          atomicAdd(&flags[p & 1], (int)__popcll(bad_lanes));
-      }
-    }
+    const int bn_ticket = task - n_cn_tasks; /* (the draw that found the check-node tasks gone handed the last task's count in) */
     if (tid == 0) {
       flags[2] = 0;
       flags[8 + ((p + 1) & 1)] = 0; /* the next pass' queue: last drawn from before the previous pass' last barrier, first
@@ -416,11 +472,17 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
         flags[3] = 1;
     }
     __syncthreads();
+    /* unsatisfied lanes after pass p - 1, one per thread and task that saw any (0 for p = 1, which does not look): exact up to
+     * LDPC_EAGER_MAX_BAD_LANES, a lower bound above -- see the queue word.  (The low half is still being drawn from.) */
+    const int bad_prev = LDPC_Q_BAD(__hip_atomic_load(pq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
     if constexpr (IO::pass_stamps) {
       if (tid == 0 && p <= 9) {
         io.stamps()[2 * p] = (uint32_t)wall_clock64();
-        io.stamps()[22 + p] = (uint32_t)flags[p & 1];
+        io.stamps()[22 + p] = (uint32_t)bad_prev;
+        io.stamps()[32 + p] = (uint32_t)flags[7];
       }
+      if (tid == 0)
+        flags[7] = 0; /* (next added to behind the bit-node barrier) */
     }
     if (io.has_abort() && flags[3]) { /* (set by one of the two abort sources) */
       n_iter = max_pass + 1;
@@ -429,8 +491,7 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
     /* (the core columns' device copy, written in the prologue by this workgroup's own waves, is read from here on: the
      * barriers since then order it at workgroup scope, which is all a CU's write-through vector cache needs; an agent-
      * scope fence here would write back and invalidate the XCD's L2) */
-    const int bad_prev = flags[p & 1]; /* unsatisfied lanes after pass p - 1 (after the channel's hard decisions for p = 1) */
-    if (!io.use_crc() && p >= 3 && flags[p & 1] == 0) {
+    if (!io.use_crc() && p >= 3 && bad_prev == 0) {
       n_iter = p - 1;
       break;
     }
@@ -438,7 +499,7 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
     if constexpr (IO::bn_tickets) {
     /* the next ticket is asked for behind an item's gather and looked at behind its store: the draw's round trip runs
      * under the tail of the task (profiles/r04/decoder_ab25_late_draw.txt) */
-    for (int ticket = bn_ticket, nxt = 0; ticket < n_bn_tickets; ticket = LDPC_UNIFORM(nxt) - n_cn_tasks) {
+    for (int ticket = bn_ticket, nxt = 0; ticket < n_bn_tickets; ticket = LDPC_Q_TICKET(LDPC_UNIFORM(nxt)) - n_cn_tasks) {
       LDPC_TLOG_BEGIN();
       /* (ticket and task record in one scalar load) */
       const int item0 = code->f_bn_rec[ticket][0] + lane, end = code->f_bn_rec[ticket][1];
@@ -477,7 +538,7 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
       LDPC_TLOG_END(1, maxdeg);
     }
     } else {
-    for (int ticket = bn_ticket; ticket * bn_group < n_bn_tasks; ticket = ldpc_draw(pq, lane) - n_cn_tasks) {
+    for (int ticket = bn_ticket; ticket * bn_group < n_bn_tasks; ticket = LDPC_Q_TICKET(ldpc_draw(pq, lane)) - n_cn_tasks) {
       for (int task = ticket * bn_group; task < (ticket + 1) * bn_group && task < n_bn_tasks; task++) {
         LDPC_TLOG_BEGIN();
         const int item = code->f_bn_task[task][0] + lane, end = code->f_bn_task[task][1];
@@ -493,9 +554,7 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
     }
     }
 #endif
-    cn_ticket = ldpc_draw(&flags[8 + ((p + 1) & 1)], lane);
-    if (tid == 0)
-      flags[(p + 1) & 1] = 0;
+    cn_ticket = LDPC_Q_TICKET(ldpc_draw(&flags[8 + ((p + 1) & 1)], lane));
     __syncthreads();
     if constexpr (IO::pass_stamps) {
       if (tid == 0 && p <= 9)

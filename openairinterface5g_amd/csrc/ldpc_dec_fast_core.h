@@ -226,7 +226,7 @@ LDPC_HD void ldpc_fast_cn_edge(const ldpc_fast_lds &L, uint32_t info, int t, uin
  * In all the check-node bodies the suffixes l / h (_lo / _hi) of a packed register stand for lanes (0,2) / (1,3). */
 /* boff_r / boff_a (several blocks per workgroup, ldpc_dec_fast_mblock.h): byte offset of the item's block inside a
  * message / extension-LLR row resp. inside an APP row; 0 in the one-block kernels, where they fold away. */
-template <int D, bool EXT, int MODE, bool P1 = false>
+template <int D, bool EXT, int MODE, bool P1 = false, bool SYN = true>
 LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int rstride, int boff_r = 0, int boff_a = 0)
 {
   const int t = 4 * j + boff_r, ta = 4 * j + boff_a; /* t: position in message and extension rows; ta: in APP rows */
@@ -239,12 +239,12 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
 #pragma unroll
   for (int k = 0; k < D; k++) {
     const uint32_t info = L.etbl[e0 + k];
-    const uint32_t rw = P1 ? 0u : *reinterpret_cast<const uint32_t *>(rrow + k * rstride);
+    const uint32_t rw = (P1 || (!SYN && EXT && k == D - 1)) ? 0u : *reinterpret_cast<const uint32_t *>(rrow + k * rstride);
     uint32_t dl, dh;
     if (EXT && k == D - 1)
-      ldpc_fast_cn_edge<true, P1>(L, info, t, rw, true, dl, dh, parw, extl, exth);
+      ldpc_fast_cn_edge<true, P1>(L, info, t, rw, SYN, dl, dh, parw, extl, exth);
     else
-      ldpc_fast_cn_edge<false, P1>(L, info, ta, rw, true, dl, dh, parw, extl, exth);
+      ldpc_fast_cn_edge<false, P1>(L, info, ta, rw, SYN, dl, dh, parw, extl, exth);
     if (MODE <= 1) {
       d_lo[k] = dl;
       d_hi[k] = dh;
@@ -280,7 +280,7 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
       dh = d_hi[k];
     } else {
       const uint32_t info = L.etbl[e0 + k];
-      const uint32_t rw = P1 ? 0u : *reinterpret_cast<const uint32_t *>(rrow + k * rstride);
+      const uint32_t rw = (P1 || (EXT && k == D - 1)) ? 0u : *reinterpret_cast<const uint32_t *>(rrow + k * rstride);
       if (EXT && k == D - 1)
         ldpc_fast_cn_edge<true, P1>(L, info, t, rw, false, dl, dh, parw, extl, exth);
       else
@@ -297,7 +297,7 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
   }
   /* per lane: number of "not negative" neighbours mod 2, from bit 7 of the biased APP bytes and bit 8 of
    * the extension sums; parity of the hard decisions = that ^ (D & 1) */
-  return ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw, EXT, extl, exth, D);
+  return SYN ? ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw, EXT, extl, exth, D) : 0u;
 }
 
 /* The same check-node item with the "minimum of the OTHER edges" taken from prefixes and suffixes instead of through the
@@ -310,7 +310,7 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
  * (tools/ubench/valu_rate.hip).  The sign bytes of an edge are gathered once in the forward sweep (one v_perm, needed
  * anyway) and kept instead of the two difference words.  Registers per edge: M per half + signs, P per half and pair.
  * Bit-identical outputs: the minimum over the other edges is the same number whichever way it is found. */
-template <int D, bool EXT, bool P1 = false>
+template <int D, bool EXT, bool P1 = false, bool SYN = true>
 LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, int rstride, int boff_r = 0, int boff_a = 0)
 {
   const int t = 4 * j + boff_r, ta = 4 * j + boff_a;
@@ -323,12 +323,12 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
 #pragma unroll
   for (int k = 0; k < D; k++) {
     const uint32_t info = L.etbl[e0 + k];
-    const uint32_t rw = P1 ? 0u : *reinterpret_cast<const uint32_t *>(rrow + k * rstride);
+    const uint32_t rw = (P1 || (!SYN && EXT && k == D - 1)) ? 0u : *reinterpret_cast<const uint32_t *>(rrow + k * rstride);
     uint32_t dl, dh;
     if (EXT && k == D - 1)
-      ldpc_fast_cn_edge<true, P1>(L, info, t, rw, true, dl, dh, parw, extl, exth);
+      ldpc_fast_cn_edge<true, P1>(L, info, t, rw, SYN, dl, dh, parw, extl, exth);
     else
-      ldpc_fast_cn_edge<false, P1>(L, info, ta, rw, true, dl, dh, parw, extl, exth);
+      ldpc_fast_cn_edge<false, P1>(L, info, ta, rw, SYN, dl, dh, parw, extl, exth);
     const ldpc_v2u ml = ldpc_sm_key(dl);
     const ldpc_v2u mh = ldpc_sm_key(dh);
     m_lo[k] = ldpc_u2u32(ml);
@@ -372,7 +372,7 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
       sh = last ? ldpc_pminu(a0h, a1h) : ldpc_pmin3_keys(sh, a0h, a1h);
     }
   }
-  return ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw, EXT, extl, exth, D);
+  return SYN ? ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw, EXT, extl, exth, D) : 0u;
 }
 
 /* TWO items of one degree group per thread (a double task, ldpc_graph.h f_cn_task), walked edge by edge TOGETHER: the same
@@ -380,7 +380,7 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
  * arithmetic -> store overlap inside one wave.  e0x / jx = first edge and 4-lane group of item x; returns item A's mask, item
  * B's in mask_b.  (An inactive second item is given item A's coordinates by the caller: it then stores the same bytes
  * twice.) */
-template <int D, bool EXT, bool P1 = false>
+template <int D, bool EXT, bool P1 = false, bool SYN = true>
 LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e0b, int jb, int Z, int rstride, uint32_t &mask_b)
 {
   constexpr int N = 2, NP = D / 2;
@@ -400,15 +400,15 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
 #pragma unroll
     for (int n = 0; n < N; n++) {
       info[n] = L.etbl[e0[n] + k];
-      rw[n] = P1 ? 0u : *reinterpret_cast<const uint32_t *>(rrow[n] + k * rstride);
+      rw[n] = (P1 || (!SYN && EXT && k == D - 1)) ? 0u : *reinterpret_cast<const uint32_t *>(rrow[n] + k * rstride);
     }
 #pragma unroll
     for (int n = 0; n < N; n++) {
       uint32_t dl, dh;
       if (EXT && k == D - 1)
-        ldpc_fast_cn_edge<true, P1>(L, info[n], t[n], rw[n], true, dl, dh, parw[n], extl[n], exth[n]);
+        ldpc_fast_cn_edge<true, P1>(L, info[n], t[n], rw[n], SYN, dl, dh, parw[n], extl[n], exth[n]);
       else
-        ldpc_fast_cn_edge<false, P1>(L, info[n], t[n], rw[n], true, dl, dh, parw[n], extl[n], exth[n]);
+        ldpc_fast_cn_edge<false, P1>(L, info[n], t[n], rw[n], SYN, dl, dh, parw[n], extl[n], exth[n]);
       const ldpc_v2u ml = ldpc_sm_key(dl);
       const ldpc_v2u mh = ldpc_sm_key(dh);
       m_lo[n][k] = ldpc_u2u32(ml);
@@ -459,7 +459,7 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
   uint32_t out[N];
 #pragma unroll
   for (int n = 0; n < N; n++) {
-    out[n] = ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw[n], EXT, extl[n], exth[n], D);
+    out[n] = SYN ? ldpc_fast_odd_lanes<LDPC_SEL_EO>(parw[n], EXT, extl[n], exth[n], D) : 0u;
   }
   mask_b = out[1];
   return out[0];
@@ -470,13 +470,13 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
 #else
 #define LDPC_CN2_ATTR LDPC_HD
 #endif
-template <bool P1 = false>
+template <bool P1 = false, bool SYN = true>
 LDPC_CN2_ATTR uint32_t ldpc_fast_cn2_dispatch(int deg, const ldpc_fast_lds &L, int e0a, int ja, int e0b, int jb, int Z, int rstride, uint32_t &mask_b)
 {
   switch (deg) {
-    case 3: return ldpc_fast_cn_ps2<3, true, P1>(L, e0a, ja, e0b, jb, Z, rstride, mask_b);
-    case 4: return ldpc_fast_cn_ps2<4, true, P1>(L, e0a, ja, e0b, jb, Z, rstride, mask_b);
-    default: return ldpc_fast_cn_ps2<5, true, P1>(L, e0a, ja, e0b, jb, Z, rstride, mask_b);
+    case 3: return ldpc_fast_cn_ps2<3, true, P1, SYN>(L, e0a, ja, e0b, jb, Z, rstride, mask_b);
+    case 4: return ldpc_fast_cn_ps2<4, true, P1, SYN>(L, e0a, ja, e0b, jb, Z, rstride, mask_b);
+    default: return ldpc_fast_cn_ps2<5, true, P1, SYN>(L, e0a, ja, e0b, jb, Z, rstride, mask_b);
   }
 }
 
@@ -487,7 +487,7 @@ LDPC_CN2_ATTR uint32_t ldpc_fast_cn2_dispatch(int deg, const ldpc_fast_lds &L, i
  * CPU emulation calls the one-lane body once per pair: same results). */
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ uint32_t ldpc_swap_pair(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false); }
-template <bool P1>
+template <bool P1, bool SYN = true>
 __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, int e0, int j, int Z, int rstride, int half)
 {
   /* the pair network of ldpc_fast_cn_ps over this lane's ten slots; the partner lane's minimum over ALL its edges is the
@@ -507,7 +507,7 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
     const uint32_t info = L.etbl[ebase + kk];
     const uint32_t rw = P1 ? 0u : *reinterpret_cast<const uint32_t *>(rrow + kk * rstride);
     uint32_t dl, dh, pw = 0;
-    ldpc_fast_cn_edge<false, P1>(L, info, t, rw, true, dl, dh, pw, extl, exth);
+    ldpc_fast_cn_edge<false, P1>(L, info, t, rw, SYN, dl, dh, pw, extl, exth);
     ldpc_v2u ml = ldpc_sm_key(dl);
     ldpc_v2u mh = ldpc_sm_key(dh);
     uint32_t sg = ldpc_perm(dh, dl, LDPC_SEL_SIGNS);
@@ -519,7 +519,8 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
     m_lo[k] = ldpc_u2u32(ml); m_hi[k] = ldpc_u2u32(mh);
     s4[k] = sg;
     sx4 ^= sg;
-    parw ^= pw;
+    if (SYN)
+      parw ^= pw;
     if (k & 1) {
       const int i = k / 2;
       p_lo[i] = ldpc_u2u32(ldpc_pmin3_keys(i ? ldpc_as_v2u(p_lo[i - 1]) : cap, ldpc_as_v2u(m_lo[k - 1]), ml));
@@ -529,7 +530,8 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
   /* the partner lane's minimum over all its edges starts this lane's suffix; signs and parity are merged */
   ldpc_v2u sl = ldpc_as_v2u(ldpc_swap_pair(p_lo[NP - 1])), sh = ldpc_as_v2u(ldpc_swap_pair(p_hi[NP - 1]));
   sx4 ^= ldpc_swap_pair(sx4);
-  parw ^= ldpc_swap_pair(parw);
+  if (SYN)
+    parw ^= ldpc_swap_pair(parw);
   sx4 ^= 0x80808080u; /* 19 - 1 others: an even count (see ldpc_fast_cn_ps; a neutral slot xor-ed zeros into sx4) */
 #pragma unroll
   for (int i = NP - 1; i >= 0; i--) {
@@ -552,7 +554,7 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
       sh = ldpc_pmin3_keys(sh, ldpc_as_v2u(m_hi[2 * i]), ldpc_as_v2u(m_hi[2 * i + 1]));
     }
   }
-  return ldpc_fast_odd_lanes(parw, false, 0u, 0u, 19);
+  return SYN ? ldpc_fast_odd_lanes(parw, false, 0u, 0u, 19) : 0u;
 }
 #endif
 
@@ -598,26 +600,26 @@ LDPC_HD uint32_t ldpc_fast_pc(const ldpc_fast_lds &L, int D, int ext, int e0, in
 #define LDPC_F_MODE_D19 2
 #endif
 /* dispatch on the task's (wave-uniform) degree */
-template <bool P1 = false>
+template <bool P1 = false, bool SYN = true>
 LDPC_HD uint32_t ldpc_fast_cn_dispatch(int deg, int ext, const ldpc_fast_lds &L, int e0, int j, int Z, int rstride, int boff_r = 0,
                                        int boff_a = 0)
 {
   if (!ext) {
     switch (deg) {
-      case 19: return ldpc_fast_cn<19, false, LDPC_F_MODE_D19, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-      case 10: return ldpc_fast_cn_ps<10, false, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-      default: return ldpc_fast_cn_ps<8, false, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
+      case 19: return ldpc_fast_cn<19, false, LDPC_F_MODE_D19, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+      case 10: return ldpc_fast_cn_ps<10, false, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+      default: return ldpc_fast_cn_ps<8, false, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
     }
   }
   switch (deg) {
-    case 3: return ldpc_fast_cn_ps<3, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-    case 4: return ldpc_fast_cn_ps<4, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-    case 5: return ldpc_fast_cn_ps<5, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-    case 6: return ldpc_fast_cn_ps<6, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-    case 7: return ldpc_fast_cn_ps<7, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-    case 8: return ldpc_fast_cn_ps<8, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-    case 9: return ldpc_fast_cn_ps<9, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
-    default: return ldpc_fast_cn_ps<10, true, P1>(L, e0, j, Z, rstride, boff_r, boff_a);
+    case 3: return ldpc_fast_cn_ps<3, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+    case 4: return ldpc_fast_cn_ps<4, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+    case 5: return ldpc_fast_cn_ps<5, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+    case 6: return ldpc_fast_cn_ps<6, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+    case 7: return ldpc_fast_cn_ps<7, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+    case 8: return ldpc_fast_cn_ps<8, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+    case 9: return ldpc_fast_cn_ps<9, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
+    default: return ldpc_fast_cn_ps<10, true, P1, SYN>(L, e0, j, Z, rstride, boff_r, boff_a);
   }
 }
 

@@ -322,6 +322,11 @@ static void build_fast_section(ldpc_code_desc_t *d, int shape, int mb, int pair1
   for (int r = 0; r < d->nrows; r++)
     if (d->pc_lo[r] & 3)
       return; /* (never for NR's lifting sizes; f_ok stays 0: the generic kernel serves the code) */
+  /* the queue word of a pass is {unsatisfied lanes : 16 | tickets : 16} (ldpc_dec_fast_block.h): every wave draws one ticket past
+   * the end (at most 64 waves), and a task hands in at most 64 lanes.  (f_n_bn_tickets <= f_n_bn_tasks, which bounds the draws of
+   * the callers that queue by f_bn_group as well) */
+  if (d->f_n_cn_tasks + d->f_n_bn_tasks + 64 >= 65536 || 64 * d->f_n_cn_tasks >= 65536)
+    return;
   d->f_ok = 1;
 }
 

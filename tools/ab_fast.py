@@ -67,9 +67,9 @@ def main():
             k, _, val = kv.partition("=")
             env[k] = val
         r = subprocess.run([sys.executable, __file__, "--child"], capture_output=True, text=True, env=env, timeout=900)
-        if r.returncode != 0:
-            print(f"{label}: FAILED\n{r.stderr[-1500:]}")
-            continue
+        if r.returncode != 0:       # (nothing more is started on a GPU that may have faulted)
+            print(f"{label}: FAILED with exit status {r.returncode}, the remaining variants are not run\n{r.stderr[-1500:]}")
+            sys.exit(1)
         rows[label] = json.loads(r.stdout.strip().splitlines()[-1])
     keys = list(next(iter(rows.values())).keys()) if rows else []
     print("%-26s" % "case" + "".join("%16s" % l for l in rows))

@@ -10,7 +10,8 @@ for tu in ldpc_decoder_fast ldpc_server tb_rx_fused; do
   /opt/rocm/bin/hipcc $F "$@" -c $tu.hip -o $B/$tu.o &
 done
 wait
+# (every other object of the Makefile's list as `make` left it)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic-functions -Wl,--version-script=exports.map \
-  -o ../../tools/ab/libldpc_hip_$name.so build/ldpc_decoder.o $B/ldpc_decoder_fast.o $B/ldpc_server.o build/ldpc_encoder.o build/ldpc_api.o \
-  build/ldpc_graph.o build/tb_chain.o $B/tb_rx_fused.o build/nr_coding_host.o -lpthread
+  -o ../../tools/ab/libldpc_hip_$name.so $B/ldpc_decoder_fast.o $B/ldpc_server.o $B/tb_rx_fused.o \
+  $(ls build/*.o | grep -v -e /ldpc_decoder_fast.o -e /ldpc_server.o -e /tb_rx_fused.o) -lpthread
 rm -rf $B

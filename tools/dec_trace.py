@@ -54,9 +54,12 @@ def analyse(d, label, ms_untraced):
             prev = np.where(have_b, b, a)
         eager = [(int(((w[sel, 20] >> p) & 1).sum())) for p in range(1, 10)]
         bad = [int(np.median(w[sel, 22 + p])) for p in range(1, min(k + 1, 9) + 1)]
+        noparity = [int(np.median(w[sel, 32 + p])) for p in range(1, min(k + 1, 9) + 1)]
         print(f"   n_iter = {k}: {int(sel.sum())} blocks, total {dur[sel].mean():.2f} us | check-node + bit-node phase per pass (us; a phase that "
               f"follows a parity sweep includes it): " + ", ".join(row))
-        print(f"      parity sweeps run behind pass 1..9 by this many blocks: {eager}; median unsatisfied lanes counted in pass 1..: {bad}")
+        print(f"      parity sweeps run behind pass 1..9 by this many blocks: {eager}; median unsatisfied lanes counted in pass 1.. "
+              f"(one per thread and task; exact up to 96, a lower bound above -- the tasks drawn after that skip the parity): {bad}; "
+              f"median check-node tasks that ran without the parity in pass 1..: {noparity}")
     # per CU: order, gaps, busy
     gaps, busy, last_end, per_cu_n = [], np.zeros(ncu), np.zeros(ncu), np.zeros(ncu, dtype=int)
     for c in range(ncu):
