@@ -1,8 +1,8 @@
 """The UL receive chain on the GPU on the frequency-selective slots of ul_slot_np.py, every DMRS port on the air: one
 pusch_channel_estimation call for the descriptors of every layer (layer l's set at ch_off + l n_rx ch_stride), channel_level_grid
-and channel_compensation_grid (one layer) or channel_level_grid_mmse and mmse_2layers_grid (two layers), and decode_symbols, all on
-one side stream with nothing but descriptors, est_delay, max_ch and nvar uploaded.  ul_ch must equal the CPU form's estimates over
-the whole array, the shifts and records the numpy receivers run on those estimates, the decoder's results those of the same call
+and channel_compensation_grid (one layer) or channel_level_grid_mmse and mmse_2layers_grid (two layers), and decode_symbols -- two
+layers below 64QAM: channel_level_grid_ml, ml_2layers_grid and decode_scrambled on the LLRs --, all on one side stream with nothing
+but descriptors, est_delay, max_ch and nvar uploaded.  ul_ch must equal the CPU form's estimates over the whole array, the shifts and records the numpy receivers run on those estimates, the decoder's results those of the same call
 fed the numpy record; and the block must decode.  test_ul_slot_host.py holds the same estimates to the true channel and shows on
 the CPU that a subtly wrong estimator would fail these slots."""
 import numpy as np
@@ -40,6 +40,10 @@ def run_device(m, sl, record=None):
             if L == 1:
                 m.ulsch_channel_level_grid(ch_d, n_rx, sl["ch_stride"], sl["first"], out=lv_d)
                 m.ulsch_channel_compensation_grid(rx_d, ch_d, n_rx, sl["rx_stride"], sl["ch_stride"], sl["gsegs"], lv_d, rec)
+            elif U.is_ml(c):                                               # rec holds the block's LLRs
+                mc_d = torch.tensor([sl["max_ch"]], dtype=torch.int32, device="cuda")
+                m.ulsch_channel_level_grid_ml(ch_d, n_rx, sl["ch_stride"], sl["first"], mc_d, out=lv_d)
+                m.ulsch_ml_2layers_grid(rx_d, ch_d, n_rx, sl["rx_stride"], sl["ch_stride"], sl["gsegs"], lv_d, rec)
             else:
                 mc_d = torch.tensor([sl["max_ch"]], dtype=torch.int32, device="cuda")
                 nv_d = torch.tensor([sl["nvar"]], dtype=torch.int32, device="cuda")
@@ -47,7 +51,7 @@ def run_device(m, sl, record=None):
                 m.ulsch_mmse_2layers_grid(rx_d, ch_d, n_rx, sl["rx_stride"], sl["ch_stride"], sl["gsegs"], lv_d, nv_d, rec)
         else:
             rec = torch.from_numpy(record).cuda()
-        m.ulsch_decode_symbols_device(rxt, rec, harq, out, ack, itm, [sl["scr"]])
+        (m.ulsch_decode_scrambled_device if U.is_ml(c) else m.ulsch_decode_symbols_device)(rxt, rec, harq, out, ack, itm, [sl["scr"]])
     torch.cuda.synchronize()
     return (None if ch_d is None else ch_d.cpu().numpy().reshape(-1, 2), int(lv_d[0]), rec.cpu().numpy(), out.cpu().numpy()[:tb["A"] // 8],
             ack.cpu().numpy(), itm.cpu().numpy(), harq.cpu().numpy())

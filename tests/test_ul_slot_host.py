@@ -148,6 +148,9 @@ def test_selective_slot_on_the_cpu_forms(built, name):
         print(f"    {what}: error {p_int:.0f} interior ({p_int / b_int:.1f} x bound), {p_edge:.0f} edge ({p_edge / b_edge:.1f} x)")
         f = c["delay_factor"] if what.startswith("est_delay") else 3.0
         assert p_int >= f * b_int or p_edge >= f * b_edge, (name, what, p_int, b_int, p_edge, b_edge)
-        if must_fail:
+        if what in c["survives"]:                         # QPSK: the estimate misses its bound, the block decodes all the same
+            got, ack, iters = U.decode_record(sl, U.front_records(sl, chp, m)[1])
+            assert must_fail and ack and np.array_equal(got, sl["pay"]), (name, what, iters)
+        elif must_fail:
             got, ack, iters = U.decode_record(sl, U.front_records(sl, chp, m)[1])
             assert not ack and max(iters) > U.MAX_ITER and not np.array_equal(got, sl["pay"]), (name, what, iters)

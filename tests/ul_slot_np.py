@@ -1,5 +1,6 @@
 """A float64 PUSCH slot on the OFDM grid with a frequency-selective channel, and the receive chain that must invert it: DMRS
-channel estimation, channel level, compensation (one layer) or the two-layer MMSE receiver, de-mapping and decoding.  The model
+channel estimation, channel level, compensation (one layer) or the two-layer MMSE receiver (below 64QAM: the max-log ML
+receiver), de-mapping and decoding.  The model
 knows nothing of csrc/ but what a transmitter has too: the layer planes of dlsch_encode_symbols_host and the conjugated pilots of
 pusch_dmrs_host (the pilot on the air is their conjugate).  test_ul_slot_host.py runs the chain on the CPU forms, test_gpu_ul_slot.py
 on the GPU, both on the slots of CASES.
@@ -34,6 +35,7 @@ import rx_chest_np as chest_ref
 from layer_np import symbols_np
 from qam_np import demap_np
 from rx_front_np import compensate_np, level_np
+from rx_ml_np import level_ml_np, llr_np, ml_np
 from rx_mmse_np import level_mmse_np, mmse_np, records_np
 from test_scrambling_host import c_init_of
 from test_tb_scrambled_emul import unscramble
@@ -48,10 +50,15 @@ SIGMA_2L = 3.0                          # E2E_SIGMA of test_rx_mmse_host.py
 GAIN_2L = (400.0, 480.0)                # E2E_GAIN of test_rx_mmse_host.py
 
 
-def _case(name, mode, ports, n_rx, Qm, N, tau, gain, e_rel, tau2, rate, seed, rb=10, cdm=1, BG=1, delay_factor=3.0):
+def _case(name, mode, ports, n_rx, Qm, N, tau, gain, e_rel, tau2, rate, seed, rb=10, cdm=1, BG=1, delay_factor=3.0, corr=0.0, survives=()):
     return dict(name=name, mode=mode, ports=ports, n_layers=len(ports), n_rx=n_rx, Qm=Qm, N=N, tau=tau, gain=gain, e_rel=e_rel, tau2=tau2,
                 rate=rate, seed=seed, rb=rb, cdm=cdm, BG=BG, delay_checks=not ports[0] & 2, delay_factor=delay_factor,
-                sigma=SIGMA_1L if len(ports) == 1 else SIGMA_2L)
+                sigma=SIGMA_1L if len(ports) == 1 else SIGMA_2L, corr=corr, survives=survives)
+
+
+def is_ml(case):
+    """two layers below 64QAM go through the max-log ML receiver, which writes LLRs, not symbol records"""
+    return case["n_layers"] == 2 and case["Qm"] < 6
 
 
 # One layer: every estimator mode, port 0 (w_f constant), port 1 (w_f alternates) and port 2 (type 1, delta = 1; two CDM groups without
@@ -60,6 +67,8 @@ def _case(name, mode, ports, n_rx, Qm, N, tau, gain, e_rel, tau2, rate, seed, rb
 # test_ul_slot_host.py allow each mode: the interpolating modes take the main tap's delay out, the averaging ones and the
 # separation of two ports on one comb do not.  The code rates are high enough that an estimate a few REs off no longer decodes.
 # delay_factor: by how much a wrong est_delay must miss the bound (test_ul_slot_host.py says why "2L-T1I" cannot reach 3).
+# The last two go through the ML receiver (two layers, QPSK and 16QAM) with the layers' columns at correlation 0.6.  survives: the
+# perturbations after which the block decodes all the same -- QPSK at 40 dB takes a negated delay's 25 degrees.
 CASES = [
     _case("1L-T1I-p0", T1I, (0,), 2, 6, 256, (6, -5), (2200.0, 2600.0), 0.010, 9, 0.80, 11),
     _case("1L-T2I-p1", T2I, (1,), 4, 8, 512, (8, -7, 6, -8), (2200.0, 2600.0), 0.010, 11, 0.80, 12),
@@ -70,6 +79,9 @@ CASES = [
     _case("2L-T2I", T2I, (0, 1), 2, 6, 512, (5, -4), GAIN_2L, 0.010, 9, 0.75, 22),
     _case("2L-T1A", T1A, (0, 1), 4, 6, 512, (1, -1, 1, -1), GAIN_2L, 0.010, 3, 0.75, 23),
     _case("2L-T2A", T2A, (0, 1), 2, 6, 512, (1, -1), GAIN_2L, 0.010, 3, 0.75, 24),
+    # through the ML receiver, the layers' columns at correlation 0.6 (build_slot): 16QAM on four antennas, QPSK on two
+    _case("2L-T1I-ml16", T1I, (0, 1), 4, 4, 512, (7, -6, 5, -7), GAIN_2L, 0.007, 10, 0.88, 31, delay_factor=2.0, corr=0.6),
+    _case("2L-T1I-ml4", T1I, (0, 1), 2, 2, 512, (7, -6), GAIN_2L, 0.007, 10, 0.92, 32, delay_factor=2.0, corr=0.6, survives=("est_delay negated",)),
 ]
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 
@@ -135,7 +147,13 @@ def build_slot(m, case):
     if L == 1:
         g = col[None]
     else:                                                              # mmse_e2e_case: layer 1 is layer 0 turned and sign-alternated
-        g = np.stack([col, col * np.exp(1j * rng.uniform(0, 2 * np.pi)) * (-1.0) ** np.arange(n_rx)])
+        o = col * np.exp(1j * rng.uniform(0, 2 * np.pi)) * (-1.0) ** np.arange(n_rx)
+        if c["corr"]:
+            # ... plus corr times layer 0's column a quarter turn from it: every path keeps its gain, |c j + sqrt(1 - c^2)| = 1, and
+            # the columns' correlation is corr but for the spread of the gains
+            o = 1j * c["corr"] * o / (-1.0) ** np.arange(n_rx) + np.sqrt(1.0 - c["corr"] ** 2) * o
+            assert abs(abs(np.vdot(col, o)) / (np.linalg.norm(col) * np.linalg.norm(o)) - c["corr"]) < 0.03
+        g = np.stack([col, o])
     e = c["e_rel"] * np.abs(g) * np.exp(1j * rng.uniform(0, 2 * np.pi, g.shape))
     k = np.arange(12 * rb)
     h = (g[..., None] * np.exp(-2j * np.pi * k * tau[None, :, None] / N) + e[..., None] * np.exp(-2j * np.pi * k * c["tau2"] / N))
@@ -262,6 +280,15 @@ def front_records(sl, ch, m=None):
             a, b = _extract(sl, ch, s)
             out = m.ulsch_compensate_host(a, b, n_rx, s["nb_re"], s["nb_re"], Qm, lv) if m else compensate_np(a, b, Qm, lv)
             rec.reshape(Qm // 2, plane, 2)[:, s["sym_off"]:s["sym_off"] + s["nb_re"]] = out
+    elif is_ml(c):                                                     # the "record" is the block's LLRs
+        if m:
+            lv = int(m.ulsch_level_ml_host(chf, n_rx, f["nb_re"], f["nb_re"], sl["max_ch"])[0])
+        else:
+            lv = int(level_ml_np(chf.reshape(2, n_rx, f["nb_re"], 2), sl["max_ch"])[0])
+        for s in sl["gsegs"]:
+            a, b = _extract(sl, ch, s)
+            out = m.ulsch_ml_2layers_host(a, b, n_rx, s["nb_re"], s["nb_re"], Qm, lv) if m else ml_np(a, b.reshape(2, n_rx, s["nb_re"], 2), Qm, lv)
+            llr_np(rec, out, Qm, s["sym_off"])
     else:
         if m:
             lv = int(m.ulsch_level_mmse_host(chf, n_rx, f["nb_re"], f["nb_re"], sl["max_ch"])[0])
@@ -278,10 +305,11 @@ def front_records(sl, ch, m=None):
 
 
 def decode_record(sl, rec):
-    """(payload, ack, per-segment pass counts) of the record through demap_np, unscramble and the oracle's decoder"""
+    """(payload, ack, per-segment pass counts) of the record through demap_np (the ML receiver's LLRs: as they are), unscramble and
+    the oracle's decoder"""
     tb, Qm = sl["tb"], sl["case"]["Qm"]
     pl = rec.reshape(Qm // 2, tb["G"] // Qm, 2)
-    llr = unscramble(demap_np(pl[0], list(pl[1:]), Qm), c_init_of(*sl["scr"]), 0)
+    llr = unscramble(rec if is_ml(sl["case"]) else demap_np(pl[0], list(pl[1:]), Qm), c_init_of(*sl["scr"]), 0)
     s = O.segmentation(None, O.len_with_crc(1, tb["A"]), tb["BG"])
     harq = [np.zeros(66 * 384 + 16, np.int16) for _ in range(s["C"])]
     got, ack, iters, _ = O.ulsch_decode(tb, llr, harq, MAX_ITER)
