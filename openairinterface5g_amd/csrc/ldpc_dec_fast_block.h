@@ -509,10 +509,10 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
           const int sc = (int)ldpc_umulhi((uint32_t)item0, zq_magic), j = item0 - sc * zq;
           const uint32_t colrec = coltbl[sc];
           const uint32_t lw = src32[(int)(colrec & 0xffu) * zq + j];
-          uint32_t acc_e = 0, acc_o = 0;
-          ldpc_fast_bn_gather(L, colrec, maxdeg, j, Z, 0, acc_e, acc_o);
+          uint32_t ae = 0, at = 0; /* ldpc_fast_bn_acc */
+          ldpc_fast_bn_gather(L, colrec, maxdeg, j, Z, 0, ae, at);
           nxt = ldpc_draw_issue(pq, lane);
-          ldpc_fast_bn_finish(L, (int)(colrec & 0xffu), (int)((colrec >> 8) & 0xffu), j, Z, astride, lw, acc_e, acc_o, 0);
+          ldpc_fast_bn_finish(L, (int)(colrec & 0xffu), (int)((colrec >> 8) & 0xffu), j, Z, astride, lw, ae, at, 0);
         } else {
           nxt = ldpc_draw_issue(pq, lane);
         }

@@ -327,6 +327,11 @@ static void build_fast_section(ldpc_code_desc_t *d, int shape, int mb, int pair1
    * the callers that queue by f_bn_group as well) */
   if (d->f_n_cn_tasks + d->f_n_bn_tasks + 64 >= 65536 || 64 * d->f_n_cn_tasks >= 65536)
     return;
+  /* the bit-node gathers sum three bytes of every window in one 32-bit word (ldpc_fast_bn_acc): with the LLR word at most
+   * 32 terms of 255 to a byte sum, i.e. at most 31 edges to a column (NR's largest: 30) */
+  for (int c = 0; c < d->ncore; c++)
+    if (d->col_ptr[c + 1] - d->col_ptr[c] > 31)
+      return;
   d->f_ok = 1;
 }
 

@@ -173,36 +173,6 @@ LDPC_HD uint32_t ldpc_fast_odd_lanes(uint32_t parw, bool ext, uint32_t extl, uin
  * multiple of 4 (a class of nr rows drops lanes nr Z - 32 .. nr Z - 1; ldpc_build_code_desc checks it), so an item counts whole
  * or not at all: a compare and a select, where the general mask cost seven instructions per item. */
 LDPC_HD uint32_t ldpc_fast_valid_lanes(int valid) { return valid > 0 ? 0x01010101u : 0u; }
-/* The row's sign bytes, accumulated in the forward sweep two edges to an instruction: the compiler keeps a chain of xors as
- * it is written, one v_xor_b32 per edge; a three-input xor costs the same.  Edge k's bytes go in with edge k + 1's (or alone,
- * the last of an odd row): never behind the window of edge k + 2. */
-LDPC_HD uint32_t ldpc_fast_cn_sign_acc(uint32_t sx4, uint32_t s4_prev, uint32_t s4_k, int k, int D)
-{
-  if (k & 1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_bitop3_b32(sx4, s4_prev, s4_k, 0x96);
-#else
-    return sx4 ^ s4_prev ^ s4_k;
-#endif
-  }
-  return k == D - 1 ? sx4 ^ s4_k : sx4;
-}
-/* The four biased output bytes of a check-node edge.  o4 = the magnitudes, 0 .. 127 a byte; sx4 = the row's sign bytes (0xff = an
- * odd number of negative inputs, else 0x00 -- LDPC_SEL_SIGNS) with 0x80 xor-ed into every byte once per row; s4 = the edge's own
- * sign bytes.  x = sx4 ^ s4 is 0x7f (the other edges hold an odd number of negatives) or 0x80 per byte, and the byte wanted is
- * 128 + o = o ^ 0x80 resp. 128 - o = (o ^ 0x7f) + 1, i.e. (o ^ x) + (x & 1): no carry between the bytes (the largest values are
- * 0x80 + 0x7f and 0x7f + 1).  On the device x is never formed: two three-input bit operations (o ^ sx ^ s, truth table 0x96,
- * and (sx ^ s) & 0x01010101, 0x28) at the plain 32-bit rate and an add, where xor + xor + v_xad_u32 paid the three-operand
- * add's slower rate (tools/ubench/valu_rate.hip). */
-LDPC_HD uint32_t ldpc_fast_cn_out_bytes(uint32_t o4, uint32_t sx4, uint32_t s4)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_bitop3_b32(o4, sx4, s4, 0x96) + __builtin_amdgcn_bitop3_b32(sx4, s4, 0x01010101u, 0x28);
-#else
-  const uint32_t x4 = sx4 ^ s4;
-  return (o4 ^ x4) + (x4 & 0x01010101u);
-#endif
-}
 
 /* One check-node item: lifted row with first edge e0, lanes t..t+3 (t = 4j).  D = row degree; EXT = the
  * last edge goes to the row's degree-1 column; KEEP = keep the per-edge magnitudes in registers between
@@ -296,10 +266,12 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
   m1l = ldpc_pminu(m1l, cap); m2l = ldpc_pminu(m2l, cap);
   m1h = ldpc_pminu(m1h, cap); m2h = ldpc_pminu(m2h, cap);
   const uint32_t sl = (ldpc_u2u32(m1l) - 0x80008000u) + ldpc_u2u32(m2l), sh = (ldpc_u2u32(m1h) - 0x80008000u) + ldpc_u2u32(m2h);
-  /* Signs are applied to the four output bytes at once.  Bit 15 of a half of d_k says "negative"; those bits are spread
-   * over a byte each with one v_perm (LDPC_SEL_SIGNS), for the row's xor once and per edge once, and go through
-   * ldpc_fast_cn_out_bytes like the sign bytes of ldpc_fast_cn_ps. */
-  const uint32_t sx4 = ldpc_perm(sxh, sxl, LDPC_SEL_SIGNS) ^ 0x80808080u;
+  /* Signs are applied to the four output bytes at once.  Bit 15 of a half of (sx ^ d_k) says "negative"; the bytes
+   * that hold those bits (1 and 3 of each register) are gathered with one v_perm, for the row's xor once and per edge
+   * once.  With n = 0 / 1 per byte and a magnitude o <= 127, the biased byte is 128 + o = o ^ 0x80 for n = 0 and
+   * 128 - o = (o ^ 0x7f) + 1 for n = 1, i.e. (o ^ (0x80 - n)) + n: three plain 32-bit ops for four lanes, no carry
+   * between the bytes (the largest value is 0x80). */
+  const uint32_t sx4 = ldpc_perm(sxh, sxl, LDPC_SEL_EO);
 #pragma unroll
   for (int k = 0; k < D; k++) {
     uint32_t dl, dh;
@@ -318,7 +290,8 @@ LDPC_HD uint32_t ldpc_fast_cn(const ldpc_fast_lds &L, int e0, int j, int Z, int 
     const ldpc_v2u mh = KEEP ? ldpc_as_v2u(g_hi[k]) : ldpc_sm_key(dh);
     const uint32_t ol = sl - ldpc_u2u32(ldpc_pminu(ml, m2l)), oh = sh - ldpc_u2u32(ldpc_pminu(mh, m2h)); /* magnitudes, 0..127 per half */
     const uint32_t o4 = ldpc_perm(oh, ol, 0x06020400u);
-    const uint32_t w = ldpc_fast_cn_out_bytes(o4, sx4, ldpc_perm(dh, dl, LDPC_SEL_SIGNS));
+    const uint32_t n4 = ((sx4 ^ ldpc_perm(dh, dl, LDPC_SEL_EO)) >> 7) & 0x01010101u;
+    const uint32_t w = (o4 ^ (0x80808080u - n4)) + n4;
     *reinterpret_cast<uint32_t *>(rrow + k * rstride) = w;
     *reinterpret_cast<uint32_t *>(rpad + k * rstride) = w;
   }
@@ -361,7 +334,7 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
     m_lo[k] = ldpc_u2u32(ml);
     m_hi[k] = ldpc_u2u32(mh);
     s4[k] = ldpc_perm(dh, dl, LDPC_SEL_SIGNS); /* bit 15 of the four halves, a byte each */
-    sx4 = ldpc_fast_cn_sign_acc(sx4, k ? s4[k - 1] : 0u, s4[k], k, D);
+    sx4 ^= s4[k];
     if ((k & 1) && k < D - 1) { /* P of pair k / 2: wanted by the pairs (and the single edge) behind it */
       const int i = k / 2;
       p_lo[i] = ldpc_u2u32(ldpc_pmin3_keys(i ? ldpc_as_v2u(p_lo[i - 1]) : cap, ldpc_as_v2u(m_lo[k - 1]), ml));
@@ -369,11 +342,14 @@ LDPC_HD uint32_t ldpc_fast_cn_ps(const ldpc_fast_lds &L, int e0, int j, int Z, i
     }
   }
   /* Signs.  The byte of s4 that stands for a lane is 0xff (d < 0) or 0x00 (LDPC_SEL_SIGNS), so the xor over the OTHER edges
-   * is 0xff = "an odd number of them is negative" or 0x00; 0x80 is xor-ed in once per row (ldpc_fast_cn_out_bytes). */
+   * is 0xff = "an odd number of them is negative" or 0x00; 0x80 is xor-ed in once per row: x = 0x7f (odd) or 0x80.  The
+   * biased output byte 128 + o (x = 0x80) or 128 - o = (o ^ 0x7f) + 1 (x = 0x7f) is (o ^ x) + (x & 1): four plain 32-bit
+   * ops per edge for four lanes, no carry between the bytes (the largest value is 0x80 + 0x7f resp. 0x7f + 1). */
   sx4 ^= 0x80808080u;
   auto put = [&](int k, ldpc_v2u ol, ldpc_v2u oh) {
     const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06020400u); /* low bytes: the magnitudes 0..127 */
-    const uint32_t w = ldpc_fast_cn_out_bytes(o4, sx4, s4[k]);
+    const uint32_t x4 = sx4 ^ s4[k];
+    const uint32_t w = (o4 ^ x4) + (x4 & 0x01010101u);
     *reinterpret_cast<uint32_t *>(rrow + k * rstride) = w;
     *reinterpret_cast<uint32_t *>(rpad + k * rstride) = w;
   };
@@ -438,7 +414,7 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
       m_lo[n][k] = ldpc_u2u32(ml);
       m_hi[n][k] = ldpc_u2u32(mh);
       s4[n][k] = ldpc_perm(dh, dl, LDPC_SEL_SIGNS);
-      sx4[n] = ldpc_fast_cn_sign_acc(sx4[n], k ? s4[n][k - 1] : 0u, s4[n][k], k, D);
+      sx4[n] ^= s4[n][k];
       if ((k & 1) && k < D - 1) {
         const int i = k / 2;
         p_lo[n][i] = ldpc_u2u32(ldpc_pmin3_keys(i ? ldpc_as_v2u(p_lo[n][i - 1]) : cap, ldpc_as_v2u(m_lo[n][k - 1]), ml));
@@ -450,7 +426,8 @@ LDPC_HD uint32_t ldpc_fast_cn_ps2(const ldpc_fast_lds &L, int e0a, int ja, int e
   sx4[1] ^= 0x80808080u;
   auto put = [&](int n, int k, ldpc_v2u ol, ldpc_v2u oh) {
     const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06020400u);
-    const uint32_t w = ldpc_fast_cn_out_bytes(o4, sx4[n], s4[n][k]);
+    const uint32_t x4 = sx4[n] ^ s4[n][k];
+    const uint32_t w = (o4 ^ x4) + (x4 & 0x01010101u);
     *reinterpret_cast<uint32_t *>(rrow[n] + k * rstride) = w;
     *reinterpret_cast<uint32_t *>(rpad[n] + k * rstride) = w;
   };
@@ -541,7 +518,7 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
     }
     m_lo[k] = ldpc_u2u32(ml); m_hi[k] = ldpc_u2u32(mh);
     s4[k] = sg;
-    sx4 = ldpc_fast_cn_sign_acc(sx4, k ? s4[k - 1] : 0u, sg, k, N);
+    sx4 ^= sg;
     if (SYN)
       parw ^= pw;
     if (k & 1) {
@@ -565,7 +542,8 @@ __device__ __forceinline__ uint32_t ldpc_fast_cn19_pair(const ldpc_fast_lds &L, 
       const bool live = k < N - 1 || !half;
       const ldpc_v2u ol = ldpc_pmin3_keys(pvl, ldpc_as_v2u(m_lo[ko]), sl), oh = ldpc_pmin3_keys(pvh, ldpc_as_v2u(m_hi[ko]), sh);
       const uint32_t o4 = ldpc_perm(ldpc_u2u32(oh), ldpc_u2u32(ol), 0x06020400u);
-      const uint32_t w = ldpc_fast_cn_out_bytes(o4, sx4, s4[k]);
+      const uint32_t x4 = sx4 ^ s4[k];
+      const uint32_t w = (o4 ^ x4) + (x4 & 0x01010101u);
       if (live) {
         *reinterpret_cast<uint32_t *>(rrow + k * rstride) = w;
         *reinterpret_cast<uint32_t *>(rpad + k * rstride) = w;
@@ -645,23 +623,9 @@ LDPC_HD uint32_t ldpc_fast_cn_dispatch(int deg, int ext, const ldpc_fast_lds &L,
   }
 }
 
-/* Sums of a bit-node item, four ops per window and not five (both gathers are bound by VALU issue): ae += bytes 0 and 2 (mask,
- * add) = S0 + 2^16 S2, at += the window >> 8 WHOLE (shift, add) = S1 + 2^8 S2 + 2^16 S3, with S_i the sum of byte i over the
- * column's edges and the biased LLR word.  The high half of ae is S2, so the odd lanes' packed sums S1 + 2^16 S3 are
- * at - (S2 << 8), taken once per item (ldpc_fast_bn_finish).  No overflow: a column has at most 31 edges (ldpc_build_code_desc
- * refuses the fast kernels otherwise; NR's largest is 30), so S_i <= (31 + 1) * 255 = 8 160 < 2^13 and
- * at <= 8 160 * (1 + 2^8 + 2^16) < 2^30. */
-LDPC_HD void ldpc_fast_bn_acc(uint32_t w, uint32_t &ae, uint32_t &at)
-{
-  ae += w & 0x00ff00ffu;
-  at += w >> 8;
-}
-LDPC_HD uint32_t ldpc_fast_bn_odd_sums(uint32_t ae, uint32_t at) { return at - ((ae >> 16) << 8); }
-
 /* One bit-node item: core column c, bits u..u+3 (u = 4j): APP = clamp_s8(llr + sum r) (bnProc.h:136-160), in two steps.
- * ldpc_fast_bn_gather: ae / at += the biased message bytes of the column's edges (ldpc_fast_bn_acc): packed 16-bit sums of
- * lanes (0,2), whole-word sums for lanes (1,3).  colrec = f_coltbl entry of the column; maxdeg = wave-uniform loop bound >=
- * the column's degree.
+ * ldpc_fast_bn_gather: acc_e / acc_o += the biased message bytes of the column's edges, as packed 16-bit sums of lanes
+ * (0,2) and (1,3).  colrec = f_coltbl entry of the column; maxdeg = wave-uniform loop bound >= the column's degree.
  * The gather is a chain table entry -> address -> window per edge; four edges are kept in flight.  Table entry =
  * {x = Z - shift, y = LDS address of the message row - (x & 3)}: u and Z are multiples of 4, so the window's byte
  * phase is x & 3 for every item and y + p is the aligned dword that holds its first byte.  Columns with fewer than
@@ -669,8 +633,8 @@ LDPC_HD uint32_t ldpc_fast_bn_odd_sums(uint32_t ae, uint32_t at) { return at - (
 /* first = index of the column's first list entry.  The entries of the NEXT four edges are requested before the current four
  * windows are waited for: one exposed LDS round trip per step instead of two (BG1 Zc = 384: -2..4 % on the whole kernel,
  * profiles/r03/decoder_ab*.txt; gathering all entries and then all windows at once, unrolled per loop bound, was slower). */
-LDPC_HD void ldpc_fast_bn_gather_from(const ldpc_fast_lds &L, int first, int maxdeg, int j, int Z, int boff_r, uint32_t &ae,
-                                      uint32_t &at)
+LDPC_HD void ldpc_fast_bn_gather_from(const ldpc_fast_lds &L, int first, int maxdeg, int j, int Z, int boff_r, uint32_t &acc_e,
+                                      uint32_t &acc_o)
 {
   const int u = 4 * j;
   const uint2 *tbl = reinterpret_cast<const uint2 *>(L.ctbl) + first;
@@ -698,29 +662,35 @@ LDPC_HD void ldpc_fast_bn_gather_from(const ldpc_fast_lds &L, int first, int max
         ce[i] = tbl[k + 4 + i];
     }
 #pragma unroll
-    for (int i = 0; i < 4; i++)
-      ldpc_fast_bn_acc(ldpc_alignbyte(hi[i], lo[i], ph[i]), ae, at);
+    for (int i = 0; i < 4; i++) {
+      const uint32_t w = ldpc_alignbyte(hi[i], lo[i], ph[i]);
+      acc_e += w & 0x00ff00ffu;
+      acc_o += (w >> 8) & 0x00ff00ffu;
+    }
   }
   for (; k < maxdeg; k++) {
     const uint2 c1 = tbl[k];
     const uint32_t q = (uint32_t)u + c1.x;
     const uint32_t p = q < q - (uint32_t)Z ? q : q - (uint32_t)Z;
-    ldpc_fast_bn_acc(ldpc_window_al(L.base, c1.y + p + (uint32_t)boff_r, q), ae, at);
+    const uint32_t v = ldpc_window_al(L.base, c1.y + p + (uint32_t)boff_r, q);
+    acc_e += v & 0x00ff00ffu;
+    acc_o += (v >> 8) & 0x00ff00ffu;
   }
 }
-LDPC_HD void ldpc_fast_bn_gather(const ldpc_fast_lds &L, uint32_t colrec, int maxdeg, int j, int Z, int boff_r, uint32_t &ae,
-                                 uint32_t &at)
+LDPC_HD void ldpc_fast_bn_gather(const ldpc_fast_lds &L, uint32_t colrec, int maxdeg, int j, int Z, int boff_r, uint32_t &acc_e,
+                                 uint32_t &acc_o)
 {
-  ldpc_fast_bn_gather_from(L, (int)(colrec >> 16), maxdeg, j, Z, boff_r, ae, at);
+  ldpc_fast_bn_gather_from(L, (int)(colrec >> 16), maxdeg, j, Z, boff_r, acc_e, acc_o);
 }
-/* ldpc_fast_bn_finish: the sums (ae, at) of ALL `deg` edges of column c (each byte biased by 128) + the channel LLRs (true
- * int8 bytes, added like one more window) -> clamped APP, stored twice; the one finishing step of both gathers */
-LDPC_HD void ldpc_fast_bn_finish(const ldpc_fast_lds &L, int c, int deg, int j, int Z, int astride, uint32_t llr_word, uint32_t ae,
-                                 uint32_t at, int boff_a)
+/* ldpc_fast_bn_finish: the sums of ALL `deg` edges of column c (each byte biased by 128) + the channel LLRs (true int8
+ * bytes) -> clamped APP, stored twice */
+LDPC_HD void ldpc_fast_bn_finish(const ldpc_fast_lds &L, int c, int deg, int j, int Z, int astride, uint32_t llr_word, uint32_t acc_e,
+                                 uint32_t acc_o, int boff_a)
 {
   const int u = 4 * j;
-  ldpc_fast_bn_acc(llr_word ^ 0x80808080u, ae, at);
-  const uint32_t acc_e = ae, acc_o = ldpc_fast_bn_odd_sums(ae, at); /* packed 16-bit sums of lanes (0,2) and (1,3) */
+  const uint32_t lw = llr_word ^ 0x80808080u;
+  acc_e += lw & 0x00ff00ffu;
+  acc_o += (lw >> 8) & 0x00ff00ffu;
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(LDPC_NO_SAT_PK)
   /* biased APP byte = clamp(app, -128, 127) + 128 = clamp(sum - deg * 128, 0, 255): v_sat_pk_u8_i16 clamps both 16-bit
    * halves to 0 .. 255 and packs them into two bytes -- one subtract, one pack per register, one v_perm to interleave */
@@ -744,9 +714,9 @@ LDPC_HD void ldpc_fast_bn_finish(const ldpc_fast_lds &L, int c, int deg, int j, 
 LDPC_HD void ldpc_fast_bn(const ldpc_fast_lds &L, uint32_t colrec, int maxdeg, int j, int Z, int astride,
                           uint32_t llr_word, int boff_r = 0, int boff_a = 0)
 {
-  uint32_t ae = 0, at = 0;
-  ldpc_fast_bn_gather(L, colrec, maxdeg, j, Z, boff_r, ae, at);
-  ldpc_fast_bn_finish(L, (int)(colrec & 0xffu), (int)((colrec >> 8) & 0xffu), j, Z, astride, llr_word, ae, at, boff_a);
+  uint32_t acc_e = 0, acc_o = 0;
+  ldpc_fast_bn_gather(L, colrec, maxdeg, j, Z, boff_r, acc_e, acc_o);
+  ldpc_fast_bn_finish(L, (int)(colrec & 0xffu), (int)((colrec >> 8) & 0xffu), j, Z, astride, llr_word, acc_e, acc_o, boff_a);
 }
 
 /* G bit-node items of one thread, all of short columns (ldpc_graph.h f_bn_ticket), walked edge by edge TOGETHER: G table
@@ -756,7 +726,10 @@ template <int G>
 LDPC_HD void ldpc_fast_bn_multi(const ldpc_fast_lds &L, const uint32_t (&rec)[G], const int (&jj)[G], const uint32_t (&lw)[G],
                                 const bool (&live)[G], int md, int Z, int astride)
 {
-  uint32_t ae[G], at[G]; /* ldpc_fast_bn_acc */
+  /* sums: ae = bytes 0 and 2 of the windows (mask, add), at = the windows >> 8 whole (shift, add) = S1 + 2^8 S2 + 2^16 S3 with
+   * S_i the sum of byte i over the edges (< 2^13: no overflow); the high half of ae is S2, so the odd lanes' packed sums
+   * S1 + 2^16 S3 = at - (S2 << 8), once per item: four ops per edge instead of five (this path is bound by VALU issue) */
+  uint32_t ae[G], at[G];
   const uint2 *tbl[G];
 #pragma unroll
   for (int g = 0; g < G; g++) {
@@ -779,13 +752,17 @@ LDPC_HD void ldpc_fast_bn_multi(const ldpc_fast_lds &L, const uint32_t (&rec)[G]
       ph[g] = q;
     }
 #pragma unroll
-    for (int g = 0; g < G; g++)
-      ldpc_fast_bn_acc(ldpc_alignbyte(hi[g], lo[g], ph[g]), ae[g], at[g]);
+    for (int g = 0; g < G; g++) {
+      const uint32_t w = ldpc_alignbyte(hi[g], lo[g], ph[g]);
+      ae[g] += w & 0x00ff00ffu;
+      at[g] += w >> 8;
+    }
   }
 #pragma unroll
   for (int g = 0; g < G; g++)
     if (live[g])
-      ldpc_fast_bn_finish(L, (int)(rec[g] & 0xffu), (int)((rec[g] >> 8) & 0xffu), jj[g], Z, astride, lw[g], ae[g], at[g], 0);
+      ldpc_fast_bn_finish(L, (int)(rec[g] & 0xffu), (int)((rec[g] >> 8) & 0xffu), jj[g], Z, astride, lw[g], ae[g],
+                          at[g] - ((ae[g] >> 16) << 8), 0);
 }
 
 /* hard decision of code bit `b` (< ncore*Z) from the biased APP store */
