@@ -509,8 +509,8 @@ int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, ui
  *   channel_level_grid_mmse: log2_maxh[tb] = max(0, (log2_approx(avgs) >> 1) - 3) (:1639-1647), avgs = max(0, the 2 n_rx pairs'
  *     averages) of the measurement symbol scaled by nr_ulsch_scale_channel with shift_ch_ext = log2_approx(max_ch[tb] >> 11)
  *     (:1614, the general branch :392-402).
- * max_ch and nvar come out of the reference's channel estimator (nr_ul_channel_estimation.c:187, :468-469); the estimator
- * here does not produce them, so they are inputs, one value per tb like shift, read from device memory in DEVICE mode.
+ * max_ch and nvar come out of the reference's channel estimator (nr_ul_channel_estimation.c:187, :468-469): inputs here, one
+ * value per tb like shift, read from device memory in DEVICE mode, where pusch_channel_estimation_meas writes them.
  * mem modes, staging and refusals are those of the _grid calls; further refusals: Qm other than 6 or 8 (two layers of QPSK /
  * 16QAM take the ML receiver, which writes LLRs: the _ml calls below), n_rx other than 2 or 4, 2 (sym_off + nb_re) > plane, a NULL
  * nvar / max_ch or (DEVICE) one that is not device memory of that GPU, two segments whose doubled output ranges overlap.
@@ -580,7 +580,7 @@ int32_t nrLDPC_hip_ulsch_level_ml_host(const int16_t *chFext, uint32_t n_rx, uin
  * bwp_start_subcarrier) and exactly 12 rb_size c16 are written at ch_off + a ch_ant_stride, overwritten: the reference's memset
  * of the whole symbol and its TYPE1_INTERP spill of four entries behind the allocation are not reproduced.  est_delay holds
  * one int32 per (descriptor, antenna) at delay_off + a, the value nr_est_delay would have found (the search itself, a
- * fixed-point IDFT, is not built); NULL means 0 everywhere.  max_ch and nvar are not produced.  Deviations from the
+ * fixed-point IDFT, is not built); NULL means 0 everywhere.  max_ch and nvar: pusch_channel_estimation_meas below.  Deviations from the
  * reference: TYPE2_AVG reads every RE relative to the descriptor's symbol and PRB b uses pilots 4b .. 4b + 3.
  * mem = HOST stages one contiguous span of the grid, from the lowest to the highest c16 any (descriptor, antenna) pair reads,
  * works on a bounce of the span of estimates from the lowest to the highest c16 written, and copies only the write set back to
@@ -626,6 +626,65 @@ int32_t nrLDPC_hip_pusch_dmrs_host(uint32_t c_init, uint32_t dmrs_offset, uint32
 int32_t nrLDPC_hip_delay_table_host(uint32_t fft_size, int32_t delay, int16_t *out);
 int32_t nrLDPC_hip_pusch_chest_segments(const nrLDPC_hip_pusch_alloc_t *alloc, const nrLDPC_hip_pusch_chest_cfg_t *cfg, uint32_t n_alloc, uint32_t n_rx,
                                         nrLDPC_hip_chest_seg_t *seg_out, uint32_t cap, uint32_t *n_seg_out);
+/* The estimator's measurements and the time average of its estimates: what nr_rx_pusch_tp has when the estimation loop ends
+ * (nr_ulsch_demodulation.c:1470-1535), so that a rank-2 slot needs no host value between rxdataF and the payload.
+ * pusch_channel_estimation_meas: ul_ch is written exactly as pusch_channel_estimation writes it, same write set, same bits, and
+ * in the same call max_ch[tb] and nvar[tb] (tb < n_tb) receive what the reference passes on to its two-layer receivers, in the
+ * int32 / uint32 arrays channel_level_grid_mmse / _ml and mmse_2layers_grid read.  Descriptor i belongs to block seg_tb[i] (host
+ * memory, like the descriptors); a block's descriptors -- all its DMRS symbols, both layers' ports -- need not be adjacent.
+ *   One descriptor is one call of nr_pusch_channel_estimation (one DMRS symbol, one port, all n_rx antennas) with noise_amp2, a
+ *   uint64, and nest_count starting at 0 (nr_ul_channel_estimation.c:148-149):
+ *     TYPE1_INTERP  max over the 3 rb_size LS pairs of |r|, |i| of the int32 value BEFORE the int16 cast (:186-187: a full-scale
+ *       grid gives more than 32767 where the estimate wraps); every RE k < 12 rb_size adds c16amp2(c16sub(ul_ls_est[k], ul_ch[k]))
+ *       (:246-247), ul_ls_est[k] the cast LS value of pair k >> 2, ul_ch[k] the estimate the call stores, the difference wrapping
+ *       to int16, its square sum a uint32; nest_count = 12 rb_size n_rx.
+ *     TYPE2_INTERP  per pair n < 2 rb_size: max over ch = (ch0 + ch1) >> 1 (:268-269), noise_amp2 += c16amp2(c16sub(ch0, ch))
+ *       (:273); nest_count = 2 rb_size n_rx.
+ *     TYPE1_AVG / TYPE2_AVG  max over the averages of PRBs 1 .. rb_size - 2: the first and the last PRB are not looked at, as
+ *       written (:295, :330 against :309-311), so rb_size <= 2 contributes nothing; nest_count = 0.  TYPE2_AVG takes the values
+ *       this estimator forms (its two deviations above).
+ *     nvar_tmp = (uint32_t)(noise_amp2 / nest_count), 0 when nest_count = 0 (:468-469, nr_ulsch_demodulation.c:1481).
+ *   max_ch[tb] = the maximum over the block's descriptors and antennas, from 0 (:1470, :1489); nvar[tb] = (sum of the block's
+ *   nvar_tmp, a uint32 sum) / nvar_div[tb] (:1491, :1524), where the caller passes nvar_div[tb] = nr_of_symbols nrOfLayers n_rx
+ *   (host memory) -- all symbols of the allocation, not its DMRS symbols, as written.  A block without a descriptor gets 0 and 0.
+ *   Integer maximum and sum do not depend on the order, so the values are bit for bit the reference's.
+ * mem, staging and refusals are pusch_channel_estimation's; refused besides, before anything is enqueued or written: a NULL
+ * seg_tb / nvar_div / max_ch / nvar, seg_tb[i] >= n_tb, nvar_div[tb] = 0, (DEVICE) max_ch / nvar that are not 4-byte aligned device
+ * memory of that GPU.  A capturing stream is refused.
+ * pusch_chest_meas_host: one descriptor over n_rx antennas on the CPU from csrc/nr_chest.h, no GPU (rx_off and delay_off apply,
+ * est_delay may be NULL; nothing is stored but the three results): *max_ch from 0, *noise_amp2, *nest_count.
+ * pusch_chest_time_avg: nr_chest_time_domain_avg (openair1/PHY/NR_REFSIG/dmrs_nr.c:343-417).  For plane q < n_plane of descriptor
+ * i the 12 rb_size c16 at ch_off[0] + q ch_ant_stride are overwritten with the average of those at ch_off[0 .. n_sym - 1] + q
+ * ch_ant_stride: the later symbols are added to the first with adds_epi16 -- saturating per int16 component, one symbol after
+ * the other in the order given -- then >> 1 (two symbols), >> 2 (four), C's / 3 (three: towards zero, not a shift).  n_sym = 1
+ * reads and writes nothing; the other symbols' estimates stay as they are.  The reference loops over nb_antennas_rx planes of
+ * ch_estimates, which with two layers are layer 0's alone: n_plane = n_rx reproduces that, n_plane = 2 n_rx averages both layers.
+ * Afterwards the grid calls read the first DMRS symbol: the caller puts first_dmrs_out into the allocation's dmrs_symbol
+ * (:1535-1536 of nr_ulsch_demodulation.c).  mem as above (HOST stages the span from the lowest to the highest c16 the descriptors
+ * reach and copies only the write set back).  Refused: NULL arrays, n_plane outside 1..16, n_sym outside 1..4 (the reference
+ * asserts beyond four), rb_size = 0, write ranges of two (descriptor, plane) pairs that overlap, a later symbol's range that
+ * overlaps a written range, another mem value, a misaligned or foreign device pointer, a capturing stream.
+ * pusch_chest_time_avg_host: one descriptor, one plane, on the CPU from the same header, no GPU.
+ * pusch_chest_avg_segments (host only): one descriptor per allocation with ch_off[k] = the allocation's ch_off + (its k-th DMRS
+ * symbol) fft_size and first_dmrs_out[i] = its first DMRS symbol.  It counts the DMRS symbols inside the allocation where the
+ * reference counts the bitmap's bits from symbol 0 (get_dmrs_symbols_in_slot); a valid PDU has no DMRS bit outside its symbols, so
+ * the two are equal.  Refused: what pusch_chest_segments refuses of the allocation's symbols and width, no DMRS symbol, more than
+ * four, more descriptors than cap. */
+typedef struct nrLDPC_hip_chest_avg_seg {
+  uint64_t ch_off[4]; /* c16 offset of plane 0's estimate of PUSCH subcarrier 0 in the k-th DMRS symbol; [0] is overwritten */
+  uint32_t n_sym;     /* DMRS symbols, 1..4 */
+  uint32_t rb_size;
+} nrLDPC_hip_chest_avg_seg_t;
+int32_t nrLDPC_hip_pusch_channel_estimation_meas(const int16_t *rxdataF, uint64_t rx_ant_stride, int16_t *ul_ch, uint64_t ch_ant_stride, uint32_t n_rx,
+                                                 const nrLDPC_hip_chest_seg_t *seg, uint32_t n_seg, const int32_t *est_delay, const uint32_t *seg_tb,
+                                                 const uint32_t *nvar_div, uint32_t n_tb, int32_t *max_ch, uint32_t *nvar, int32_t mem, void *stream);
+int32_t nrLDPC_hip_pusch_chest_meas_host(const int16_t *rxdataF, uint64_t rx_ant_stride, uint32_t n_rx, const nrLDPC_hip_chest_seg_t *seg,
+                                         const int32_t *est_delay, int32_t *max_ch, uint64_t *noise_amp2, uint32_t *nest_count);
+int32_t nrLDPC_hip_pusch_chest_time_avg(int16_t *ul_ch, uint64_t ch_ant_stride, uint32_t n_plane, const nrLDPC_hip_chest_avg_seg_t *seg, uint32_t n_seg,
+                                        int32_t mem, void *stream);
+int32_t nrLDPC_hip_pusch_chest_time_avg_host(int16_t *ul_ch, const nrLDPC_hip_chest_avg_seg_t *seg);
+int32_t nrLDPC_hip_pusch_chest_avg_segments(const nrLDPC_hip_pusch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_chest_avg_seg_t *out, uint32_t cap,
+                                            uint32_t *n_out, uint8_t *first_dmrs_out);
 /* ---------------------------------------------------------------------------------------------------
  * PDSCH resource mapping with DMRS onto the transmit grid: the resource mapping loop of nr_generate_pdsch (openair1/PHY/
  * NR_TRANSPORT/nr_dlsch.c:205-474) and its unit-precoding copy (:483-535) for one list of descriptors, one per (allocation, OFDM

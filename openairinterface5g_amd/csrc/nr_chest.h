@@ -248,4 +248,119 @@ NR_CHE_HD uint32_t nr_che_avg(uint32_t mode, const uint32_t *rx, uint32_t N, uin
   s.i = nr_che_cast16(s.i / (int32_t)np);
   return nr_che_pack(s);
 }
+
+/*
+ * The measurements of a call, max_ch and nvar (:187, :246-247, :269, :273, :311, :405, :468-469), one output unit at a time next
+ * to the unit's estimates.  A call's results are max_ch, an int32 maximum, and noise_amp2, a uint64 sum, over all antennas; both
+ * are order-free, so each unit hands back its own share:
+ *   TYPE1_INTERP  group g holds REs 4g .. 4g + 3, whose ul_ls_est is the cast LS value of pair g (:188-190).  Its share: the
+ *     maximum over |r|, |i| of pair g's int32 LS value BEFORE the cast (:186-187), and c16amp2(c16sub(ls16, ul_ch[k])) of its four
+ *     REs (:246-247) against the estimates the unit stores; c16sub wraps to int16, c16amp2 is a uint32.  nest_count: 12 rb_size
+ *     per antenna (:255).
+ *   TYPE2_INTERP  pair m (6-RE block m) belongs to the group that holds RE 6m, g = 6m / 4, and to no other: its share is the
+ *     maximum over ch (:269) and c16amp2(c16sub(ch0, ch)) (:273).  nest_count: 2 rb_size per antenna (:274).
+ *   TYPE1_AVG / TYPE2_AVG  PRB b counts for the maximum when 1 <= b <= rb_size - 2 (:309-311, :386-405: the first and the last
+ *     PRB's code has no max_ch line); no noise term, nest_count 0.
+ * |x| is taken in int32: an int16 -32768 gives 32768.
+ */
+NR_CHE_HD int32_t nr_che_abs_max(int32_t m, nr_che_c c)
+{
+  const int32_t r = c.r < 0 ? -c.r : c.r, i = c.i < 0 ? -c.i : c.i;
+  const int32_t v = r > i ? r : i;
+  return m > v ? m : v;
+}
+/* c16amp2(c16sub(a, b)) (tools_defs.h:182-191) */
+NR_CHE_HD uint32_t nr_che_sub_amp2(nr_che_c a, nr_che_c b)
+{
+  const int32_t r = nr_che_cast16(a.r - b.r), i = nr_che_cast16(a.i - b.i);
+  return (uint32_t)(r * r) + (uint32_t)(i * i);
+}
+/* calls per antenna of nest_count's increments */
+NR_CHE_HD uint32_t nr_che_nest_per_antenna(uint32_t mode, uint32_t rb_size)
+{
+  return mode == NR_CHE_TYPE1_INTERP ? 12u * rb_size : (mode == NR_CHE_TYPE2_INTERP ? 2u * rb_size : 0u);
+}
+/* TYPE1_INTERP: the int32 LS value of pair n before the cast (:178-185); bits from pilot plo on */
+NR_CHE_HD nr_che_c nr_che_t1_ls32(const uint32_t *rx, uint32_t N, uint32_t k0, uint32_t port, uint32_t dmrs_offset, uint64_t bits, uint32_t plo, uint32_t n)
+{
+  const uint32_t delta = nr_che_delta1(port);
+  nr_che_c ls = {0, 0};
+  for (uint32_t kl = 0; kl < 2u; kl++) {
+    const nr_che_c x = nr_che_unpack(rx[nr_che_wrap(k0, 4u * n + 2u * kl + delta, N)]);
+    const nr_che_c t = nr_che_mul_shift(nr_che_unit_pilot(bits, plo, 2u * n + kl, dmrs_offset, port), x, 16);
+    ls.r += t.r;
+    ls.i += t.i;
+  }
+  return ls;
+}
+/* TYPE1_INTERP, group g with its stored estimates out[4]: max_ch = max(max_ch, ...), the group's four noise terms */
+NR_CHE_HD uint64_t nr_che_t1_meas(const uint32_t *rx, uint32_t N, uint32_t k0, uint32_t port, uint32_t dmrs_offset, uint64_t bits, uint32_t g,
+                                  const uint32_t *out, int32_t *max_ch)
+{
+  nr_che_c ls = nr_che_t1_ls32(rx, N, k0, port, dmrs_offset, bits, nr_che_unit_first_pilot(NR_CHE_TYPE1_INTERP, g), g);
+  *max_ch = nr_che_abs_max(*max_ch, ls);
+  ls.r = nr_che_cast16(ls.r);
+  ls.i = nr_che_cast16(ls.i);
+  uint64_t noise = 0;
+  for (uint32_t j = 0; j < 4u; j++)
+    noise += nr_che_sub_amp2(ls, nr_che_unpack(out[j]));
+  return noise;
+}
+/* TYPE2_INTERP: ch0 of 6-RE block m (:264) */
+NR_CHE_HD nr_che_c nr_che_t2_ch0(const uint32_t *rx, uint32_t N, uint32_t k0, uint32_t port, uint32_t dmrs_offset, uint64_t bits, uint32_t plo, uint32_t m)
+{
+  return nr_che_mul_shift16(nr_che_unit_pilot(bits, plo, 2u * m, dmrs_offset, port), nr_che_unpack(rx[nr_che_wrap(k0, 6u * m, N) + nr_che_nushift(port)]),
+                            15);
+}
+/* TYPE2_INTERP, group g: the share of the pair it owns, if it owns one (blocks < n_blocks = 2 rb_size) */
+NR_CHE_HD uint64_t nr_che_t2_meas(const uint32_t *rx, uint32_t N, uint32_t k0, uint32_t port, uint32_t dmrs_offset, uint64_t bits, uint32_t g,
+                                  int32_t *max_ch)
+{
+  const uint32_t m0 = (4u * g) / 6u, m = (4u * g + 3u) / 6u, plo = 2u * m0;
+  if ((6u * m) / 4u != g) /* RE 6m lies in another group (m0 < m: in the one before) */
+    return 0;
+  const nr_che_c ch = nr_che_t2_block(rx, N, k0, port, dmrs_offset, bits, plo, m);
+  *max_ch = nr_che_abs_max(*max_ch, ch);
+  return nr_che_sub_amp2(nr_che_t2_ch0(rx, N, k0, port, dmrs_offset, bits, plo, m), ch);
+}
+/* TYPE1_AVG / TYPE2_AVG, PRB b with its value v */
+NR_CHE_HD int32_t nr_che_avg_meas(uint32_t rb_size, uint32_t b, uint32_t v, int32_t max_ch)
+{
+  return (b >= 1u && b + 2u <= rb_size) ? nr_che_abs_max(max_ch, nr_che_unpack(v)) : max_ch;
+}
+/* the call's nvar_tmp (:468-469; the caller's variable starts at 0, nr_ulsch_demodulation.c:1481) */
+NR_CHE_HD uint32_t nr_che_nvar_tmp(uint64_t noise_amp2, uint32_t nest_count) { return nest_count ? (uint32_t)(noise_amp2 / nest_count) : 0u; }
+
+/*
+ * nr_chest_time_domain_avg (openair1/PHY/NR_REFSIG/dmrs_nr.c:343-417), one c16: w[0 .. n - 1] = the entry in the n DMRS symbols
+ * in symbol order.  The later symbols are added to the first with adds_epi16, saturating per component and one after the other
+ * (:358-370); then >> 1 for two symbols (:372-378), >> 2 for four (:379-385), C's / 3 for three (:386-414: towards zero).
+ */
+NR_CHE_HD int32_t nr_che_tavg16(int32_t acc, uint32_t n)
+{
+  return n == 2u ? acc >> 1 : (n == 4u ? acc >> 2 : (n == 3u ? acc / 3 : acc));
+}
+/* one later symbol's entry added to the running sum; the sum divided */
+NR_CHE_HD uint32_t nr_che_tavg_add(uint32_t acc, uint32_t x)
+{
+  nr_che_c a = nr_che_unpack(acc);
+  const nr_che_c b = nr_che_unpack(x);
+  a.r = nr_che_sat16(a.r + b.r);
+  a.i = nr_che_sat16(a.i + b.i);
+  return nr_che_pack(a);
+}
+NR_CHE_HD uint32_t nr_che_tavg_div(uint32_t acc, uint32_t n)
+{
+  nr_che_c a = nr_che_unpack(acc);
+  a.r = nr_che_tavg16(a.r, n);
+  a.i = nr_che_tavg16(a.i, n);
+  return nr_che_pack(a);
+}
+NR_CHE_HD uint32_t nr_che_tavg(const uint32_t *w, uint32_t n)
+{
+  uint32_t acc = w[0];
+  for (uint32_t s = 1; s < n; s++)
+    acc = nr_che_tavg_add(acc, w[s]);
+  return nr_che_tavg_div(acc, n);
+}
 #endif

@@ -1629,6 +1629,128 @@ def pusch_channel_estimation(rx, rx_ant_stride, ch, ch_ant_stride, n_rx, segs, e
 
 
 # ---------------------------------------------------------------------------------------------------------
+# The estimator's max_ch / nvar and the time average of its estimates (include/nrLDPC_hip.h: pusch_channel_estimation_meas,
+# pusch_chest_time_avg and their host forms; csrc/nr_chest.h)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_pusch_channel_estimation_meas", "nrLDPC_hip_pusch_chest_meas_host", "nrLDPC_hip_pusch_chest_time_avg",
+            "nrLDPC_hip_pusch_chest_time_avg_host", "nrLDPC_hip_pusch_chest_avg_segments"]
+
+
+class nrLDPC_hip_chest_avg_seg_t(C.Structure):
+    _fields_ = [("ch_off", C.c_uint64 * 4), ("n_sym", C.c_uint32), ("rb_size", C.c_uint32)]
+
+
+def _chest_meas_lib():
+    L = _chest_lib()
+    P, A = C.POINTER(nrLDPC_hip_chest_seg_t), C.POINTER(nrLDPC_hip_chest_avg_seg_t)
+    U = C.POINTER(C.c_uint32)
+    L.nrLDPC_hip_pusch_channel_estimation_meas.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, P, C.c_uint32, C.c_void_p, U, U,
+                                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_pusch_channel_estimation_meas.restype = C.c_int32
+    L.nrLDPC_hip_pusch_chest_meas_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), U]
+    L.nrLDPC_hip_pusch_chest_meas_host.restype = C.c_int32
+    L.nrLDPC_hip_pusch_chest_time_avg.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, A, C.c_uint32, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_pusch_chest_time_avg.restype = C.c_int32
+    L.nrLDPC_hip_pusch_chest_time_avg_host.argtypes = [C.c_void_p, A]
+    L.nrLDPC_hip_pusch_chest_time_avg_host.restype = C.c_int32
+    L.nrLDPC_hip_pusch_chest_avg_segments.argtypes = [C.POINTER(nrLDPC_hip_pusch_alloc_t), C.c_uint32, A, C.c_uint32, U, C.POINTER(C.c_uint8)]
+    L.nrLDPC_hip_pusch_chest_avg_segments.restype = C.c_int32
+    return L
+
+
+def _chest_avg_seg_array(segs):
+    """dicts with ch_off (a sequence of up to four c16 offsets), n_sym, rb_size -> an array of nrLDPC_hip_chest_avg_seg_t"""
+    arr = (nrLDPC_hip_chest_avg_seg_t * max(len(segs), 1))()
+    for i, d in enumerate(segs):
+        for k, v in enumerate(list(d["ch_off"])[:4]):
+            arr[i].ch_off[k] = v
+        arr[i].n_sym, arr[i].rb_size = d["n_sym"], d["rb_size"]
+    return arr
+
+
+def _chest_avg_check_extent(segs, n_plane, ch_stride, ch_len):
+    for s in segs:
+        if not 1 <= s["n_sym"] <= 4 or s["rb_size"] == 0 or len(s["ch_off"]) < s["n_sym"]:
+            continue                                                   # the library names what is wrong with those
+        if max(s["ch_off"][:s["n_sym"]]) + (n_plane - 1) * ch_stride + 12 * s["rb_size"] > ch_len:
+            raise ValueError("a descriptor's channel estimates leave the array")
+
+
+def _u32_array(values):
+    return (C.c_uint32 * max(len(values), 1))(*[int(v) for v in values])
+
+
+def pusch_channel_estimation_meas(rx, rx_ant_stride, ch, ch_ant_stride, n_rx, segs, seg_tb, nvar_div, est_delay=None, max_ch=None, nvar=None,
+                                  stream=None):
+    """nrLDPC_hip_pusch_channel_estimation_meas: pusch_channel_estimation that also forms max_ch / nvar per block.  seg_tb = the block
+    of each descriptor, nvar_div = nr_of_symbols * nrOfLayers * n_rx per block (both host sequences).  numpy int16 arrays -> host
+    call, returns (ch, max_ch int32[n_tb], nvar uint32[n_tb]); torch int16 CUDA tensors -> device call enqueued on `stream` into
+    `max_ch` / `nvar` (torch int32 CUDA, >= n_tb elements; nvar holds the uint32), returns (ch, max_ch, nvar)."""
+    n_tb = len(nvar_div)
+    assert len(seg_tb) == len(segs)
+    host = isinstance(rx, np.ndarray)
+    if host:
+        if est_delay is not None:
+            est_delay = np.ascontiguousarray(est_delay, np.int32)
+        max_ch, nvar_i = np.zeros(max(n_tb, 1), np.int32), np.zeros(max(n_tb, 1), np.int32)
+    else:
+        assert max_ch is not None and nvar is not None and max_ch.numel() >= n_tb and nvar.numel() >= n_tb
+        nvar_i = nvar
+    ptr, numel, mem, s = _mem_of((rx, ch), stream, (est_delay, max_ch, nvar_i))
+    _chest_check_extent(segs, n_rx, rx_ant_stride, ch_ant_stride, numel(rx) // 2, numel(ch) // 2, None if est_delay is None else numel(est_delay))
+    _check(_chest_meas_lib().nrLDPC_hip_pusch_channel_estimation_meas(ptr(rx), rx_ant_stride, ptr(ch), ch_ant_stride, n_rx, _chest_seg_array(segs),
+                                                                      len(segs), ptr(est_delay), _u32_array(seg_tb), _u32_array(nvar_div), n_tb,
+                                                                      ptr(max_ch), ptr(nvar_i), mem, s), "nrLDPC_hip_pusch_channel_estimation_meas")
+    return (ch, max_ch[:n_tb], nvar_i[:n_tb].view(np.uint32)) if host else (ch, max_ch, nvar)
+
+
+def pusch_chest_meas_host(rx, rx_ant_stride, n_rx, seg, est_delay=None):
+    """nrLDPC_hip_pusch_chest_meas_host: one descriptor over n_rx antennas on the CPU (csrc/nr_chest.h, no GPU).  rx = int16 grid,
+    est_delay = int32 array indexed from seg's delay_off, or None.  Returns (max_ch, noise_amp2, nest_count) as Python ints."""
+    assert rx.dtype == np.int16 and rx.flags.c_contiguous
+    if est_delay is not None:
+        est_delay = np.ascontiguousarray(est_delay, np.int32)
+    _chest_check_extent([dict(seg, ch_off=0)], n_rx, rx_ant_stride, 0, rx.size // 2, 1 << 62, None if est_delay is None else est_delay.size)
+    mx, noise, nest = C.c_int32(0), C.c_uint64(0), C.c_uint32(0)
+    _check(_chest_meas_lib().nrLDPC_hip_pusch_chest_meas_host(rx.ctypes.data, rx_ant_stride, n_rx, _chest_seg_array([seg]),
+                                                              None if est_delay is None else est_delay.ctypes.data, C.byref(mx), C.byref(noise),
+                                                              C.byref(nest)), "nrLDPC_hip_pusch_chest_meas_host")
+    return mx.value, noise.value, nest.value
+
+
+def pusch_chest_time_avg(ch, ch_ant_stride, n_plane, segs, stream=None):
+    """nrLDPC_hip_pusch_chest_time_avg: ch = the full-width channel estimates, averaged in place over each descriptor's DMRS symbols
+    into its first (segs: dicts with ch_off, n_sym, rb_size; pusch_chest_avg_segments derives them).  numpy int16 -> host call;
+    torch int16 CUDA -> device call enqueued on `stream`.  Returns ch."""
+    ptr, numel, mem, s = _mem_of((ch,), stream)
+    _chest_avg_check_extent(segs, n_plane, ch_ant_stride, numel(ch) // 2)
+    _check(_chest_meas_lib().nrLDPC_hip_pusch_chest_time_avg(ptr(ch), ch_ant_stride, n_plane, _chest_avg_seg_array(segs), len(segs), mem, s),
+           "nrLDPC_hip_pusch_chest_time_avg")
+    return ch
+
+
+def pusch_chest_time_avg_host(ch, seg):
+    """nrLDPC_hip_pusch_chest_time_avg_host: one descriptor, one plane, on the CPU (no GPU), in place.  Returns ch."""
+    assert ch.dtype == np.int16 and ch.flags.c_contiguous
+    _chest_avg_check_extent([seg], 1, 0, ch.size // 2)
+    _check(_chest_meas_lib().nrLDPC_hip_pusch_chest_time_avg_host(ch.ctypes.data, _chest_avg_seg_array([seg])), "nrLDPC_hip_pusch_chest_time_avg_host")
+    return ch
+
+
+def pusch_chest_avg_segments(allocs, cap=None):
+    """nrLDPC_hip_pusch_chest_avg_segments: allocs = dicts with the fields of nrLDPC_hip_pusch_alloc_t.  Returns (segs, first_dmrs):
+    one dict with ch_off, n_sym, rb_size and the first DMRS symbol per allocation."""
+    n = len(allocs)
+    arr = _struct_array(nrLDPC_hip_pusch_alloc_t, allocs, _RXG_ALLOC_KEYS)
+    cap = n if cap is None else cap
+    out, n_out, first = (nrLDPC_hip_chest_avg_seg_t * max(cap, 1))(), C.c_uint32(0), (C.c_uint8 * max(n, 1))()
+    _check(_chest_meas_lib().nrLDPC_hip_pusch_chest_avg_segments(arr, n, out, cap, C.byref(n_out), first), "nrLDPC_hip_pusch_chest_avg_segments")
+    segs = [dict(ch_off=[int(out[i].ch_off[k]) for k in range(out[i].n_sym)], n_sym=int(out[i].n_sym), rb_size=int(out[i].rb_size))
+            for i in range(n_out.value)]
+    return segs, [int(first[i]) for i in range(n_out.value)]
+
+
+# ---------------------------------------------------------------------------------------------------------
 # PDSCH resource mapping with DMRS (include/nrLDPC_hip.h: pdsch_resource_mapping and its host forms; csrc/nr_pdsch_map.h)
 # ---------------------------------------------------------------------------------------------------------
 EXPORTS += ["nrLDPC_hip_pdsch_resource_mapping", "nrLDPC_hip_pdsch_map_host", "nrLDPC_hip_pdsch_dmrs_host", "nrLDPC_hip_pdsch_map_segments"]

@@ -19,6 +19,20 @@ and the kernel -- not the host's enqueueing.  The legs alternate inside one loop
 
 Before timing, the chain runs once and the payloads and ACKs are checked, and the device's estimates of one block are compared
 with the host form's.
+
+  python tools/slot_rx_chest.py [reps] meas -> one JSON line: what max_ch / nvar and the time average cost
+
+One rank-2 block over the carrier (273 PRB, N = 4096, n_rx = 4, ports 0 and 1), one and two DMRS symbols, each estimator mode:
+per configuration the legs, alternating inside one loop, each one call behind a filler (a matrix product) and between two events,
+
+  estimation                 nrLDPC_hip_pusch_channel_estimation on the 2 x DMRS-symbols descriptors
+  estimation_meas            nrLDPC_hip_pusch_channel_estimation_meas on the same descriptors (its estimates and results are
+                             checked against the first call's and the host form's before timing)
+  level                      nrLDPC_hip_ulsch_channel_level_grid_mmse on the block: what one more small launch with a table
+                             upload costs, the yardstick for the difference of the first two
+  time_avg                   nrLDPC_hip_pusch_chest_time_avg over the 2 n_rx planes (two DMRS symbols only)
+
+A library without the two new calls (NRLDPC_HIP_LIB naming an older build) is timed on the legs it has.
 """
 import json
 import sys
@@ -36,6 +50,104 @@ chest_freq = 1 if len(sys.argv) > 2 and sys.argv[2] == "avg" else 0
 m = pkg.ldpc
 pkg.LDPCinit()
 LG, LC = m._rxg_lib(), m._chest_lib()
+
+
+def measure_meas():
+    """the `meas` mode (module docstring)"""
+    n_rx, rb, N = 4, 273, 4096
+    L = pkg.load_library()
+    has_meas = hasattr(L, "nrLDPC_hip_pusch_channel_estimation_meas")
+    LM, LX = (m._chest_meas_lib() if has_meas else None), m._rxm_lib()
+    rng = np.random.default_rng(3)
+    stride = 14 * N
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        rx = torch.from_numpy(rng.integers(-2000, 2001, (n_rx * stride * 2,)).astype(np.int16)).cuda()
+        ch = torch.zeros(2 * n_rx * stride * 2, dtype=torch.int16, device="cuda")
+        ch2 = torch.zeros_like(ch)
+        mx, nv, lv = (torch.zeros(1, dtype=torch.int32, device="cuda") for _ in range(3))
+        fill_a = torch.randn(6144, 6144, dtype=torch.float16, device="cuda")
+        fill_c = torch.empty_like(fill_a)
+    torch.cuda.synchronize()
+    s_ptr = side.cuda_stream
+    res = {"reps": reps, "n_rx": n_rx, "rb": rb, "fft_size": N, "layers": 2, "library_has_meas": has_meas, "configs": {}}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for mode in range(4):
+        for n_dmrs in (1, 2):
+            pos = (1 << 2) | ((1 << 11) if n_dmrs == 2 else 0)
+            alloc = dict(tb=0, Qm=6, dmrs_config_type=mode & 1, num_dmrs_cdm_grps_no_data=1, dmrs_symbol=2, fft_size=N, first_carrier_offset=N - 6 * rb,
+                         bwp_start=0, rb_start=0, rb_size=rb, start_symbol=0, nr_of_symbols=14, ul_dmrs_symb_pos=pos, plane=2 * 14 * 12 * rb, rx_slot_off=0,
+                         ch_off=0, rec_off=0)
+            cfg = dict(slot=3, scid=0, dmrs_scrambling_id=77, port=0, chest_freq=mode >> 1)
+            csegs = []
+            for layer, port in enumerate((0, 1)):
+                mine = m.pusch_chest_segments([alloc], [dict(cfg, port=port)], n_rx)
+                csegs += [dict(c, ch_off=c["ch_off"] + layer * n_rx * stride, delay_off=0) for c in mine]
+            first = m.pusch_grid_segments([alloc])[1]
+            seg_arr, first_arr = m._chest_seg_array(csegs), m._rx_grid_seg_array(first)
+            tb_arr, div_arr = m._u32_array([0] * len(csegs)), m._u32_array([14 * 2 * n_rx])
+
+            def estimation(out=ch):
+                assert LC.nrLDPC_hip_pusch_channel_estimation(rx.data_ptr(), stride, out.data_ptr(), stride, n_rx, seg_arr, len(csegs), None, m.MEM_DEVICE,
+                                                              s_ptr) == 0, m.last_error()
+
+            def estimation_meas():
+                assert LM.nrLDPC_hip_pusch_channel_estimation_meas(rx.data_ptr(), stride, ch2.data_ptr(), stride, n_rx, seg_arr, len(csegs), None, tb_arr,
+                                                                   div_arr, 1, mx.data_ptr(), nv.data_ptr(), m.MEM_DEVICE, s_ptr) == 0, m.last_error()
+
+            def level():
+                assert LX.nrLDPC_hip_ulsch_channel_level_grid_mmse(ch.data_ptr(), n_rx, stride, first_arr, 1, mx.data_ptr(), lv.data_ptr(), m.MEM_DEVICE,
+                                                                   s_ptr) == 0, m.last_error()
+            legs = {"estimation": estimation, "level": level}
+            out = {"descriptors": len(csegs)}
+            if has_meas:
+                legs["estimation_meas"] = estimation_meas
+                with torch.cuda.stream(side):
+                    estimation()
+                    estimation_meas()
+                torch.cuda.synchronize()
+                want_mx, want_nv = 0, 0
+                rx_h = rx.cpu().numpy().reshape(-1, 2)
+                for c in csegs:
+                    a, noise, nest = m.pusch_chest_meas_host(rx_h, stride, n_rx, c)
+                    want_mx, want_nv = max(want_mx, a), want_nv + (noise // nest if nest else 0)
+                out["meas_equals_plain_and_host_form"] = bool(torch.equal(ch, ch2)) and int(mx[0]) == want_mx and int(nv[0]) == want_nv // (14 * 2 * n_rx)
+                out["max_ch"], out["nvar"] = int(mx[0]), int(nv[0])
+                if n_dmrs == 2:
+                    asegs = m.pusch_chest_avg_segments([alloc])[0]
+                    avg_arr = m._chest_avg_seg_array(asegs)
+
+                    def time_avg():
+                        assert LM.nrLDPC_hip_pusch_chest_time_avg(ch2.data_ptr(), stride, 2 * n_rx, avg_arr, 1, m.MEM_DEVICE, s_ptr) == 0, m.last_error()
+                    legs["time_avg"] = time_avg
+            for fn in legs.values():
+                with torch.cuda.stream(side):
+                    for _ in range(3):
+                        fn()
+            torch.cuda.synchronize()
+            ts = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    with torch.cuda.stream(side):
+                        torch.mm(fill_a, fill_a, out=fill_c)
+                        e0.record()
+                        fn()
+                        e1.record()
+                    torch.cuda.synchronize()
+                    ts[k].append(e0.elapsed_time(e1) * 1e3)
+            for k, v in ts.items():
+                out[k + "_us"] = {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)), "p10": float(np.percentile(v, 10)),
+                                  "p90": float(np.percentile(v, 90))}
+            if has_meas:
+                out["meas_minus_plain_us"] = {"median": float(np.median(ts["estimation_meas"]) - np.median(ts["estimation"])),
+                                              "min": float(np.min(ts["estimation_meas"]) - np.min(ts["estimation"]))}
+            res["configs"][f"{('TYPE1_INTERP', 'TYPE2_INTERP', 'TYPE1_AVG', 'TYPE2_AVG')[mode]}_dmrs{n_dmrs}"] = out
+    print(json.dumps(res))
+
+
+if len(sys.argv) > 2 and sys.argv[2] == "meas":
+    measure_meas()
+    sys.exit(0)
 A = 213176
 while m.nr_segmentation(A + 24, 1) is None:
     A += 8
