@@ -704,6 +704,10 @@ int launch_decoder(int kernel, ldpc_dec_args a, const CodeEntry *ce, uint32_t n_
     static const int fair_env = [] { const char *e = getenv("NRLDPC_HIP_FAIR"); return e ? atoi(e) : 1; }();
     if (fair_env && hsel.f_wg_per_cu >= 2 && n_blocks > (uint32_t)G().n_cus && hsel.f_n_threads >= 256)
       a.fair = hsel.f_n_threads / 256; /* waves per SIMD of one workgroup */
+    /* homogeneous launches of more workgroups than are resident at once: each one warms the LLR row of the block that follows it
+     * on its XCD (ldpc_kernels.h warm_ahead; the kernel compares with the launch's own size) */
+    const uint32_t resident = (uint32_t)(G().n_cus * std::max(1, hsel.f_wg_per_cu));
+    a.warm_ahead = (!a.jobs && n_blocks > resident) ? resident : 0u;
     HIP_TRY(ldpc_launch_dec_fast(a, hsel, n_blocks, s));
     if (trace_d) {
       std::vector<unsigned long long> h((size_t)n_blocks * 32);
@@ -760,6 +764,8 @@ int fill_dec_args(const t_nrLDPC_dec_params &p, const CodeEntry *ce, ldpc_dec_ar
   a.pull_stagger_ticks = a.pull_first_round = 0;
   a.trace = nullptr;
   a.fair = 0;
+  a.n_app = a.n_ext = 0; /* (the launchers of the homogeneous fast kernels fill them) */
+  a.warm_ahead = 0;
   for (int i = 0; i < 4; i++)
     a.crc_pow_tbl[i] = G().crc_pow[i];
   if (a.use_crc) {

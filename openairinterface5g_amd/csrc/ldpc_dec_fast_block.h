@@ -41,7 +41,7 @@ typedef const ldpc_dec_job LDPC_CONST_AS *ldpc_job_ptr_t; /* job records are rea
  *                             also takes [2p], [2p + 1] the clocks behind pass p's check-node / bit-node barrier, [20] the
  *                             passes that ran the eager parity sweep (bit p), [22 + p] the unsatisfied lanes counted by pass p
  *                             (exact up to LDPC_EAGER_MAX_BAD_LANES, a lower bound above), [32 + p] the check-node tasks of
- *                             pass p that ran without the parity
+ *                             pass p that ran without the parity, [42] .. [44] the prologue's steps (see there)
  *   int tid()                 threadIdx.x
  *   uint32_t ld_llr(p)        one dword of src32_prologue()'s row: a plain load, or one that bypasses the caches when the
  *                             row was written by the host while this kernel was running (resident server)
@@ -63,7 +63,27 @@ typedef const ldpc_dec_job LDPC_CONST_AS *ldpc_job_ptr_t; /* job records are rea
  *                             takes turns with them at the issue priority, pass by pass (see below)
  *   bool eager_check()        latency path: evaluate the parity check of a pass in a sweep of its own right after the
  *                             pass, instead of folding it into the next pass' check-node phase (which costs a whole
- *                             check-node phase when the block has converged); same results, same pass counts */
+ *                             check-node phase when the block has converged); same results, same pass counts
+ *   int n_app(code, zq)       dwords of the core / extension columns that the prologue copies from the LLR row into LDS:
+ *   int n_ext(code, zq)       ldpc_desc_n_app / ldpc_desc_n_ext of the descriptor, or the same numbers from the kernel arguments
+ *                             (homogeneous batch launches), which are there a scalar round trip earlier -- the LLR loads, the
+ *                             only long wait of the prologue, then go out as soon as the arguments have arrived
+ *   static bool warm_next     the caller knows which block follows this one on its XCD:
+ *   const uint32_t *warm_row()  ... that block's LLR row (num_llr bytes), or nullptr (no such block, warming switched off): one
+ *                             dword per cache line of it is requested at the start of the second pass and dropped */
+
+/* A/B switches like LDPC_SYN_SKIP (tools/build_variant.sh <name> -D...): the prologue's LLR extents from the kernel arguments, its
+ * LLR loads unconditional so that they are in flight together, the next row warmed in L2.  The last one is off: its arm was
+ * level on the headline code and slower on others (profiles/r19/README.md) */
+#ifndef LDPC_DEC_LLR_ARGS
+#define LDPC_DEC_LLR_ARGS 1
+#endif
+#ifndef LDPC_DEC_LLR_TOGETHER
+#define LDPC_DEC_LLR_TOGETHER 1
+#endif
+#ifndef LDPC_DEC_WARM
+#define LDPC_DEC_WARM 0
+#endif
 
 #ifndef LDPC_MUTE_ITEMS
 #define LDPC_MUTE_ITEMS 1 /* A/B: tools/build_variant.sh <name> -DLDPC_MUTE_ITEMS=0 */
@@ -122,6 +142,24 @@ __device__ __forceinline__ int ldpc_draw_issue(int *counter, int lane)
     t = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   return t;
 }
+
+/* the prologue's LLR extents by the descriptor (io.n_app / io.n_ext) */
+__device__ __forceinline__ int ldpc_desc_n_app(ldpc_code_ptr_t code, int zq) { return code->ncore * zq; }
+__device__ __forceinline__ int ldpc_desc_n_ext(ldpc_code_ptr_t code, int zq) { return code->f_ext_global ? 0 : (code->ncols - code->ncore) * zq; }
+
+/* "x has arrived": an empty statement that needs x in a scalar / vector register and that no memory access moves across.  The
+ * diagnostic instantiation reads the clock behind it, so that a stamp is not taken before what it speaks of is there; the
+ * request for the next block's row ends in one, so that the loads are made and their one wait stands where they are.  (The host
+ * build stores x into a volatile, which keeps its loads alive for the sanitizers.) */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LDPC_STAMP_BEHIND_S(x) asm volatile("" ::"s"(x) : "memory")
+#define LDPC_STAMP_BEHIND_V(x) asm volatile("" ::"v"(x) : "memory")
+#define LDPC_STAMP_BEHIND_ALL() __builtin_amdgcn_s_waitcnt(0) /* every load and LDS store of this wave */
+#else
+#define LDPC_STAMP_BEHIND_S(x) do { volatile uint32_t ldpc_keep_ = (uint32_t)(x); (void)ldpc_keep_; } while (0)
+#define LDPC_STAMP_BEHIND_V(x) LDPC_STAMP_BEHIND_S(x)
+#define LDPC_STAMP_BEHIND_ALL() ((void)0)
+#endif
 
 /* The code's tables, made absolute for this workgroup's LDS, and the row of zero bytes the padded bit-node lists point at:
  * [f_lds_etbl, f_lds_zero + Z + 4).  Done by the block body's prologue unless its caller says they are there already
@@ -210,19 +248,45 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
    * needs 3 + 4 such loads per thread for Zc = 384).  From HBM they go out before anything else; from host memory (the
    * server path, `stage`) only after the table copies -- loads retire in order, and the tables' device loads would
    * otherwise sit behind a trip over the link. */
-  const int n_app = ncore * zq, n_ext = ext_global ? 0 : (code->ncols - ncore) * zq;
+  const int n_app = io.n_app(code, zq), n_ext = io.n_ext(code, zq);
   uint32_t va[4], ve[4];
   if (!stage) {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int ia = tid + k * nt;
+#if LDPC_DEC_LLR_TOGETHER
+      /* every lane loads, the ones without a dword of their own the row's first one (a wave of them is one request): as
+       * `cond ? load : 0` each load sat in a branch of its own with its use -- the ^ 0x80808080 of the copy below -- and a
+       * wait for it: eight round trips to memory one after the other, not eight loads in flight */
+      va[k] = io.ld_llr(srcp + (ia < n_app ? ia : 0));
+      ve[k] = io.ld_llr(srcp + (ia < n_ext ? n_app + ia : 0));
+#else
       va[k] = ia < n_app ? io.ld_llr(srcp + ia) : 0u;
       ve[k] = ia < n_ext ? io.ld_llr(srcp + n_app + ia) : 0u;
+#endif
+    }
+  }
+  if constexpr (IO::pass_stamps) {
+    /* [42] the descriptor's scalars are there (and this wave's LLR loads are out), [43] the first LLR load of the last wave has
+     * returned, [44] this wave's table copies -- and, loads returning in order, its LLR loads -- are done */
+    if (tid == 0) {
+      LDPC_STAMP_BEHIND_S(ncore + num_llr + ext_global);
+      io.stamps()[42] = (uint32_t)wall_clock64();
+    }
+    if (tid == nt - 64) {
+      LDPC_STAMP_BEHIND_V(va[0]);
+      io.stamps()[43] = (uint32_t)wall_clock64();
     }
   }
   const bool have_tables = io.tables_resident();
   if (!have_tables)
     ldpc_fast_tables_to_lds(fsm, code, tid, nt);
+  if constexpr (IO::pass_stamps) {
+    if (tid == 0) {
+      LDPC_STAMP_BEHIND_ALL();
+      io.stamps()[44] = (uint32_t)wall_clock64();
+    }
+  }
   if (stage) {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -322,6 +386,30 @@ __device__ __forceinline__ int ldpc_dec_fast_block(uint8_t *fsm, ldpc_code_ptr_t
         __builtin_amdgcn_s_setprio(1);
       else
         __builtin_amdgcn_s_setprio(0);
+    }
+    if constexpr (IO::warm_next && LDPC_DEC_WARM != 0) {
+      /* The row of the block that follows this one on its XCD, asked for while this block has eight passes to go: one dword per
+       * 128-byte line, counted from the row's start, and the row's last dword (a row that does not start on a line boundary ends
+       * one line later).  The value is dropped -- nothing of it lives into the task loop below; the wave's next wait for a vector
+       * memory load covers it */
+      if (p == 2 && tid >= nt - 64) {
+        /* One wave asks, four loads per lane in flight together, so one wave waits, once, for one trip to memory -- the
+         * workgroup's youngest wave, which the SIMD's arbiter serves last anyway; the others draw its tasks meanwhile.  (As
+         * volatile loads, one per lane of a fifth of the threads, each was a system-scope load with a wait of its own.)  Lanes
+         * without a line of their own ask for the last dword again */
+        if (const uint32_t *nx = io.warm_row()) {
+          const int n_lines = (num_llr + 127) >> 7, last = (num_llr >> 2) - 1;
+          uint32_t got = 0;
+          for (int t0 = lane; t0 <= n_lines; t0 += 256) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              const int i = 32 * (t0 + 64 * k);
+              got ^= nx[i < last ? i : last];
+            }
+          }
+          LDPC_STAMP_BEHIND_V(got);
+        }
+      }
     }
     const uint32_t ab_word = (io.has_abort() && tid == 0 && p >= 2) ? io.abort_load() : 0u; /* in flight during the check-node phase */
     /* likewise the transport block's flag (a load that leaves the caches: its latency would otherwise sit between the

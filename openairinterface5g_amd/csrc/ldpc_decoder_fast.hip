@@ -64,7 +64,35 @@ template <bool JOBS, bool CRC = false, bool TRACE = false> struct ldpc_batch_io 
   __device__ __forceinline__ uint32_t ld_llr(const uint32_t *p) const { return *p; }
   __device__ __forceinline__ const uint32_t *src32_prologue() const { return src32(); }
   __device__ __forceinline__ uint32_t *stage_core() const { return nullptr; }
+  /* homogeneous launches: the launcher has put the row's extents beside the row's address (ldpc_fill_llr_extents) */
+  __device__ __forceinline__ int n_app(ldpc_code_ptr_t code, int zq) const
+  {
+    return (!JOBS && LDPC_DEC_LLR_ARGS) ? (int)a.n_app : ldpc_desc_n_app(code, zq);
+  }
+  __device__ __forceinline__ int n_ext(ldpc_code_ptr_t code, int zq) const
+  {
+    return (!JOBS && LDPC_DEC_LLR_ARGS) ? (int)a.n_ext : ldpc_desc_n_ext(code, zq);
+  }
+  /* ... and how many workgroups are resident at once: workgroups are handed to the XCDs in turn, so with a.warm_ahead a multiple
+   * of their number block blockIdx.x + a.warm_ahead is the one that follows this one on its XCD, and most likely on its CU */
+  static constexpr bool warm_next = !JOBS;
+  __device__ __forceinline__ const uint32_t *warm_row() const
+  {
+    /* (a.n_blocks, not gridDim.x: with the grid's size in use the compiler reads blockDim.x through a vector load, a round trip
+     * in front of the prologue's LLR loads) */
+    const uint32_t nb = blockIdx.x + a.warm_ahead;
+    if (a.warm_ahead == 0 || nb >= a.n_blocks)
+      return nullptr;
+    return reinterpret_cast<const uint32_t *>(a.llr + (size_t)nb * a.llr_stride);
+  }
 };
+
+/* the prologue's LLR extents of a homogeneous launch, from the descriptor the launch runs on (= ldpc_desc_n_app / ldpc_desc_n_ext) */
+static void ldpc_fill_llr_extents(ldpc_dec_args &a, const ldpc_code_desc_t &hc)
+{
+  a.n_app = (uint32_t)(hc.ncore * hc.f_zq);
+  a.n_ext = hc.f_ext_global ? 0u : (uint32_t)((hc.ncols - hc.ncore) * hc.f_zq);
+}
 
 /* JOBS = heterogeneous batch (one job record per workgroup, optional transport-block abort flags); the homogeneous
  * variant carries none of that through its loops.  One register budget for every workgroup size -- 128 VGPRs, i.e. 16
@@ -244,12 +272,15 @@ hipError_t ldpc_fast_kernel_init(void)
   return hipSuccess;
 }
 
-hipError_t ldpc_launch_dec_fast(const ldpc_dec_args &a, const ldpc_code_desc_t &hc, uint32_t n_blocks, hipStream_t stream)
+hipError_t ldpc_launch_dec_fast(const ldpc_dec_args &a0, const ldpc_code_desc_t &hc, uint32_t n_blocks, hipStream_t stream)
 {
   if (n_blocks == 0)
     return hipSuccess;
-  if (a.jobs)
-    return ldpc_launch_dec_fast_jobs(a, hc.f_n_threads, hc.f_lds_total, n_blocks, stream);
+  if (a0.jobs)
+    return ldpc_launch_dec_fast_jobs(a0, hc.f_n_threads, hc.f_lds_total, n_blocks, stream);
+  ldpc_dec_args a = a0;
+  ldpc_fill_llr_extents(a, hc);
+  a.n_blocks = n_blocks; /* (io.warm_row(): no request behind the launch's last row) */
   /* a lifting size with instantiations of its own (one block per workgroup: f_rstride = Z + 4, f_astride = 2 Z) */
   if (ldpc_fast_zc_enabled(hc.Z) && hc.f_mb == 1 && hc.f_rstride == hc.Z + 4 && hc.f_astride == 2 * hc.Z && !a.trace) {
     if (a.use_crc ? ldpc_launch_zc<false, true>(hc.Z, n_blocks, hc.f_n_threads, hc.f_lds_total, stream, a)
@@ -310,12 +341,15 @@ hipError_t ldpc_launch_dec_fast_multi_jobs(const ldpc_dec_args &a, int sub, int 
   return hipGetLastError();
 }
 
-hipError_t ldpc_launch_dec_fast_pull(const ldpc_dec_args &a, const ldpc_code_desc_t &hc, uint32_t n_blocks, hipStream_t stream)
+hipError_t ldpc_launch_dec_fast_pull(const ldpc_dec_args &a0, const ldpc_code_desc_t &hc, uint32_t n_blocks, hipStream_t stream)
 {
   if (n_blocks == 0)
     return hipSuccess;
-  if (a.jobs || !a.pull)
+  if (a0.jobs || !a0.pull)
     return hipErrorInvalidValue;
+  ldpc_dec_args a = a0;
+  ldpc_fill_llr_extents(a, hc);
+  a.warm_ahead = 0; /* (a workgroup writes its row itself, right before it reads it) */
   if (a.use_crc)
     hipLaunchKernelGGL(ldpc_dec_fast_pull_kernel<true>, dim3(n_blocks), dim3(hc.f_n_threads), hc.f_lds_total, stream, a);
   else

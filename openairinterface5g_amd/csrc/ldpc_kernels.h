@@ -66,7 +66,8 @@ struct ldpc_dec_args {
    * memory, device-mapped address -- into its row of `llr` (device memory, written here), then decodes from there */
   const int8_t *pull;
   uint32_t pull_stride;
-  uint32_t n_blocks; /* multi-block launches: blocks in the launch (the last workgroup may hold fewer than f_mb) */
+  uint32_t n_blocks; /* blocks in the launch, filled by the launchers that need it: multi-block launches (the last workgroup may
+                        hold fewer than f_mb), ldpc_launch_dec_fast (warm_ahead below) */
   uint32_t pull_stagger_ticks, pull_first_round; /* pull launches: see ldpc_dec_fast_pull_kernel */
   /* diagnostics (NRLDPC_HIP_DEC_TRACE=<file>, homogeneous fast launches): 32 x uint64 per workgroup -- placement, start / end
    * and the clocks of every phase of every pass (ldpc_dec_fast_kernel<.., .., true>; tools/dec_trace.py) */
@@ -74,6 +75,16 @@ struct ldpc_dec_args {
   /* > 0: workgroups of this launch share a CU, each with this many waves per SIMD -- they take turns at the issue priority
    * (ldpc_dec_fast_block.h, io.fair_turns()) */
   int32_t fair;
+  /* homogeneous one-block-per-workgroup launches (filled by ldpc_launch_dec_fast / ldpc_launch_dec_fast_pull from the host
+   * descriptor): dwords of the core resp. extension columns the prologue copies from the LLR row into LDS.  With them in the kernel
+   * arguments the prologue's LLR loads wait for the arguments only, not for a round trip to the descriptor behind them */
+  uint32_t n_app, n_ext;
+  /* Builds with -DLDPC_DEC_WARM=1 only (an A/B arm, off by default: profiles/r19/README.md).
+   * > 0: the workgroups resident at once (CUs x workgroups per CU).  Workgroup b asks, at the start of its second pass, for one
+   * dword per cache line of the LLR row of block b + warm_ahead -- the block that follows it on its XCD -- and drops the result, so
+   * that this block's prologue finds its row in the XCD's L2 (ldpc_dec_fast_block.h io.warm_row(); 0, or b + warm_ahead >=
+   * n_blocks: nothing is requested) */
+  uint32_t warm_ahead;
 };
 
 struct ldpc_enc_args {

@@ -110,6 +110,9 @@ template <bool CRC> struct srv_fast_io { /* the request header sits in LDS: read
   static constexpr bool tb_epilogue = false;
   static constexpr bool syndrome = !CRC;
   __device__ __forceinline__ bool tables_resident() const { return resident_; }
+  __device__ __forceinline__ int n_app(ldpc_code_ptr_t code, int zq) const { return ldpc_desc_n_app(code, zq); }
+  __device__ __forceinline__ int n_ext(ldpc_code_ptr_t code, int zq) const { return ldpc_desc_n_ext(code, zq); }
+  static constexpr bool warm_next = false;
   __device__ __forceinline__ uint32_t out_tag() const { return tag_; }
   __device__ __forceinline__ void put16(uint4 *p, uint32_t x, uint32_t y, uint32_t z, uint32_t t) const { srv_st16_sys(p, x, y, z, t); }
   /* the payload was written by the host (over the BAR, or into page-locked memory) while this kernel runs: system scope */

@@ -85,6 +85,9 @@ template <bool LROW, bool MUTE = false> struct tb_rx_fused_io {
   __device__ __forceinline__ uint32_t ld_llr(const uint32_t *p) const { return *p; }
   __device__ __forceinline__ const uint32_t *src32_prologue() const { return src32(); }
   __device__ __forceinline__ uint32_t *stage_core() const { return nullptr; }
+  __device__ __forceinline__ int n_app(ldpc_code_ptr_t code, int zq) const { return ldpc_desc_n_app(code, zq); }
+  __device__ __forceinline__ int n_ext(ldpc_code_ptr_t code, int zq) const { return ldpc_desc_n_ext(code, zq); }
+  static constexpr bool warm_next = false; /* (the soft-buffer stores evict such lines: profiles/r06/README.md 8) */
   static constexpr bool tb_epilogue = true;
   __device__ __forceinline__ bool tb_fused() const { return job->seg_idx >= 0; }
 

@@ -38,6 +38,12 @@ def analyse(d, label, ms_untraced):
     epi = end - lo(w[:, 1])
     print(f"   workgroup: total {dur.mean():.2f} us (min {dur.min():.2f}, max {dur.max():.2f}); prologue {pro.mean():.2f}; "
           f"hard decision + output (after the last pass) {epi.mean():.2f}")
+    if (w[:, 42] != 0).any():   # the prologue's own stamps (ldpc_dec_fast_block.h [42] .. [44])
+        med = lambda x: float(np.median(x))
+        t42, t43, t44 = (lo(w[:, k]) - start for k in (42, 43, 44))
+        print(f"   medians over the workgroups, from the workgroup's start (us): descriptor scalars there {med(t42):.2f}; first LLR load of the "
+              f"last wave back {med(t43):.2f}; wave 0's table copies and LLR loads done {med(t44):.2f}; behind the prologue's barrier {med(pro):.2f}"
+              f"  |  hard decision, from its start to the end behind the stores' barrier {med(epi):.2f}  |  whole workgroup {med(dur):.2f}")
     for k in sorted(set(n_iter.tolist())):
         sel = n_iter == k
         row = []
