@@ -439,8 +439,25 @@ int32_t nrLDPC_hip_ulsch_level_host(const int16_t *chFext, uint32_t n_rx, uint64
  * pusch_grid_segments (host only, no GPU): the descriptors of n_alloc PUSCH allocations as nr_rx_pusch_tp derives them
  * (:1584-1665): one segment per OFDM symbol with nb_re = get_nb_re_pusch > 0, allocation after allocation in symbol order,
  * sym_off the running sum (llr_offset / Qm), start_re = (first_carrier_offset + (rb_start + bwp_start) 12) % fft_size, rx_off =
- * rx_slot_off + symbol fft_size, ch_off = the allocation's ch_off + dmrs_symbol fft_size; first_sym_out[i] = allocation i's
- * measurement symbol, its first with REs.  At most `cap` segments are written, *n_seg_out receives their number.  Refused:
+ * rx_slot_off + symbol fft_size, ch_off = the allocation's ch_off + d fft_size with d the DMRS symbol whose estimates the OFDM
+ * symbol reads; first_sym_out[i] = allocation i's measurement symbol, its first with REs.  alloc.dmrs_symbol chooses d, two modes:
+ *   NRLDPC_HIP_DMRS_SYMBOL_FOLLOW (255, the reference's INVALID_VALUE, its value at :1460): as the reference with chest_time = 0
+ *     wherever the DMRS symbols carry data (one deviation, below).
+ *     pusch_vars->dmrs_symbol becomes the allocation's first DMRS symbol during estimation (:1477-1478) and the level reads that one
+ *     (:1606): first_sym_out names it.  The symbol loop sets dmrs_symbol = symbol when it reaches a DMRS symbol, before that
+ *     symbol's inner_rx (:1403-1408, :1414), and inner_rx extracts at dmrs_symbol ofdm_symbol_size (:1294): every segment names the
+ *     latest DMRS symbol of the allocation at or before its OFDM symbol, those in front of the first DMRS symbol the first.  The
+ *     reference's symbol jobs share pusch_vars->dmrs_symbol and run on a thread pool; this is its result with the symbols run
+ *     in order, one job in flight.  One deliberate deviation: the reference creates a symbol job only for a symbol with REs
+ *     (:1654-1666, num_pusch_symbols_per_thread = 1), so with type 1 and two CDM groups without data, where a DMRS symbol has no
+ *     REs, :1408 never runs and the reference keeps the first DMRS symbol's estimates for the whole slot.  Here the symbols behind
+ *     such a DMRS symbol read its estimates all the same; to reproduce the reference there, pass the first DMRS symbol explicitly.
+ *   0..13: that symbol for every segment and for first_sym_out.  This is chest_time = 1, where dmrs_symbol is the first DMRS
+ *     symbol for the whole slot (:1535-1537, after pusch_chest_time_avg), and any slot with a single DMRS symbol.  An explicit
+ *     symbol on a slot with several DMRS symbols is NOT what the reference does with chest_time = 0: the symbols behind the second
+ *     DMRS symbol would be demodulated with the first one's estimates.
+ * At most `cap` segments are written, *n_seg_out receives their number.  Refused: a dmrs_symbol of 14..254, 255 with no DMRS
+ * symbol inside the allocation's symbols (the reference would read estimates at 255 fft_size),
  * start_symbol + nr_of_symbols > 14, nr_of_symbols = 0, a DMRS symbol of the allocation followed by another (the reference
  * asserts, :421), rb_size = 0, 12 rb_size > fft_size, first_carrier_offset >= fft_size, a dmrs_config_type other than 0 (type 1)
  * or 1 (type 2), num_dmrs_cdm_grps_no_data other than 1 or 2, the sum of nb_re above plane, no symbol with REs, more than cap
@@ -450,6 +467,7 @@ int32_t nrLDPC_hip_ulsch_level_host(const int16_t *chFext, uint32_t n_rx, uint64
 #define NRLDPC_HIP_RXG_FULL 0
 #define NRLDPC_HIP_RXG_DMRS1 1
 #define NRLDPC_HIP_RXG_DMRS2 2
+#define NRLDPC_HIP_DMRS_SYMBOL_FOLLOW 255 /* alloc.dmrs_symbol: every symbol reads the latest DMRS symbol at or before it */
 typedef struct nrLDPC_hip_rx_grid_seg {
   uint32_t tb;       /* index into shift / log2_maxh */
   uint8_t Qm;        /* 2, 4, 6, 8 */
@@ -470,7 +488,7 @@ typedef struct nrLDPC_hip_pusch_alloc {
   uint8_t Qm;
   uint8_t dmrs_config_type;           /* 0: type 1, 1: type 2 */
   uint8_t num_dmrs_cdm_grps_no_data;  /* 1 or 2 */
-  uint8_t dmrs_symbol;                /* the symbol whose estimates are used; the caller decides (chest_time changes it) */
+  uint8_t dmrs_symbol;                /* NRLDPC_HIP_DMRS_SYMBOL_FOLLOW (chest_time = 0), or 0..13: one symbol's estimates for all */
   uint32_t fft_size;                  /* N */
   uint32_t first_carrier_offset;
   uint32_t bwp_start, rb_start, rb_size;

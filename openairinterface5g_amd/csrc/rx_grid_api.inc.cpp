@@ -45,12 +45,31 @@ int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, ui
       return set_error("pusch_grid_segments: num_dmrs_cdm_grps_no_data must be 1 or 2");
     if (type == 1 && cdm == 2)
       return set_error("pusch_grid_segments: type 2 with two CDM groups without data is not supported (the level runs over extracted entries beyond nb_re)");
+    /* whose estimates a symbol reads: an explicit symbol for the whole allocation, or the reference's own rule with chest_time = 0 --
+     * dmrs_symbol starts as the allocation's first DMRS symbol (nr_ulsch_demodulation.c:1460, :1477-1478; the level reads that one,
+     * :1606) and the symbol loop moves it to each DMRS symbol it reaches before that symbol's inner_rx (:1403-1408).  One deliberate
+     * deviation: the reference runs that loop only for symbols with REs (:1666), so with two CDM groups without data its DMRS
+     * symbols never move dmrs_symbol; here every DMRS symbol of the allocation does. */
+    const bool follow = a.dmrs_symbol == NRLDPC_HIP_DMRS_SYMBOL_FOLLOW;
+    if (!follow && a.dmrs_symbol >= 14)
+      return set_error("pusch_grid_segments: dmrs_symbol must be 0..13 or 255 (NRLDPC_HIP_DMRS_SYMBOL_FOLLOW)");
+    uint32_t first_dmrs = a.dmrs_symbol, cur_dmrs = a.dmrs_symbol;
+    if (follow) {
+      first_dmrs = a.start_symbol;
+      while (first_dmrs < a.start_symbol + a.nr_of_symbols && !nr_rxg_is_dmrs(a.ul_dmrs_symb_pos, first_dmrs))
+        first_dmrs++;
+      if (first_dmrs == a.start_symbol + a.nr_of_symbols)
+        return set_error("pusch_grid_segments: dmrs_symbol = 255 needs a DMRS symbol inside the allocation (the reference would read estimates at 255 fft_size)");
+      cur_dmrs = first_dmrs;
+    }
     const uint32_t start_re = nr_rxg_start_re(a.first_carrier_offset, a.bwp_start, a.rb_start, N);
     uint32_t off = 0;
     bool have_first = false;
     for (uint32_t sym = a.start_symbol; sym < a.start_symbol + a.nr_of_symbols; sym++) {
       if (nr_rxg_double_dmrs(a.ul_dmrs_symb_pos, sym))
         return set_error("pusch_grid_segments: two adjacent DMRS symbols are not supported");
+      if (follow && nr_rxg_is_dmrs(a.ul_dmrs_symb_pos, sym))
+        cur_dmrs = sym;
       const uint32_t nb = nr_rxg_nb_re(a.ul_dmrs_symb_pos, sym, type, cdm, a.rb_size);
       if (nb == 0)
         continue;
@@ -65,13 +84,14 @@ int32_t nrLDPC_hip_pusch_grid_segments(const nrLDPC_hip_pusch_alloc_t *alloc, ui
       g.fft_size = N;
       g.start_re = start_re;
       g.rx_off = a.rx_slot_off + (uint64_t)sym * N;
-      g.ch_off = a.ch_off + (uint64_t)a.dmrs_symbol * N;
+      g.ch_off = a.ch_off + (uint64_t)cur_dmrs * N;
       g.rec_off = a.rec_off;
       off += nb;
       if (off > a.plane)
         return set_error("pusch_grid_segments: the symbols' REs add up to more than plane");
       segs.push_back(g);
       if (!have_first) {
+        g.ch_off = a.ch_off + (uint64_t)first_dmrs * N;
         first.push_back(g);
         have_first = true;
       }

@@ -1238,6 +1238,7 @@ def ulsch_channel_compensation(rx, ch, n_rx, ant_stride, segs, shift, records, s
 EXPORTS += ["nrLDPC_hip_ulsch_channel_level_grid", "nrLDPC_hip_ulsch_channel_compensation_grid", "nrLDPC_hip_ulsch_extract_host",
             "nrLDPC_hip_pusch_grid_segments"]
 RXG_FULL, RXG_DMRS1, RXG_DMRS2 = 0, 1, 2
+DMRS_SYMBOL_FOLLOW = 255                # alloc["dmrs_symbol"]: every symbol reads the latest DMRS symbol at or before it (chest_time = 0)
 
 
 class nrLDPC_hip_rx_grid_seg_t(C.Structure):
@@ -1315,8 +1316,10 @@ def ulsch_extract_host(rx_sym, ch_sym, pattern, fft_size, start_re, nb_re):
 
 
 def pusch_grid_segments(allocs, cap=None):
-    """nrLDPC_hip_pusch_grid_segments: allocs = dicts with the fields of nrLDPC_hip_pusch_alloc_t.  Returns (segs, first_sym), lists
-    of dicts with the fields of nrLDPC_hip_rx_grid_seg_t."""
+    """nrLDPC_hip_pusch_grid_segments: allocs = dicts with the fields of nrLDPC_hip_pusch_alloc_t (dmrs_symbol = DMRS_SYMBOL_FOLLOW:
+    every symbol reads the latest DMRS symbol at or before it, the reference with chest_time = 0 but for two CDM groups without
+    data; 0..13: that symbol's estimates for the whole allocation).  Returns (segs, first_sym),
+    lists of dicts with the fields of nrLDPC_hip_rx_grid_seg_t."""
     n, arr = len(allocs), _struct_array(nrLDPC_hip_pusch_alloc_t, allocs, _RXG_ALLOC_KEYS)
     cap = 14 * n if cap is None else cap
     out, first, n_out = (nrLDPC_hip_rx_grid_seg_t * max(cap, 1))(), (nrLDPC_hip_rx_grid_seg_t * max(n, 1))(), C.c_uint32(0)

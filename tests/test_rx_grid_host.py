@@ -132,6 +132,89 @@ def test_pusch_grid_segments_equals_the_symbol_loop(built, dmrs_type, cdm):
     assert get_nb_re_pusch(dict(allocs[0], start_symbol_index=0), 2) == (12 - cdm * (6 if dmrs_type == 0 else 4)) * allocs[0]["rb_size"]
 
 
+# (start_symbol, nr_of_symbols, DMRS symbols): two and three DMRS symbols; DMRS on the first symbol; one DMRS symbol behind the start;
+# DMRS bits outside the allocation's symbols on both sides (1 and 12), two inside
+FOLLOW_SHAPES = [(0, 14, (2, 11)), (0, 14, (2, 7, 11)), (0, 14, (0, 5, 10)), (1, 12, (3,)), (3, 8, (1, 5, 9, 12))]
+
+
+@pytest.mark.parametrize("dmrs_type,cdm", [(0, 1), (0, 2), (1, 1)])
+def test_pusch_grid_segments_follows_the_reference_dmrs_symbol(built, dmrs_type, cdm):
+    """dmrs_symbol = 255: ch_off per segment from the restatement of the reference's own writes to pusch_vars->dmrs_symbol
+    (rx_grid_np.dmrs_symbol_rule), not from the implementation's formula.  With one CDM group without data (either type) every DMRS
+    symbol has REs and a symbol job, and the library's descriptors are the restated reference's.  With two (type 1) they DEPART from
+    it, deliberately: the reference creates no job for a symbol without REs (:1666), :1408 never runs for its DMRS
+    symbols and every symbol keeps the first DMRS symbol's estimates; the library moves on to each DMRS symbol's estimates all the
+    same, which is the restatement with that gate lifted (job_for_every_symbol).  Both expectations are stated below."""
+    import openairinterface5g_amd as pkg
+    from rx_grid_np import dmrs_symbol_rule, get_next_dmrs_symbol_in_slot
+    m = pkg.ldpc
+    assert m.DMRS_SYMBOL_FOLLOW == 255
+    allocs = [alloc(tb=i, Qm=(2, 4, 6, 8)[i % 4], dmrs_config_type=dmrs_type, num_dmrs_cdm_grps_no_data=cdm, start_symbol=s0, nr_of_symbols=ns,
+                    ul_dmrs_symb_pos=sum(1 << d for d in dm), rb_size=1 + i, rb_start=i, dmrs_symbol=m.DMRS_SYMBOL_FOLLOW, rec_off=1000 * i,
+                    ch_off=5 + i) for i, (s0, ns, dm) in enumerate(FOLLOW_SHAPES)]
+    segs, first = m.pusch_grid_segments(allocs)
+    want, want_first, spans = [], [], []
+    for a, (s0, ns, dm) in zip(allocs, FOLLOW_SHAPES):
+        pdu = dict(a, start_symbol_index=a["start_symbol"])
+        meas, rows = symbol_loop(pdu, a["Qm"])
+        with_res = [symbol for symbol, _, _ in rows]
+        inside = [d for d in dm if s0 <= d < s0 + ns]
+        ref_level, ref_read = dmrs_symbol_rule(pdu, chest_time=0)                             # the reference as written
+        level, read = dmrs_symbol_rule(pdu, chest_time=0, job_for_every_symbol=True)          # what the library does
+        # the library's rule in words: the latest DMRS symbol of the allocation at or before the symbol, the first one in front of it
+        assert level == ref_level == inside[0] and read == {s: max([d for d in inside if d <= s], default=inside[0]) for s in with_res}
+        if cdm == 1:
+            assert ref_read == read
+        else:                                                           # the departure: the reference never leaves the first DMRS symbol
+            assert ref_read == {s: inside[0] for s in with_res} and not set(inside) & set(with_res)
+            assert {s for s in with_res if ref_read[s] != read[s]} == ({s for s in with_res if s > inside[1]} if len(inside) > 1 else set())
+        # chest_time = 1 changes the level's symbol alone, and only where :1535-1537's end_symbol = nr_of_symbols ends the search early
+        level1, read1 = dmrs_symbol_rule(pdu, chest_time=1)
+        assert read1 == ref_read and level1 == (level if level < ns else 255) == get_next_dmrs_symbol_in_slot(a["ul_dmrs_symb_pos"], s0, ns) & 0xff
+        start_re = (a["first_carrier_offset"] + (a["rb_start"] + a["bwp_start"]) * 12) % a["fft_size"]
+        for symbol, nb_re, sym_off in rows:
+            is_dmrs = (a["ul_dmrs_symb_pos"] >> symbol) & 1
+            d = dict(tb=a["tb"], Qm=a["Qm"], pattern=(DMRS1 if dmrs_type == 0 else DMRS2) if is_dmrs else FULL, nb_re=nb_re, plane=a["plane"],
+                     sym_off=sym_off, fft_size=a["fft_size"], start_re=start_re, rx_off=a["rx_slot_off"] + symbol * a["fft_size"],
+                     ch_off=a["ch_off"] + read[symbol] * a["fft_size"], rec_off=a["rec_off"])
+            want.append(d)
+            if symbol == meas:
+                want_first.append(dict(d, ch_off=a["ch_off"] + level * a["fft_size"]))
+        spans.append(sorted({read[symbol] for symbol, _, _ in rows}))
+    early = dict(allocs[0], start_symbol_index=4, nr_of_symbols=6, ul_dmrs_symb_pos=1 << 9)          # the early end of :1535-1537's search
+    assert dmrs_symbol_rule(early, chest_time=1)[0] == 255 and dmrs_symbol_rule(early, chest_time=0)[0] == 9
+    assert segs == want and first == want_first
+    assert spans == [[d for d in dm if s0 <= d < s0 + ns] for s0, ns, dm in FOLLOW_SHAPES]      # every DMRS symbol inside serves a span
+    # an explicit symbol keeps its meaning: the same descriptors but for ch_off, which names that symbol everywhere
+    for d_sym in (0, 2, 13):
+        e_segs, e_first = m.pusch_grid_segments([dict(a, dmrs_symbol=d_sym) for a in allocs])
+        off = {a["tb"]: a["ch_off"] + d_sym * a["fft_size"] for a in allocs}
+        assert e_segs == [dict(s, ch_off=off[s["tb"]]) for s in want] and e_first == [dict(s, ch_off=off[s["tb"]]) for s in want_first]
+    # with one DMRS symbol the two modes agree
+    one = [a for a, (_, _, dm) in zip(allocs, FOLLOW_SHAPES) if len(dm) == 1]
+    assert m.pusch_grid_segments(one) == m.pusch_grid_segments([dict(a, dmrs_symbol=3) for a in one])
+
+
+def test_pusch_grid_segments_dmrs_symbol_refusals(built):
+    """14..254 name no symbol; 255 needs a DMRS symbol inside the allocation.  Neither refusal writes anything."""
+    import openairinterface5g_amd as pkg
+    m = pkg.ldpc
+    L = m._rxg_lib()
+    bad = [(dict(dmrs_symbol=14), "0..13 or 255"), (dict(dmrs_symbol=100), "0..13 or 255"), (dict(dmrs_symbol=254), "0..13 or 255"),
+           (dict(dmrs_symbol=255, ul_dmrs_symb_pos=0), "needs a DMRS symbol"),
+           (dict(dmrs_symbol=255, start_symbol=4, nr_of_symbols=5, ul_dmrs_symb_pos=(1 << 2) | (1 << 10)), "needs a DMRS symbol")]
+    for change, why in bad:
+        with pytest.raises(RuntimeError):
+            m.pusch_grid_segments([alloc(), alloc(**change)])
+        assert why in m.last_error(), (change, m.last_error())
+        arr = (m.nrLDPC_hip_pusch_alloc_t * 2)(*[m.nrLDPC_hip_pusch_alloc_t(**{k: a.get(k, 0) for k in m._RXG_ALLOC_KEYS}) for a in (alloc(), alloc(**change))])
+        out, first, n = (m.nrLDPC_hip_rx_grid_seg_t * 28)(), (m.nrLDPC_hip_rx_grid_seg_t * 2)(), C.c_uint32(77)
+        assert L.nrLDPC_hip_pusch_grid_segments(arr, 2, out, 28, first, C.byref(n)) < 0 and why in m.last_error()
+        assert n.value == 77 and bytes(out) == bytes(C.sizeof(out)) and bytes(first) == bytes(C.sizeof(first))
+    # the explicit symbol need not be a DMRS symbol of the allocation (the caller decides), and no DMRS symbol at all is fine with one
+    m.pusch_grid_segments([alloc(dmrs_symbol=13), alloc(dmrs_symbol=0, ul_dmrs_symb_pos=0)])
+
+
 def test_pusch_grid_segments_refusals(built):
     import openairinterface5g_amd as pkg
     m = pkg.ldpc

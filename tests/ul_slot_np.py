@@ -111,35 +111,9 @@ def dmrs_res(mode, port, n_pil):
     return 2 * k + ((port >> 1) & 1)
 
 
-def build_slot(m, case):
-    """The transport block, its descriptors and the slot of one case.  Returns a dict: tb, scr, pay, alloc, gsegs, first, csegs (every
-    layer's), delay (int32 per (descriptor, antenna): tau[a]), rx (int16 [n_rx, rx_stride, 2]), rx_stride, ch_stride, h (complex128
-    [n_layers, n_rx, 12 rb]: the true channel on the allocation), h16 (its rounding to int16 [.., 2]), g, e, max_ch (the largest
-    component of h16) and nvar = 2 sigma^2."""
-    from test_gpu_tb_chain import valid_tbs
-    c = case
-    rng = np.random.default_rng(9000 + c["seed"])
-    N, rb, L, n_rx, Qm, typ = c["N"], c["rb"], c["n_layers"], c["n_rx"], c["Qm"], c["mode"] & 1
-    n_rb = N // 12 - 1 - (N // 12 - 1) % 2                              # the carrier's width: the wrap lies between two PRBs
-    rb_start = n_rb // 2 - rb // 2                                      # half of the allocation on either side of the wrap
-    dmrs_sym = 2 + (c["seed"] & 1)
-    S = 13 * 12 * rb + ((8 if typ else 6) * rb if c["cdm"] == 1 else 0)  # data REs per layer
-    G = Qm * L * S
-    tb = dict(A=valid_tbs(int(G * c["rate"]), c["BG"]), G=G, BG=c["BG"], Qm=Qm, Nl=L, rv=0, tbslbrm=0)
-    scr = (int(rng.integers(0, 0x10000)), 0, int(rng.integers(0, 1024)))
-    pay = rng.integers(0, 256, tb["A"] // 8, dtype=np.uint8)
-    rx_stride, ch_stride = 14 * N + 9, 14 * N + 64
-    alloc = dict(tb=0, Qm=Qm, dmrs_config_type=typ, num_dmrs_cdm_grps_no_data=c["cdm"], dmrs_symbol=dmrs_sym, fft_size=N,
-                 first_carrier_offset=N - 6 * n_rb, bwp_start=0, rb_start=rb_start, rb_size=rb, start_symbol=0, nr_of_symbols=14,
-                 ul_dmrs_symb_pos=1 << dmrs_sym, plane=G // Qm, rx_slot_off=5, ch_off=7, rec_off=0)
-    cfg = dict(slot=int(rng.integers(0, 20)), scid=c["seed"] & 1, dmrs_scrambling_id=int(rng.integers(0, 65536)), port=c["ports"][0],
-               chest_freq=c["mode"] >> 1)
-    gsegs, first = m.pusch_grid_segments([alloc])
-    csegs = chest_descriptors(m, alloc, cfg, c["ports"], n_rx, ch_stride)
-    assert len(csegs) == L and all(s["mode"] == c["mode"] for s in csegs) and sum(s["nb_re"] for s in gsegs) == S
-    k0 = csegs[0]["start_re"]
-    assert k0 + 12 * rb > N and 24 <= N - k0 <= 12 * rb - 24, "a PRB pair lies on each side of the wrap"
-    # the channel
+def channel_of(c, rng):
+    """The case's channel on its allocation, drawn from rng: (g, e, h complex128 [n_layers, n_rx, 12 rb], h16, max_ch)"""
+    N, rb, L, n_rx = c["N"], c["rb"], c["n_layers"], c["n_rx"]
     tau = np.array(c["tau"], np.float64)
     assert len(tau) == n_rx and np.abs(tau).max() <= 20 and (n_rx == 1 or (tau.min() < 0 < tau.max() and len(set(c["tau"])) > 1))
     gm, ph = rng.uniform(*c["gain"], n_rx), rng.uniform(0, 2 * np.pi, n_rx)
@@ -162,6 +136,52 @@ def build_slot(m, case):
         assert (np.abs(h) ** 2 >= 2 ** 17).all() and (np.abs(h) ** 2 < 2 ** 18).all()
     max_ch = int(np.abs(h16.astype(np.int32)).max())
     assert L == 1 or max_ch < 2048                                     # shift_ch_ext = 0 in the MMSE level
+    return g, e, h, h16, max_ch
+
+
+def span_of(dmrs, symbol):
+    """which DMRS symbol (index into dmrs) serves `symbol`: the latest at or before it, the first in front of it"""
+    return max(sum(d <= symbol for d in dmrs) - 1, 0)
+
+
+def build_slot(m, case, dmrs=None, f_span=None, rng_seed=None):
+    """The transport block, its descriptors and the slot of one case.  Returns a dict: tb, scr, pay, alloc, gsegs, first, csegs (every
+    layer's), delay (int32 per (descriptor, antenna): tau[a]), rx (int16 [n_rx, rx_stride, 2]), rx_stride, ch_stride, h (complex128
+    [n_layers, n_rx, 12 rb]: the true channel on the allocation), h16 (its rounding to int16 [.., 2]), g, e, max_ch (the largest
+    component of h16) and nvar = 2 sigma^2.
+    By default one DMRS symbol (2 or 3 by the seed), named in alloc.dmrs_symbol.  ul_slot_tv_np.py passes dmrs = several DMRS symbols
+    (alloc.dmrs_symbol = 255; csegs layer-major, within a layer in symbol order) and f_span = a complex factor on the channel per
+    DMRS symbol, which holds from that symbol to the next (span_of); h stays the channel without it, max_ch is taken with it."""
+    from test_gpu_tb_chain import valid_tbs
+    c = case
+    rng = np.random.default_rng(9000 + c["seed"] if rng_seed is None else rng_seed)
+    N, rb, L, n_rx, Qm, typ = c["N"], c["rb"], c["n_layers"], c["n_rx"], c["Qm"], c["mode"] & 1
+    n_rb = N // 12 - 1 - (N // 12 - 1) % 2                              # the carrier's width: the wrap lies between two PRBs
+    rb_start = n_rb // 2 - rb // 2                                      # half of the allocation on either side of the wrap
+    follow = dmrs is not None
+    dmrs = tuple(dmrs) if follow else (2 + (c["seed"] & 1),)
+    n_dm = len(dmrs)
+    f_span = np.ones(n_dm, np.complex128) if f_span is None else np.asarray(f_span, np.complex128)
+    S = (14 - n_dm) * 12 * rb + n_dm * ((8 if typ else 6) * rb if c["cdm"] == 1 else 0)  # data REs per layer
+    G = Qm * L * S
+    tb = dict(A=valid_tbs(int(G * c["rate"]), c["BG"]), G=G, BG=c["BG"], Qm=Qm, Nl=L, rv=0, tbslbrm=0)
+    scr = (int(rng.integers(0, 0x10000)), 0, int(rng.integers(0, 1024)))
+    pay = rng.integers(0, 256, tb["A"] // 8, dtype=np.uint8)
+    rx_stride, ch_stride = 14 * N + 9, 14 * N + 64
+    alloc = dict(tb=0, Qm=Qm, dmrs_config_type=typ, num_dmrs_cdm_grps_no_data=c["cdm"], dmrs_symbol=255 if follow else dmrs[0], fft_size=N,
+                 first_carrier_offset=N - 6 * n_rb, bwp_start=0, rb_start=rb_start, rb_size=rb, start_symbol=0, nr_of_symbols=14,
+                 ul_dmrs_symb_pos=sum(1 << d for d in dmrs), plane=G // Qm, rx_slot_off=5, ch_off=7, rec_off=0)
+    cfg = dict(slot=int(rng.integers(0, 20)), scid=c["seed"] & 1, dmrs_scrambling_id=int(rng.integers(0, 65536)), port=c["ports"][0],
+               chest_freq=c["mode"] >> 1)
+    gsegs, first = m.pusch_grid_segments([alloc])
+    csegs = chest_descriptors(m, alloc, cfg, c["ports"], n_rx, ch_stride)
+    assert len(csegs) == L * n_dm and all(s["mode"] == c["mode"] for s in csegs) and sum(s["nb_re"] for s in gsegs) == S
+    assert [(s["rx_off"] - alloc["rx_slot_off"]) // N for s in csegs] == list(dmrs) * L
+    k0 = csegs[0]["start_re"]
+    assert k0 + 12 * rb > N and 24 <= N - k0 <= 12 * rb - 24, "a PRB pair lies on each side of the wrap"
+    g, e, h, h16, max_ch = channel_of(c, rng)
+    max_ch = int(np.abs(_c16(h[None] * f_span[:, None, None, None]).astype(np.int32)).max())
+    assert L == 1 or (max_ch < 2048 and (np.abs(h * np.abs(f_span).max()) ** 2 < 2 ** 18).all())
     # the slot
     tx = symbols_np(O.dlsch_encode(tb, pay), scr, Qm, L)              # = dlsch_encode_symbols_host, which needs a GPU (the GPU test checks)
     assert tx.shape == (L, S, 2)
@@ -172,22 +192,25 @@ def build_slot(m, case):
         v = v + c["sigma"] * (rng.standard_normal(v.shape) + 1j * rng.standard_normal(v.shape))
         rx[:, at] = _c16(v)
     for s in gsegs:
+        f = f_span[span_of(dmrs, (s["rx_off"] - alloc["rx_slot_off"]) // N)]
         j = np.arange(s["nb_re"])
         p_j = {FULL: j, DMRS1: 2 * j + 1, DMRS2: 6 * (j // 4) + 2 + j % 4}[s["pattern"]]
-        put(s["rx_off"] + (s["start_re"] + p_j) % N, np.einsum("lar,lr->ar", h[:, :, p_j], x[:, s["sym_off"]:s["sym_off"] + s["nb_re"]]))
+        put(s["rx_off"] + (s["start_re"] + p_j) % N, f * np.einsum("lar,lr->ar", h[:, :, p_j], x[:, s["sym_off"]:s["sym_off"] + s["nb_re"]]))
     n_pil = (4 if typ else 6) * rb
-    dm = np.zeros((n_rx, 12 * rb), np.complex128)
-    used = np.zeros(12 * rb, bool)
-    for l, cs in enumerate(csegs):
-        p = m.pusch_dmrs_host(cs["c_init"], cs["dmrs_offset"], n_pil, cs["port"], typ).astype(np.float64)
-        re = dmrs_res(c["mode"], cs["port"], n_pil)
-        dm[:, re] += h[l][:, re] * (p[:, 0] - 1j * p[:, 1])[None, :] / (23170.0 * np.sqrt(2.0))
-        used[re] = True
-    re = np.flatnonzero(used)
-    put(csegs[0]["rx_off"] + (k0 + re) % N, dm[:, re])
+    for i in range(n_dm):                                              # each DMRS symbol on the air with its span's factor
+        dm = np.zeros((n_rx, 12 * rb), np.complex128)
+        used = np.zeros(12 * rb, bool)
+        for l in range(L):
+            cs = csegs[l * n_dm + i]
+            p = m.pusch_dmrs_host(cs["c_init"], cs["dmrs_offset"], n_pil, cs["port"], typ).astype(np.float64)
+            re = dmrs_res(c["mode"], cs["port"], n_pil)
+            dm[:, re] += f_span[i] * h[l][:, re] * (p[:, 0] - 1j * p[:, 1])[None, :] / (23170.0 * np.sqrt(2.0))
+            used[re] = True
+        re = np.flatnonzero(used)
+        put(csegs[i]["rx_off"] + (k0 + re) % N, dm[:, re])
     delay = np.array([c["tau"][a] for _ in csegs for a in range(n_rx)], np.int32)
     return dict(case=c, tb=tb, scr=scr, pay=pay, alloc=alloc, gsegs=gsegs, first=first, csegs=csegs, delay=delay, rx=rx, rx_stride=rx_stride,
-                ch_stride=ch_stride, tx=tx, h=h, h16=h16, g=g, e=e, max_ch=max_ch, nvar=int(round(2 * c["sigma"] ** 2)))
+                ch_stride=ch_stride, tx=tx, h=h, h16=h16, g=g, e=e, max_ch=max_ch, nvar=int(round(2 * c["sigma"] ** 2)), dmrs=dmrs, f_span=f_span)
 
 
 _SLOTS = {}
