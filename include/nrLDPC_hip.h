@@ -597,8 +597,8 @@ int32_t nrLDPC_hip_ulsch_level_ml_host(const int16_t *chFext, uint32_t n_rx, uin
  * For antenna a the symbol is read at c16 index rx_off + a rx_ant_stride + subcarrier (the grid wraps at fft_size; start_re is
  * bwp_start_subcarrier) and exactly 12 rb_size c16 are written at ch_off + a ch_ant_stride, overwritten: the reference's memset
  * of the whole symbol and its TYPE1_INTERP spill of four entries behind the allocation are not reproduced.  est_delay holds
- * one int32 per (descriptor, antenna) at delay_off + a, the value nr_est_delay would have found (the search itself, a
- * fixed-point IDFT, is not built); NULL means 0 everywhere.  max_ch and nvar: pusch_channel_estimation_meas below.  Deviations from the
+ * one int32 per (descriptor, antenna) at delay_off + a, the value nr_est_delay would have found (pusch_est_delay below
+ * searches it on the GPU, in fp32; the reference's fixed-point IDFT is not built); NULL means 0 everywhere.  max_ch and nvar: pusch_channel_estimation_meas below.  Deviations from the
  * reference: TYPE2_AVG reads every RE relative to the descriptor's symbol and PRB b uses pilots 4b .. 4b + 3.
  * mem = HOST stages one contiguous span of the grid, from the lowest to the highest c16 any (descriptor, antenna) pair reads,
  * works on a bounce of the span of estimates from the lowest to the highest c16 written, and copies only the write set back to
@@ -703,6 +703,39 @@ int32_t nrLDPC_hip_pusch_chest_time_avg(int16_t *ul_ch, uint64_t ch_ant_stride, 
 int32_t nrLDPC_hip_pusch_chest_time_avg_host(int16_t *ul_ch, const nrLDPC_hip_chest_avg_seg_t *seg);
 int32_t nrLDPC_hip_pusch_chest_avg_segments(const nrLDPC_hip_pusch_alloc_t *alloc, uint32_t n_alloc, nrLDPC_hip_chest_avg_seg_t *out, uint32_t cap,
                                             uint32_t *n_out, uint8_t *first_dmrs_out);
+/* The delay search: what nr_est_delay (common/utils/nr/nr_common.c:968-990) looks for in the LS estimates of the same DMRS symbol,
+ * so that pusch_est_delay -> pusch_channel_estimation(_meas) -> level -> compensation -> decode on one stream needs no host value.
+ * csrc/nr_delay.h defines it once for host and device.  For one descriptor (the estimation's, unchanged) and antenna a, N =
+ * fft_size:
+ *   x[k], k < N, indexed from the allocation's first RE as the reference's ul_ls_est is, zero for k >= 12 rb_size.  TYPE1_INTERP:
+ *     x[4n + j], j = 0..3, is the int16-cast LS value of pilot pair n (nr_ul_channel_estimation.c:176-192); TYPE2_INTERP: REs 0..3
+ *     of 6-RE block m hold ch & ~3 per component, REs 4, 5 hold ch (:264-272).  Bit for bit csrc/nr_chest.h's values.  Every antenna
+ *     starts from zeros (the reference's type-2 line :270 adds into an array it clears once per call: not reproduced).
+ *   y[n] = sum_k x[k] exp(+2 pi i k n / N), unnormalised, in fp32; P[n] = |y[n]|^2.
+ *   The scan n = 0 .. N - 1 with P > best (strict) from best = 0, position 0; a position > N/2 has N subtracted.
+ *   flags = NRLDPC_HIP_DELAY_RUNNING_MAX: best and its position are cleared per descriptor and carried from antenna 0 to antenna a,
+ *     as the reference's delay_t is: antenna a receives the position of the largest sample over antennas 0 .. a.
+ *   flags = NRLDPC_HIP_DELAY_PER_ANTENNA: cleared per antenna -- for a receiver whose antennas see different delays.
+ *   TYPE1_AVG / TYPE2_AVG descriptors take no delay: 0.  Nothing is clamped: the estimator clamps where it reads the value.
+ * The call writes exactly n_rx int32 at est_delay[delay_off + a], the array the estimation calls read, and, where peak is given,
+ * the best that belongs to each delay at the same indices.  An all-zero symbol gives delay 0 and peak 0.
+ * This is the quantity the reference's fixed-point IDFT (oai_dfts.c) approximates, not a port of it: where two samples are closer
+ * than the transforms' errors the two may pick different samples.  Host form, kernel and the kernel run on the
+ * CPU perform the same IEEE operations in the same order and agree bit for bit, peaks included.
+ * mem = HOST stages the span of the grid the pilots lie in, as pusch_channel_estimation does.  mem = DEVICE enqueues two kinds of
+ * launches on `stream` (one search per fft_size, one combination) and returns; the first call per (GPU, fft_size) also allocates
+ * that size's twiddle table (fft_size + 4 float pairs, kept until the process ends) and uploads it with a synchronous copy, so
+ * it blocks: run one call per fft_size at start-up where the first slot must not wait.
+ * Refused before anything is enqueued or written: what pusch_channel_estimation refuses of n_rx, mem and the descriptors, a NULL
+ * rxdataF / seg / est_delay, an unknown flag, delay ranges [delay_off, delay_off + n_rx) of two descriptors that overlap, a
+ * misaligned or foreign device pointer, a capturing stream.
+ * pusch_est_delay_host: one descriptor over n_rx antennas on the CPU from the same header, no GPU (rx_off and delay_off apply). */
+#define NRLDPC_HIP_DELAY_RUNNING_MAX 0
+#define NRLDPC_HIP_DELAY_PER_ANTENNA 1
+int32_t nrLDPC_hip_pusch_est_delay(const int16_t *rxdataF, uint64_t rx_ant_stride, uint32_t n_rx, const nrLDPC_hip_chest_seg_t *seg, uint32_t n_seg,
+                                   uint32_t flags, int32_t *est_delay, float *peak, int32_t mem, void *stream);
+int32_t nrLDPC_hip_pusch_est_delay_host(const int16_t *rxdataF, uint64_t rx_ant_stride, uint32_t n_rx, const nrLDPC_hip_chest_seg_t *seg, uint32_t flags,
+                                        int32_t *est_delay, float *peak);
 /* ---------------------------------------------------------------------------------------------------
  * PDSCH resource mapping with DMRS onto the transmit grid: the resource mapping loop of nr_generate_pdsch (openair1/PHY/
  * NR_TRANSPORT/nr_dlsch.c:205-474) and its unit-precoding copy (:483-535) for one list of descriptors, one per (allocation, OFDM

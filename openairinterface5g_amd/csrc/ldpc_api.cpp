@@ -1539,5 +1539,6 @@ int32_t LDPCencoder(uint8_t **input, uint8_t **output, encoder_implemparams_t *i
 #include "rx_mmse_api.inc.cpp"
 #include "rx_ml_api.inc.cpp"
 #include "rx_chest_api.inc.cpp"
+#include "rx_delay_api.inc.cpp"
 #include "tx_map_api.inc.cpp"
 #include "tx_precode_api.inc.cpp"

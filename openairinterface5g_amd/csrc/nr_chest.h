@@ -38,7 +38,8 @@
  * nushift = (p >> 1) & 1 for both types (:89), delta = delta1[p] (nr_dmrs_rx.c:44).
  *
  * The delay is an input.  nr_est_delay (common/utils/nr/nr_common.c:968-990) finds it with a fixed-point IDFT that is not
- * rebuilt here; the caller passes est_delay per antenna.  Note that the reference clears delay_t once per call and not per
+ * rebuilt here; the caller passes est_delay per antenna, from nr_delay.h's fp32 search of the same LS values or from anywhere
+ * else.  Note that the reference clears delay_t once per call and not per
  * antenna (:152-153): its delay_max_val is a running maximum, so antenna a's delay there depends on antennas 0 .. a.
  * Delay tables (nr_common.c:906-928): row get_delay_idx(d) = clamp(20 + d, 0, 40), entry k = round(256 cexp(i 2 pi k d / N)).
  */

@@ -1754,6 +1754,62 @@ def pusch_chest_avg_segments(allocs, cap=None):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# The PUSCH delay search (include/nrLDPC_hip.h: pusch_est_delay and its host form; csrc/nr_delay.h)
+# ---------------------------------------------------------------------------------------------------------
+EXPORTS += ["nrLDPC_hip_pusch_est_delay", "nrLDPC_hip_pusch_est_delay_host"]
+DELAY_RUNNING_MAX, DELAY_PER_ANTENNA = 0, 1
+
+
+def _delay_lib():
+    L = _chest_lib()
+    P = C.POINTER(nrLDPC_hip_chest_seg_t)
+    L.nrLDPC_hip_pusch_est_delay.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.nrLDPC_hip_pusch_est_delay.restype = C.c_int32
+    L.nrLDPC_hip_pusch_est_delay_host.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, P, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.nrLDPC_hip_pusch_est_delay_host.restype = C.c_int32
+    return L
+
+
+def _delay_len(segs, n_rx):
+    return max([s.get("delay_off", 0) + n_rx for s in segs] + [1])
+
+
+def pusch_est_delay(rx, rx_ant_stride, n_rx, segs, flags=DELAY_RUNNING_MAX, est_delay=None, peak=None, stream=None):
+    """nrLDPC_hip_pusch_est_delay: rx = the OFDM grid, segs = the estimation's descriptors.  numpy int16 -> host call, returns
+    (est_delay int32, peak float32), each as long as the descriptors' delay_off + n_rx reach; torch int16 CUDA -> device call
+    enqueued on `stream` into `est_delay` (torch int32 CUDA, the array the estimation calls read) and, where given, `peak` (torch
+    float32 CUDA), returns (est_delay, peak)."""
+    n = _delay_len(segs, n_rx)
+    if isinstance(rx, np.ndarray):
+        assert rx.dtype == np.int16 and rx.flags.c_contiguous
+        est_delay, peak = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        ptr_d, ptr_p, mem, s, rx_len, rx_ptr = est_delay.ctypes.data, peak.ctypes.data, MEM_HOST, None, rx.size // 2, rx.ctypes.data
+    else:
+        import torch
+        ptr, numel, mem, s = _mem_of((rx,), stream, (est_delay,))
+        assert est_delay is not None and est_delay.numel() >= n
+        assert peak is None or (peak.is_cuda and peak.dtype == torch.float32 and peak.is_contiguous() and peak.device == rx.device and peak.numel() >= n)
+        ptr_d, ptr_p, rx_len, rx_ptr = est_delay.data_ptr(), None if peak is None else peak.data_ptr(), rx.numel() // 2, rx.data_ptr()
+    _chest_check_extent([dict(g, ch_off=0) for g in segs], n_rx, rx_ant_stride, 0, rx_len, 1 << 62, None)
+    _check(_delay_lib().nrLDPC_hip_pusch_est_delay(rx_ptr, rx_ant_stride, n_rx, _chest_seg_array(segs), len(segs), flags, ptr_d, ptr_p, mem, s),
+           "nrLDPC_hip_pusch_est_delay")
+    return est_delay, peak
+
+
+def pusch_est_delay_host(rx, rx_ant_stride, n_rx, seg, flags=DELAY_RUNNING_MAX):
+    """nrLDPC_hip_pusch_est_delay_host: one descriptor over n_rx antennas on the CPU (csrc/nr_delay.h, no GPU).  Returns (est_delay
+    int32[n_rx], peak float32[n_rx]) of the descriptor's antennas."""
+    assert rx.dtype == np.int16 and rx.flags.c_contiguous
+    _chest_check_extent([dict(seg, ch_off=0)], n_rx, rx_ant_stride, 0, rx.size // 2, 1 << 62, None)
+    n = _delay_len([seg], n_rx)
+    d, p = np.zeros(n, np.int32), np.zeros(n, np.float32)
+    _check(_delay_lib().nrLDPC_hip_pusch_est_delay_host(rx.ctypes.data, rx_ant_stride, n_rx, _chest_seg_array([seg]), flags, d.ctypes.data, p.ctypes.data),
+           "nrLDPC_hip_pusch_est_delay_host")
+    o = seg.get("delay_off", 0)
+    return d[o:o + n_rx], p[o:o + n_rx]
+
+
+# ---------------------------------------------------------------------------------------------------------
 # PDSCH resource mapping with DMRS (include/nrLDPC_hip.h: pdsch_resource_mapping and its host forms; csrc/nr_pdsch_map.h)
 # ---------------------------------------------------------------------------------------------------------
 EXPORTS += ["nrLDPC_hip_pdsch_resource_mapping", "nrLDPC_hip_pdsch_map_host", "nrLDPC_hip_pdsch_dmrs_host", "nrLDPC_hip_pdsch_map_segments"]
