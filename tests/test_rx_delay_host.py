@@ -82,6 +82,21 @@ FLAGS = (D.RUNNING_MAX, D.PER_ANTENNA)
 MIS_CASES = ("rb1", "peaks-t1", "peaks-t2", "nrx3-order", "ports", "wrap")
 
 
+def put_paths(rng, rx, s, at, re_offset, tau, amp):
+    """the pilots of interpolating descriptor s on the symbol that begins at c16 `at` of every antenna of rx [n_rx, stride, 2]: one
+    path of delay tau[a] and gain amp[a] per antenna, with light noise; re_offset = 12 times the allocation's first PRB"""
+    N, typ, port, k0 = s["fft_size"], s["mode"] & 1, s["port"], s["start_re"]
+    p = np.array(R.pusch_dmrs_rx(s["c_init"], port, s["rb_size"], re_offset, typ), np.float64)
+    k = np.arange(len(p))
+    sh = (port >> 1) & 1
+    re = 6 * (k // 2) + k % 2 if typ else 2 * k + sh                            # from the allocation's first RE
+    pos = (k0 + re) % N + (sh if typ else 0)                                    # type 2: the wrap comes before nushift
+    for a in range(len(rx)):
+        h = amp[a] * np.exp(-2j * np.pi * (re + (sh if typ else 0)) * tau[a] / N)
+        v = h * (p[:, 0] - 1j * p[:, 1]) / (23170.0 * np.sqrt(2.0)) + 30.0 * (rng.standard_normal(len(p)) + 1j * rng.standard_normal(len(p)))
+        rx[a, at + pos] = np.clip(np.rint(np.stack([v.real, v.imag], -1)), -32768, 32767)
+
+
 @functools.lru_cache(maxsize=None)
 def build(name):
     """the grid and descriptors of a case: rx int16 [n_rx, rx_stride, 2], segs with delay_off = 2 + i (n_rx + 1)"""
@@ -101,15 +116,7 @@ def build(name):
         if d["zero"]:
             rx[:, at:at + N] = 0
         elif not d["mode"] >> 1:
-            p = np.array(R.pusch_dmrs_rx(s["c_init"], port, rb, 12 * prb0, typ), np.float64)
-            k = np.arange(len(p))
-            sh = (port >> 1) & 1
-            re = 6 * (k // 2) + k % 2 if typ else 2 * k + sh                    # from the allocation's first RE
-            pos = (k0 + re) % N + (sh if typ else 0)                            # type 2: the wrap comes before nushift
-            for a in range(n_rx):
-                h = d["amp"][a] * np.exp(-2j * np.pi * (re + (sh if typ else 0)) * d["tau"][a] / N)
-                v = h * (p[:, 0] - 1j * p[:, 1]) / (23170.0 * np.sqrt(2.0)) + 30.0 * (rng.standard_normal(len(p)) + 1j * rng.standard_normal(len(p)))
-                rx[a, at + pos] = np.clip(np.rint(np.stack([v.real, v.imag], -1)), -32768, 32767)
+            put_paths(rng, rx, s, at, 12 * prb0, d["tau"], d["amp"])
         at += N
     rx.setflags(write=False)
     return dict(c, rx=rx, rx_stride=rx_stride, segs=segs, n_res=2 + len(segs) * (n_rx + 1))
